@@ -23,12 +23,21 @@ all-reduce advantage moments, per-epoch gradients/statistics and the ZFilter
 sums over RCCL (torch.distributed 'nccl'); every rank applies the update of the
 global batch.
 
-Prints ONE JSON line on rank 0: the metric (timed region = K plain learn()
-calls, no instrumentation), a roofline object for the dominant kernel
-(per-launch HIP events recorded by libsurreal_mi on the learner's stream in a
-separate instrumented pass of min(K, 5) learn() calls right after the timed
-region) and the CPU baseline (the oracle restatement, timed on this host on a
-bounded sample).
+Prints ONE JSON line on rank 0.  A plain run does only what the headline
+needs: set-up, the warm-up, the timed region (K plain learn() calls, no
+instrumentation), the line with the metric and ms_per_step.  --dump-outputs DIR
+also writes what the last timed step left with the caller (the published
+parameters and the statistics vector) as DIR/<name>.npy; the inputs are seeded,
+so two builds run with the same arguments compare array for array.
+
+--full adds everything measured in runs of its own: the fixed-work
+calibration launches and the clock samples around the timed region, the
+host-fed line, a roofline object for the dominant kernel (per-launch HIP
+events recorded by libsurreal_mi on the learner's stream in a separate
+instrumented pass of min(K, 5) learn() calls right after the timed region),
+the per-class and per-phase tables, and the CPU baseline (the oracle
+restatement, timed on this host on a bounded sample).  --no-calib, --clock,
+--no-host-batch, --no-cpu-baseline and --cpu-budget act within --full.
 """
 import argparse
 import copy
@@ -475,6 +484,42 @@ def cpu_baseline(name, lc, dims, budget_s=12.0, one_thread_budget_s=6.0):
                               f'after 3 warm-ups, median {med1 * 1e3:.1f} ms'}
 
 
+DUMP_MAX_BYTES = 64 << 20
+DUMP_MAX_ELEMS = 1 << 20          # per array; a larger one is written as a fixed seeded sample
+
+
+def snapshot_outputs(learner, extra=None):
+    """What learn() leaves with its caller, copied to the host: the statistics
+    vector of the last step and the state_dict() of every published module
+    (module_dict(): the parameters a publisher or a checkpoint receives), plus
+    the modules of `extra` ({name: module}).  Taken right after the timed
+    region, before any further learn()."""
+    arrays = {'stats': learner.stats_buf}
+    mods = dict(learner.module_dict())
+    mods.update(extra or {})
+    for mname, mod in mods.items():
+        for key, t in mod.state_dict().items():
+            arrays[f'{mname}.{key}'] = t
+    return {n: t.detach().cpu().numpy() for n, t in arrays.items()}
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <name>.npy per array, float32 as computed (anything
+    else as float64); an array above DUMP_MAX_ELEMS is written as the same
+    seeded sample of its elements in every run."""
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.random.RandomState(0).randint(0, a.size, DUMP_MAX_ELEMS)
+            a = a.reshape(-1)[idx]
+        total += a.nbytes
+        if total > DUMP_MAX_BYTES:
+            raise SystemExit(f'--dump-outputs: more than {DUMP_MAX_BYTES >> 20} MB of outputs')
+        np.save(os.path.join(path, name + '.npy'), a)
+
+
 DDPG_METRIC = 'DDPG learner env-steps/sec (replay sample + n-step target + critic/actor update)'
 
 
@@ -526,11 +571,12 @@ def run_ddpg(args):
             dist.barrier()
             torch.cuda.synchronize()
 
-    calib = None if args.no_calib else calibrate(dev)
+    measure_box = args.full and not args.no_calib
+    calib = calibrate(dev) if measure_box else None
     for _ in range(args.warmup):
         step()
     barrier()
-    probe = None if args.no_calib else make_clock(args.clock, dev)
+    probe = make_clock(args.clock, dev) if measure_box else None
     if probe is not None:
         probe.start()
     t0 = time.perf_counter()
@@ -547,27 +593,8 @@ def run_ddpg(args):
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-    # instrumented pass on an eager learner (graph replays carry no per-kernel
-    # events): same launches, same shapes
-    n_inst = min(args.steps, 5)
-    learner_e = DDPGLearner(llc, ec, seed=1, device=dev, dp=dp) if graph else learner
-
-    def step_e():
-        _, got = rep.sample(B, out=buf, rank=rank, world=world)
-        learner_e.learn(rep.split(got))
-
-    step_e()
-    torch.cuda.synchronize()
-    L.kernel_timing(True)
-    for _ in range(n_inst):
-        step_e()
-    torch.cuda.synchronize()
-    L.kernel_timing(False)
-    kt = L.kernel_timing_report()
-    kernels = kernel_table(kt, n_inst)
-    dom = mfma_dominant(kt)
-    c, ms_k, fl = kt[dom]
-    ach = fl / (ms_k * 1e-3) / 1e12
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, snapshot_outputs(learner, {'ddpg_target': learner.model_target}))
     out = {
         'metric': DDPG_METRIC, 'value': round(B * args.steps / elapsed, 1),
         'unit': 'env-steps/s', 'n_gpus': world, 'steps': args.steps, 'warmup': args.warmup,
@@ -580,20 +607,42 @@ def run_ddpg(args):
                    'batch': B, 'batch_per_rank': B // world, 'replay_rows': NREP,
                    'parallelism': f'dp{world}' if world > 1 else 'single',
                    'update': 'hipGraph replay' if graph else 'eager launches'},
-        'roofline': {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 3),
-                     'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
-                     'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 4), 'traffic': None,
-                     'avg_ms': round(ms_k / c, 5), 'algorithmic_flops_per_launch': int(fl / c)},
-        'kernels': kernels,
-        'kernels_sum': kernels_sum_note(kernels, elapsed / args.steps * 1e3),
     }
+    if args.full:
+        # instrumented pass on an eager learner (graph replays carry no
+        # per-kernel events): same launches, same shapes
+        n_inst = min(args.steps, 5)
+        learner_e = DDPGLearner(llc, ec, seed=1, device=dev, dp=dp) if graph else learner
+
+        def step_e():
+            _, got = rep.sample(B, out=buf, rank=rank, world=world)
+            learner_e.learn(rep.split(got))
+
+        step_e()
+        torch.cuda.synchronize()
+        L.kernel_timing(True)
+        for _ in range(n_inst):
+            step_e()
+        torch.cuda.synchronize()
+        L.kernel_timing(False)
+        kt = L.kernel_timing_report()
+        kernels = kernel_table(kt, n_inst)
+        dom = mfma_dominant(kt)
+        c, ms_k, fl = kt[dom]
+        ach = fl / (ms_k * 1e-3) / 1e12
+        out['roofline'] = {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 3),
+                           'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s',
+                           'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 4), 'traffic': None,
+                           'avg_ms': round(ms_k / c, 5), 'algorithmic_flops_per_launch': int(fl / c)}
+        out['kernels'] = kernels
+        out['kernels_sum'] = kernels_sum_note(kernels, elapsed / args.steps * 1e3)
     attach_calib(out, calib, clock)
     if dist is not None:
         barrier()
         dist.destroy_process_group()
     if rank != 0:
         return
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         out['cpu_baseline'] = cpu_baseline_ddpg(lc, rows, D, A, B, args.cpu_budget)
     print(json.dumps(out), flush=True)
 
@@ -664,6 +713,13 @@ def main():
     ap.add_argument('--config', choices=['c2', 'c3', 'c4', 'c5'], default='c3')
     ap.add_argument('--ppo-mode', choices=['adapt', 'clip'], default=None,
                     help='override the workload\'s PPO surrogate (A/B only; C2-C5 are adapt)')
+    ap.add_argument('--full', action='store_true',
+                    help='beside the headline: calibration launches and clock samples, the '
+                         'host-fed line, the instrumented passes (roofline, per-class and '
+                         'per-phase tables) and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps write what the last one computed (published '
+                         'parameters, statistics vector) as DIR/<name>.npy')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-calib', action='store_true',
                     help='skip the fixed-work calibration launches and the clock measurement')
@@ -725,11 +781,12 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    calib = None if args.no_calib else calibrate(dev)
+    measure_box = args.full and not args.no_calib
+    calib = calibrate(dev) if measure_box else None
     for i in range(args.warmup):
         learner.learn(pool[i % len(pool)])
     barrier()
-    probe = None if args.no_calib else make_clock(args.clock, dev)
+    probe = make_clock(args.clock, dev) if measure_box else None
     if probe is not None:
         probe.start()
     # timed region: the learner exactly as a caller runs it (no instrumentation)
@@ -748,8 +805,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     epochs_run = learner.last_stats()['epochs_run']
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, snapshot_outputs(learner))
     host_fed = None
-    if not args.no_host_batch:
+    if args.full and not args.no_host_batch:
         # the same learns fed as the reference's learn() is fed: numpy batches
         # (the aggregator's output) staged by the learner itself -- one pinned
         # buffer, one H2D per batch (StagingArena, ppo.py:420-484) -- timed like
@@ -772,79 +831,80 @@ def main():
                     'ms_per_step': round(he / args.steps * 1e3, 4),
                     'note': 'numpy batches -> StagingArena (every array packed into one pinned '
                             'buffer, one async H2D) -> learn(): PCIe-inclusive, not the headline'}
-    # instrumented pass (separate, after the timed region): per-launch HIP
-    # events of the MFMA kernels recorded by the library on the learner's
-    # stream, and per-phase torch events -> roofline / kernels / phases
-    n_inst = min(args.steps, 5)
-    learner.kernel_events = {}
-    if dp is not None:
-        dp.timing = []
-    L.kernel_timing(True)
-    for k in range(n_inst):
-        learner.learn(pool[k % len(pool)])
-    barrier()
-    L.kernel_timing(False)
-    ev = learner.kernel_events
-    learner.kernel_events = None
-    allreduce = None
-    if dp is not None:
-        # per-rank time inside the stream-ordered all-reduces (max over ranks)
-        ar_ms = sum(s_.elapsed_time(e_) for s_, e_, _ in dp.timing) / n_inst
-        ar_n = len(dp.timing) / n_inst
-        ar_b = sum(b_ for _, _, b_ in dp.timing) / n_inst
-        dp.timing = None
-        t = torch.tensor([ar_ms], dtype=torch.float64, device=dev)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        allreduce = {'ms_per_step_max_over_ranks': round(float(t.item()), 4),
-                     'calls_per_step': ar_n, 'bytes_per_step': int(ar_b),
-                     'backend': dist.get_backend()}
+    if args.full:
+        # instrumented pass (separate, after the timed region): per-launch HIP
+        # events of the MFMA kernels recorded by the library on the learner's
+        # stream, and per-phase torch events -> roofline / kernels / phases
+        n_inst = min(args.steps, 5)
+        learner.kernel_events = {}
+        if dp is not None:
+            dp.timing = []
+        L.kernel_timing(True)
+        for k in range(n_inst):
+            learner.learn(pool[k % len(pool)])
+        barrier()
+        L.kernel_timing(False)
+        ev = learner.kernel_events
+        learner.kernel_events = None
+        allreduce = None
+        if dp is not None:
+            # per-rank time inside the stream-ordered all-reduces (max over ranks)
+            ar_ms = sum(s_.elapsed_time(e_) for s_, e_, _ in dp.timing) / n_inst
+            ar_n = len(dp.timing) / n_inst
+            ar_b = sum(b_ for _, _, b_ in dp.timing) / n_inst
+            dp.timing = None
+            t = torch.tensor([ar_ms], dtype=torch.float64, device=dev)
+            dist.all_reduce(t, op=dist.ReduceOp.MAX)
+            allreduce = {'ms_per_step_max_over_ranks': round(float(t.item()), 4),
+                         'calls_per_step': ar_n, 'bytes_per_step': int(ar_b),
+                         'backend': dist.get_backend()}
 
-    # per-kernel (MFMA engine) classes from the library's own events, and the
-    # learner-level launches/phases from torch events on the same stream
-    kt = L.kernel_timing_report()
-    kernels = kernel_table(kt, n_inst)
-    # phases from a pass of their own (eager launches, no per-kernel events: the
-    # library's events inside the phases inflated them ~20 % over the wall time)
-    learner.kernel_events = {}
-    for k in range(n_inst):
-        learner.learn(pool[k % len(pool)])
-    barrier()
-    ev = learner.kernel_events
-    learner.kernel_events = None
-    phases = {n: round(float(np.sum([s.elapsed_time(e) for s, e in v])) / n_inst, 4)
-              for n, v in ev.items()}
-    rhbm = roofline_hbm(kt, n_inst)
-    if mfma_dominant(kt):
-        dom = mfma_dominant(kt)
-        c, ms, fl = kt[dom]
-        ach = fl / (ms * 1e-3) / 1e12
-        traffic, tsrc = pmc_traffic(args.config, dom)
-        roof = {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 3),
-                'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 4),
-                'traffic': traffic, 'avg_ms': round(ms / c, 5),
-                'algorithmic_flops_per_launch': int(fl / c)}
-        if traffic is not None:
-            roof['traffic_unit'] = 'HBM bytes per launch'
-            roof['traffic_source'] = tsrc + ' (PMC passes of this command, launch-weighted over the class)'
-    else:
-        # C2: the fused single-CU epoch kernel dominates
-        kdur = {n: float(np.mean([s.elapsed_time(e) for s, e in v])) for n, v in ev.items()}
-        dom = max(kdur, key=kdur.get)
-        a_h1, a_h2 = lc.model.actor_fc_hidden_sizes
-        c_h1, c_h2 = lc.model.critic_fc_hidden_sizes
-        af, ab = mlp_flops_per_row(D, a_h1, a_h2, A)
-        cf, cb = mlp_flops_per_row(D, c_h1, c_h2, 1)
-        E_v = lc.algo.consts.epoch_baseline
-        flops = {
-            'ppo_fused_kernel': B * (af * (epochs_run + 2) + ab * epochs_run) + B * E_v * (cf + cb),
-            'critic_gae_kernel': B * (T + 1) * cf,
-            'ppo_epoch_grad_kernel': B * (af + ab + cf + cb),
-        }
-        fl = flops.get(dom, 0)
-        ach = fl / (kdur[dom] * 1e-3) / 1e12
-        roof = {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 6), 'peak': FP32_MFMA_PEAK_TFLOPS,
-                'unit': 'TFLOP/s', 'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 8), 'traffic': None,
-                'avg_ms': round(kdur[dom], 5), 'algorithmic_flops_per_launch': int(fl)}
+        # per-kernel (MFMA engine) classes from the library's own events, and the
+        # learner-level launches/phases from torch events on the same stream
+        kt = L.kernel_timing_report()
+        kernels = kernel_table(kt, n_inst)
+        # phases from a pass of their own (eager launches, no per-kernel events: the
+        # library's events inside the phases inflated them ~20 % over the wall time)
+        learner.kernel_events = {}
+        for k in range(n_inst):
+            learner.learn(pool[k % len(pool)])
+        barrier()
+        ev = learner.kernel_events
+        learner.kernel_events = None
+        phases = {n: round(float(np.sum([s.elapsed_time(e) for s, e in v])) / n_inst, 4)
+                  for n, v in ev.items()}
+        rhbm = roofline_hbm(kt, n_inst)
+        if mfma_dominant(kt):
+            dom = mfma_dominant(kt)
+            c, ms, fl = kt[dom]
+            ach = fl / (ms * 1e-3) / 1e12
+            traffic, tsrc = pmc_traffic(args.config, dom)
+            roof = {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 3),
+                    'peak': FP32_MFMA_PEAK_TFLOPS, 'unit': 'TFLOP/s', 'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 4),
+                    'traffic': traffic, 'avg_ms': round(ms / c, 5),
+                    'algorithmic_flops_per_launch': int(fl / c)}
+            if traffic is not None:
+                roof['traffic_unit'] = 'HBM bytes per launch'
+                roof['traffic_source'] = tsrc + ' (PMC passes of this command, launch-weighted over the class)'
+        else:
+            # C2: the fused single-CU epoch kernel dominates
+            kdur = {n: float(np.mean([s.elapsed_time(e) for s, e in v])) for n, v in ev.items()}
+            dom = max(kdur, key=kdur.get)
+            a_h1, a_h2 = lc.model.actor_fc_hidden_sizes
+            c_h1, c_h2 = lc.model.critic_fc_hidden_sizes
+            af, ab = mlp_flops_per_row(D, a_h1, a_h2, A)
+            cf, cb = mlp_flops_per_row(D, c_h1, c_h2, 1)
+            E_v = lc.algo.consts.epoch_baseline
+            flops = {
+                'ppo_fused_kernel': B * (af * (epochs_run + 2) + ab * epochs_run) + B * E_v * (cf + cb),
+                'critic_gae_kernel': B * (T + 1) * cf,
+                'ppo_epoch_grad_kernel': B * (af + ab + cf + cb),
+            }
+            fl = flops.get(dom, 0)
+            ach = fl / (kdur[dom] * 1e-3) / 1e12
+            roof = {'kernel': dom, 'bound': 'mfma', 'achieved': round(ach, 6), 'peak': FP32_MFMA_PEAK_TFLOPS,
+                    'unit': 'TFLOP/s', 'frac': round(ach / FP32_MFMA_PEAK_TFLOPS, 8), 'traffic': None,
+                    'avg_ms': round(kdur[dom], 5), 'algorithmic_flops_per_launch': int(fl)}
     ms = elapsed / args.steps * 1e3
     value = world * B * T * args.steps / elapsed
     split = (f'{dims["B_global"]} segments split over {world} GPU(s) ({B} per GPU)'
@@ -870,19 +930,18 @@ def main():
                    'parallelism': f'dp{world}' if world > 1 else 'single',
                    'epochs_run_last': epochs_run, 'ppo_mode': lc.algo.ppo_mode,
                    'launch': 'hipGraph replay' if learner._graph is not None else 'eager'},
-        'roofline': roof,
-        'kernels': kernels,
-        'kernels_sum': kernels_sum_note(kernels, ms),
-        'phase_ms_per_step': phases,
     }
+    if args.full:
+        out.update({'roofline': roof, 'kernels': kernels,
+                    'kernels_sum': kernels_sum_note(kernels, ms), 'phase_ms_per_step': phases})
+        if rhbm is not None:
+            out['roofline_hbm'] = rhbm
+        if allreduce is not None:
+            out['allreduce'] = allreduce
     attach_calib(out, calib, clock)
-    if rhbm is not None:
-        out['roofline_hbm'] = rhbm
-    if allreduce is not None:
-        out['allreduce'] = allreduce
     if host_fed is not None:
         out['host_fed'] = host_fed
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline(args.config, make_config(args.config)[0], dims,
                                            args.cpu_budget)
     if rank == 0:

@@ -101,7 +101,7 @@ def make(case):
             arrays[key] = r.astype(np.float32)
         print(f'{case} learn {it}: {time.time() - t0:.1f} s, epochs_run {s64["epochs_run"]}', flush=True)
     P.save_fixture(case, meta, arrays)
-    print(f'wrote {P.fixture_path(case)}', flush=True)
+    print('wrote ' + ' '.join(P.fixture_parts(case)), flush=True)
 
 
 if __name__ == '__main__':

@@ -58,7 +58,9 @@ Three pieces, shared by the GPU tests and by tests/golden/make_envelopes.py:
    uninformative: a frozen tensor scores 1.0 on both.  tests/negative_controls.py
    shows the checks failing on deliberately faulty learners.
 """
+import glob
 import hashlib
+import io
 import json
 import os
 
@@ -433,14 +435,43 @@ def fixture_path(case):
     return os.path.join(GOLDEN, f'envelope_{case}.npz')
 
 
+FIXTURE_PART_BYTES = 1000000     # no committed file above 1 MiB
+
+
+def fixture_parts(case):
+    """the files that hold the case's .npz: the file itself, or, for one above
+    FIXTURE_PART_BYTES, its bytes cut into envelope_<case>.npz.00, .01, ..."""
+    path = fixture_path(case)
+    return [path] if os.path.exists(path) else sorted(glob.glob(glob.escape(path) + '.[0-9][0-9]'))
+
+
 def save_fixture(case, meta, arrays):
     arrays = {k: np.asarray(v) for k, v in arrays.items()}
     arrays['meta'] = np.frombuffer(json.dumps(meta, sort_keys=True).encode(), dtype=np.uint8)
-    np.savez_compressed(fixture_path(case), **arrays)
+    buf = io.BytesIO()
+    np.savez_compressed(buf, **arrays)
+    data = buf.getvalue()
+    for old in fixture_parts(case):
+        os.remove(old)
+    path = fixture_path(case)
+    if len(data) <= FIXTURE_PART_BYTES:
+        chunks = {path: data}
+    else:
+        chunks = {f'{path}.{i:02d}': data[o:o + FIXTURE_PART_BYTES]
+                  for i, o in enumerate(range(0, len(data), FIXTURE_PART_BYTES))}
+    for p, chunk in chunks.items():
+        with open(p, 'wb') as f:
+            f.write(chunk)
 
 
 def load_fixture(case):
-    with np.load(fixture_path(case), allow_pickle=False) as z:
+    parts = fixture_parts(case)
+    assert parts, f'no fixture for case {case}'
+    data = b''
+    for p in parts:
+        with open(p, 'rb') as f:
+            data += f.read()
+    with np.load(io.BytesIO(data), allow_pickle=False) as z:
         d = {k: z[k] for k in z.files}
     meta = json.loads(bytes(d.pop('meta')).decode())
     return meta, d

@@ -32,3 +32,25 @@ def test_strong_scaling_split():
             assert dims['B_global'] % n == 0
     lc, ec, dims = bench.make_config('c2')
     assert dims['B_global'] == 64 and lc.replay.batch_size == 64
+
+
+def test_dump_outputs_writes_float_arrays(tmp_path):
+    """--dump-outputs: float32 kept, everything else float64, an array above the
+    per-array cap written as the same seeded sample every time."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rng = np.random.RandomState(1)
+    big = rng.randn(bench.DUMP_MAX_ELEMS + 17).astype(np.float32)
+    arrays = {'stats': rng.randn(5).astype(np.float32), 'ppo.z_filter.count': np.array([7], dtype=np.int64),
+              'ppo.big.weight': big}
+    for d in ('a', 'b'):
+        bench.dump_outputs(str(tmp_path / d), arrays)
+    got = {n: np.load(tmp_path / 'a' / (n + '.npy')) for n in arrays}
+    assert sorted(os.listdir(tmp_path / 'a')) == sorted(n + '.npy' for n in arrays)
+    assert got['stats'].dtype == np.float32 and np.array_equal(got['stats'], arrays['stats'])
+    assert got['ppo.z_filter.count'].dtype == np.float64 and got['ppo.z_filter.count'][0] == 7.0
+    assert got['ppo.big.weight'].shape == (bench.DUMP_MAX_ELEMS,)
+    assert np.isin(got['ppo.big.weight'], big).all()
+    assert np.array_equal(got['ppo.big.weight'], np.load(tmp_path / 'b' / 'ppo.big.weight.npy'))
+    assert sum(a.nbytes for a in got.values()) <= bench.DUMP_MAX_BYTES

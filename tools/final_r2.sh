@@ -12,15 +12,15 @@ tests)
   tail -3 $OUT/smoke.log ;;
 bench)
   for c in c3 c5 c2 c4; do
-    timeout -k 10 300 python -u bench.py --config $c --steps 20 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || exit 1
+    timeout -k 10 300 python -u bench.py --full --config $c --steps 20 --warmup 3 > $OUT/bench_$c.json 2> $OUT/bench_$c.err || exit 1
     cut -c1-300 $OUT/bench_$c.json
   done
-  timeout -k 10 300 python -u bench.py --config c3 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c3_local128.json 2> $OUT/bench_c3_local128.err || exit 1
-  SMI_PANEL_MIN_ROWS=4096 timeout -k 10 300 python -u bench.py --config c3 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c3_local128_nopanel.json 2> $OUT/bench_c3_local128_nopanel.err || exit 1
-  timeout -k 10 300 python -u bench.py --config c5 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c5_local128.json 2> $OUT/bench_c5_local128.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --config c3 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c3_local128.json 2> $OUT/bench_c3_local128.err || exit 1
+  SMI_PANEL_MIN_ROWS=4096 timeout -k 10 300 python -u bench.py --full --config c3 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c3_local128_nopanel.json 2> $OUT/bench_c3_local128_nopanel.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --config c5 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/bench_c5_local128.json 2> $OUT/bench_c5_local128.err || exit 1
   # streaming kernels at > 256 MB working sets inside learn(): 65536 segments
-  timeout -k 10 300 python -u bench.py --config c3 --local-segments 65536 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c3_local65536.json 2> $OUT/bench_c3_local65536.err || exit 1
-  SMI_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_dp2_gloo.json 2> $OUT/bench_c3_dp2_gloo.err || exit 1
+  timeout -k 10 300 python -u bench.py --full --config c3 --local-segments 65536 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_c3_local65536.json 2> $OUT/bench_c3_local65536.err || exit 1
+  SMI_DIST_BACKEND=gloo timeout -k 10 300 python -u bench.py --full --gpus 2 --steps 10 --warmup 2 --no-cpu-baseline > $OUT/bench_c3_dp2_gloo.json 2> $OUT/bench_c3_dp2_gloo.err || exit 1
   timeout -k 10 300 python -u tools/bench_hbm.py --iters 20 > $OUT/hbm_sweep.jsonl 2> $OUT/hbm_sweep.err || exit 1
   cut -c1-200 $OUT/hbm_sweep.jsonl
   cut -c1-300 $OUT/bench_c3_local128.json ;;

@@ -77,11 +77,11 @@ case "$what" in
   final)
     tests
     smoke
-    bench bench_default
-    bench bench_c3_local128 --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline
-    bench bench_c5 --config c5 --steps 5 --warmup 2 --no-cpu-baseline
-    bench bench_c2 --config c2 --no-cpu-baseline
-    bench bench_c4 --config c4 --no-cpu-baseline
+    bench bench_default --full
+    bench bench_c3_local128 --full --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline
+    bench bench_c5 --full --config c5 --steps 5 --warmup 2 --no-cpu-baseline
+    bench bench_c2 --full --config c2 --no-cpu-baseline
+    bench bench_c4 --full --config c4 --no-cpu-baseline
     kt c3 --config c3 --steps 10 --warmup 3 --no-cpu-baseline
     pmc c3 --config c3 --steps 5 --warmup 2 --no-cpu-baseline ;;
   *) die "unknown step $what" ;;

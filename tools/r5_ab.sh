@@ -19,7 +19,7 @@ for rep in 1 2; do
   i=0
   for arm in "$@"; do
     i=$((i + 1))
-    timeout -k 10 300 env $arm python -u bench.py $BARGS --no-cpu-baseline --no-host-batch \
+    timeout -k 10 300 env $arm python -u bench.py --full $BARGS --no-cpu-baseline --no-host-batch \
         > $OUT/arm${i}_$rep.json 2> $OUT/arm${i}_$rep.err || { tail -5 $OUT/arm${i}_$rep.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$OUT/arm${i}_$rep.json')); k=d.get('kernels', {})

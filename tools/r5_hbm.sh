@@ -4,7 +4,7 @@
 set -o pipefail
 OUT=gpurun_out/${1:-r5ap}; mkdir -p $OUT; export TMPDIR=/tmp
 for arm in SMI_STATS_LEAN=0 SMI_STATS_LEAN=1; do
-  timeout -k 10 600 env $arm python -u bench.py --local-segments 65536 --steps 3 --warmup 1 --no-cpu-baseline \
+  timeout -k 10 600 env $arm python -u bench.py --full --local-segments 65536 --steps 3 --warmup 1 --no-cpu-baseline \
       --no-host-batch > $OUT/bench_c3_65536_$arm.json 2> $OUT/err_$arm.log || { tail -5 $OUT/err_$arm.log; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/bench_c3_65536_$arm.json')); print('$arm', d['ms_per_step'], {k: (v.get('hbm_frac'), round(v['avg_ms']*1e3, 1)) for k, v in d['kernels'].items() if 'hbm_frac' in v})"

@@ -21,7 +21,7 @@ for l in open(sys.argv[1]):
         print(d['segments'], d['knobs'], 'dirty' if d['dirty'] else 'clean', d['steps'], d['fwd_us'], d['fwd_x_us'], d['bwd_us'])
 PY
 if [ "$2" = bench ]; then
-  timeout -k 10 300 python -u bench.py --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline \
+  timeout -k 10 300 python -u bench.py --full --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline \
       --no-host-batch > $OUT/l128.json 2> $OUT/l128.err || { tail -5 $OUT/l128.err; exit 1; }
   python3 -c "
 import json; d=json.load(open('$OUT/l128.json')); k=d.get('kernels', {})

@@ -13,7 +13,7 @@ SMI_PARITY_REPORT=$OUT/parity_report.json timeout -k 10 1100 python -u -m pytest
 rc=$?
 tail -15 $OUT/tests.log
 [ $rc -eq 0 ] || [ $rc -eq 1 ] || { echo "pytest aborted rc=$rc"; exit 1; }
-timeout -k 10 600 python -u bench.py --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/l128.json 2> $OUT/l128.err || exit 1
+timeout -k 10 600 python -u bench.py --full --local-segments 128 --steps 20 --warmup 3 --no-cpu-baseline > $OUT/l128.json 2> $OUT/l128.err || exit 1
 cut -c1-400 $OUT/l128.json
-timeout -k 10 600 python -u bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || exit 1
+timeout -k 10 600 python -u bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/c3.json 2> $OUT/c3.err || exit 1
 cut -c1-400 $OUT/c3.json

@@ -11,7 +11,7 @@ for rep in 1 2; do
   for arm in "$@"; do
     envs=(); [ "$arm" != base ] && IFS=, read -ra envs <<< "$arm"
     n=$(echo "$arm" | tr '=,' '__')
-    timeout -k 10 300 env "${envs[@]}" python -u bench.py "${args[@]}" --no-cpu-baseline --no-host-batch \
+    timeout -k 10 300 env "${envs[@]}" python -u bench.py --full "${args[@]}" --no-cpu-baseline --no-host-batch \
       > $OUT/ab_${n}_$rep.json 2> $OUT/ab_${n}_$rep.err || { tail -5 $OUT/ab_${n}_$rep.err; exit 1; }
     python3 -c "
 import json; d=json.load(open('$OUT/ab_${n}_$rep.json')); k=d['kernels']
