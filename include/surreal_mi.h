@@ -36,6 +36,35 @@ extern "C" {
 int         smi_version(void);
 const char* smi_last_error(void);
 
+/* The form (kernel name + the template instantiation the host dispatch chose)
+ * of the calling thread's last kernel launch: "" before any launch, a static
+ * string otherwise (never freed; an entry point that returns without launching
+ * leaves it unchanged).  Host bookkeeping only, for tests that must know which
+ * instantiation a shape selected.  A call of several launches reports the last
+ * one (a split-K GEMM: its reducer, which names the kernel it reduces).
+ * Spelling, stable: kernel<template arguments in declaration order>, with
+ * flags as words.  The forms of the LSTM, head, GEMM and GAE launchers
+ * ("Dispatch coverage", lists what selects each):
+ *   lstm_fwd_q_kernel<KQ,XQ,xm|xv,wW[,a4]>  KQ 16|26|28|32 k per lane, XQ 0|12|16
+ *       x columns per lane (0: xproj input), xm / xv matrix-core / VALU x
+ *       parts, wW the W_hh load layout 0|1|2, a4 every gate in every lane
+ *   lstm_fwd_r4_kernel<KP,KX[,vf]>          KP 32|64|104|128, KX 0|48|64 fused x
+ *       width (0: xproj input), vf the fixed-width row loads
+ *   lstm_fwd_kernel<U>  lstm_fwd_reg_kernel<KS>  lstm_fwd_v_kernel<R,KP,KX>
+ *   lstm_bwd_q_kernel<BR[,stg]>  lstm_bwd_v_kernel<R,KP>  lstm_bwd_r4_kernel<KW>
+ *   lstm_bwd_kernel<U>  lstm_bwd_reg_kernel<KS>
+ *   head_fwd_kernel<N1,N2,rt1|rt2[,ps]>     layer-1 / layer-2 width slots, row
+ *       tiles per workgroup, ps the statistics epilogue
+ *   head_bwd_kernel<NA,NB,rt1|rt2[,pg]>     h1 / dX width slots, pg the policy prologue
+ *   gemm_panel_kernel<fwd|dx,C>             C 16-column tiles per column group
+ *   gemm_smallk_fwd_kernel<KU>  dx_smallk_kernel<KK[,v4][,a4]>
+ *   gemm_t16_kernel<fwd|dx>  gemm_kernel<fwd|dx|dw>  gemm_dw128_kernel
+ *   gemm_dwd_kernel  gemm_dwd_group_kernel  gemm_dwt16_kernel  gemm_group_reduce_kernel
+ *   gemm_splitk_reduce_kernel<PRODUCER>     PRODUCER the split-K kernel's own form
+ *   gae_seg_kernel  gae_rows_kernel<TPR>  gae_windows_kernel<lgN>  N lanes per window
+ * Other launches report the bare kernel name. */
+const char* smi_last_launch(void);
+
 /* Device scratch for the multi-workgroup reductions (ZFilter column partials,
  * Adam norm partials, split-K GEMM partials).  The caller allocates
  * smi_workspace_bytes() of device memory and registers it.
@@ -519,7 +548,11 @@ int smi_ppo_rnn_phase(const smi_ppo_rnn_args* args, int phase, int epoch, void* 
  *            hbuf[0] = h0, hbuf[t+1] = h_t ([S+1][B][H]); cbuf likewise and
  *            gates_act [S][B][4H] (activated) when non-NULL.
  *   backward: dgates [S][B][4H] from dh [S][B][H] (dL/dh_t from the heads),
- *            given gates_act and cbuf of the forward (BPTT through c and h). */
+ *            given gates_act and cbuf of the forward (BPTT through c and h).
+ *   S == 0 (no step): smi_lstm_forward writes row 0 of hbuf / cbuf (h0 / c0)
+ *            and nothing else (no form reads xproj or touches row 1 there);
+ *            smi_lstm_forward_x and smi_lstm_backward launch nothing and leave
+ *            every buffer untouched.  All three return 0. */
 int smi_lstm_forward(const float* xproj, const float* w_hh, const float* b_hh,
                      const float* h0, const float* c0, int S, int B, int H,
                      float* hbuf, float* cbuf, float* gates_act, void* stream);

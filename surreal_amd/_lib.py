@@ -120,6 +120,7 @@ def kernel_timing_report():
 _SIGS = {
     'smi_version': (c_int, []),
     'smi_last_error': (ctypes.c_char_p, []),
+    'smi_last_launch': (ctypes.c_char_p, []),
     'smi_workspace_bytes': (c_i64, []),
     'smi_set_workspace': (c_int, [P, c_i64]),
     'smi_context_create': (P, [P, c_i64]),

@@ -10,6 +10,9 @@
 namespace smi {
 
 static thread_local char g_err[512] = "";
+// the form name of this thread's last launch (smi_last_launch): a literal the
+// dispatch site passed to check_launch, never freed
+static thread_local const char* g_last_launch = "";
 
 int set_error(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
@@ -17,6 +20,7 @@ int set_error(int code, const char* msg) {
 }
 
 int check_launch(const char* what) {
+  g_last_launch = what;
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     snprintf(g_err, sizeof(g_err), "%s: %s", what, hipGetErrorString(e));
@@ -163,6 +167,7 @@ extern "C" {
 
 int smi_version(void) { return 1; }
 const char* smi_last_error(void) { return g_err; }
+const char* smi_last_launch(void) { return g_last_launch; }
 
 /* Registers the device scratch used by the multi-workgroup reductions
  * (colstats partials, Adam norm partials).  Not part of the reference API. */

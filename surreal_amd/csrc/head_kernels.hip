@@ -861,14 +861,17 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
   const dim3 grid((unsigned)((rows + R - 1) / R));
   const int n1 = hc_nt(h1), n2 = hc_nt(h2);
   const int kslot = ktime_begin(st);
+  const char* form = "head_fwd_kernel";          // the instantiation launched (smi_last_launch)
 #define SMI_HFP(A, B, P)                                                                \
   do {                                                                                  \
     if (rt == 2) {                                                                      \
       allow_lds(head_fwd_kernel<A, B, 2, P>, lds);                                      \
       hipLaunchKernelGGL((head_fwd_kernel<A, B, 2, P>), grid, dim3(kWG), lds, st, a);   \
+      form = P ? "head_fwd_kernel<" #A "," #B ",rt2,ps>" : "head_fwd_kernel<" #A "," #B ",rt2>"; \
     } else {                                                                            \
       allow_lds(head_fwd_kernel<A, B, 1, P>, lds);                                      \
       hipLaunchKernelGGL((head_fwd_kernel<A, B, 1, P>), grid, dim3(kWG), lds, st, a);   \
+      form = P ? "head_fwd_kernel<" #A "," #B ",rt1,ps>" : "head_fwd_kernel<" #A "," #B ",rt1>"; \
     }                                                                                   \
   } while (0)
 #define SMI_HF(A, B) SMI_HFP(A, B, false)
@@ -876,7 +879,7 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
     SMI_HFP(5, 4, true);
     ktime_end(kslot, KT_GEMM_FWD,
               2.0 * (double)rows * ((double)in * h1 + (double)h1 * h2 + (double)h2 * out), st);
-    return check_launch("head_fwd_kernel");
+    return check_launch(form);
   }
   // layer-1 slots {2, 5, 8} x layer-2 slots {2, 3, 4, 5, 8} (C3 / C5: 300 x 200 -> 5, 4)
   const int m1 = n1 <= 2 ? 2 : n1 <= 5 ? 5 : 8;
@@ -898,7 +901,7 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
 #undef SMI_HFP
   ktime_end(kslot, KT_GEMM_FWD,
             2.0 * (double)rows * ((double)in * h1 + (double)h1 * h2 + (double)h2 * out), st);
-  return check_launch("head_fwd_kernel");
+  return check_launch(form);
 }
 
 int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W3,
@@ -919,14 +922,17 @@ int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W
   na = na <= 2 ? 2 : na <= 5 ? 5 : 8;
   nb = nb <= 2 ? 2 : 5;
   const int kslot = ktime_begin(st);
+  const char* form = "head_bwd_kernel";
 #define SMI_HB2(A, B, P)                                                               \
   do {                                                                                 \
     if (rt == 2) {                                                                     \
       allow_lds(head_bwd_kernel<A, B, 2, P>, lds);                                     \
       hipLaunchKernelGGL((head_bwd_kernel<A, B, 2, P>), grid, dim3(kWG), lds, st, a);  \
+      form = P ? "head_bwd_kernel<" #A "," #B ",rt2,pg>" : "head_bwd_kernel<" #A "," #B ",rt2>"; \
     } else {                                                                           \
       allow_lds(head_bwd_kernel<A, B, 1, P>, lds);                                     \
       hipLaunchKernelGGL((head_bwd_kernel<A, B, 1, P>), grid, dim3(kWG), lds, st, a);  \
+      form = P ? "head_bwd_kernel<" #A "," #B ",rt1,pg>" : "head_bwd_kernel<" #A "," #B ",rt1>"; \
     }                                                                                  \
   } while (0)
 #define SMI_HB(A, B)                                                                   \
@@ -944,7 +950,7 @@ int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W
 #undef SMI_HB2
   ktime_end(kslot, KT_GEMM_DX,
             2.0 * (double)rows * ((double)out * h2 + (double)h2 * h1 + (double)h1 * dxn), st);
-  return check_launch("head_bwd_kernel");
+  return check_launch(form);
 }
 
 }  // namespace smi

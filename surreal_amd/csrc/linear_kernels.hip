@@ -522,8 +522,10 @@ static int launch_smallk_fwd(const float* X, int64_t ldx, int M, int K, const fl
   const size_t lds = ((size_t)N * (4 * nku + 1) + ((N + 3) & ~3) + 4 * 16 * 68) * 4;
   const int tiles = (M + 63) / 64;
   const int kslot = ktime_begin(st);
+  const char* form = "gemm_smallk_fwd_kernel";
 #define SMI_SK_CASE(V)                                                                         \
   if (nku == V) {                                                                              \
+    form = "gemm_smallk_fwd_kernel<" #V ">";                                                   \
     auto k = gemm_smallk_fwd_kernel<V>;                                                        \
     allow_lds(k, lds);                                                                         \
     static int cap = 0;                                                                        \
@@ -535,7 +537,7 @@ static int launch_smallk_fwd(const float* X, int64_t ldx, int M, int K, const fl
   SMI_SK_CASE(4) SMI_SK_CASE(8) SMI_SK_CASE(12) SMI_SK_CASE(16)
 #undef SMI_SK_CASE
   ktime_end(kslot, KT_GEMM_FWD, 2.0 * M * (double)N * K, st);
-  return check_launch("gemm_smallk_fwd_kernel");
+  return check_launch(form);
 }
 
 // Weight-gradient GEMM with 128x128 output tiles (dW[m][n] = sum_r dY[r][m]
@@ -1495,7 +1497,8 @@ static int dwd_waves() {
   return w;
 }
 
-static int splitk_reduce(const GemmArgs& g, int S, int epi, hipStream_t st);
+// what: "gemm_splitk_reduce_kernel<the producer's form>" (smi_last_launch)
+static int splitk_reduce(const GemmArgs& g, int S, int epi, hipStream_t st, const char* what);
 
 // weight gradient over row-major dY / X (a_rs == 1, b_cs == 1): gemm_dwd_kernel
 static int dwd_launch(GemmArgs g, hipStream_t st) {
@@ -1549,7 +1552,7 @@ static int dwd_launch(GemmArgs g, hipStream_t st) {
             2.0 * g.M * (double)nreal * g.K + (g.ones_col >= 0 ? (double)g.M * g.K : 0.0), st);
   const int rc = check_launch("gemm_dwd_kernel");
   if (rc || S == 1) return rc;
-  return splitk_reduce(g, S, EPI_DW, st);
+  return splitk_reduce(g, S, EPI_DW, st, "gemm_splitk_reduce_kernel<gemm_dwd_kernel>");
 }
 
 // ---- grouped weight gradients (gemm_dwd_group_kernel) ----------------------
@@ -2043,16 +2046,21 @@ static int use_panel() {
   return u;
 }
 
+// returns the launched instantiation's name (smi_last_launch)
 template <int EPI>
-static void panel_dispatch(const GemmArgs& g, dim3 grid, int ntw, hipStream_t st) {
+static const char* panel_dispatch(const GemmArgs& g, dim3 grid, int ntw, hipStream_t st) {
+#define SMI_PN(C)                                                                      \
+  hipLaunchKernelGGL((gemm_panel_kernel<EPI, C>), grid, dim3(kWG), 0, st, g);          \
+  return EPI == EPI_FWD ? "gemm_panel_kernel<fwd," #C ">" : "gemm_panel_kernel<dx," #C ">"
   switch (ntw) {
-    case 1: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 1>), grid, dim3(kWG), 0, st, g); break;
-    case 2: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 2>), grid, dim3(kWG), 0, st, g); break;
-    case 4: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 4>), grid, dim3(kWG), 0, st, g); break;
-    case 5: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 5>), grid, dim3(kWG), 0, st, g); break;
-    case 7: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 7>), grid, dim3(kWG), 0, st, g); break;
-    default: hipLaunchKernelGGL((gemm_panel_kernel<EPI, 10>), grid, dim3(kWG), 0, st, g); break;
+    case 1: SMI_PN(1);
+    case 2: SMI_PN(2);
+    case 4: SMI_PN(4);
+    case 5: SMI_PN(5);
+    case 7: SMI_PN(7);
+    default: SMI_PN(10);
   }
+#undef SMI_PN
 }
 
 // tall forward / input-gradient GEMMs with 16-byte operands: gemm_panel_kernel
@@ -2095,10 +2103,10 @@ static int panel_launch(int epi, const GemmArgs& g, hipStream_t st) {
   }
   const dim3 grid((g.M + 63) / 64, (g.N + 16 * best - 1) / (16 * best), 1);
   const int kslot = ktime_begin(st);
-  if (epi == EPI_FWD) panel_dispatch<EPI_FWD>(g, grid, best, st);
-  else panel_dispatch<EPI_DX>(g, grid, best, st);
+  const char* form = epi == EPI_FWD ? panel_dispatch<EPI_FWD>(g, grid, best, st)
+                                    : panel_dispatch<EPI_DX>(g, grid, best, st);
   ktime_end(kslot, epi == EPI_FWD ? KT_GEMM_FWD : KT_GEMM_DX, 2.0 * g.M * (double)g.N * g.K, st);
-  return check_launch("gemm_panel_kernel");
+  return check_launch(form);
 }
 
 // Input gradient through a layer with at most 8 outputs (the value head's
@@ -2188,20 +2196,25 @@ static int dx_smallk_launch(const GemmArgs& g, hipStream_t st) {
   const int64_t n = (int64_t)((g.M + 3) / 4) * ((g.N + 3) / 4);
   const dim3 grid((unsigned)((n + kWG - 1) / kWG));
   const int kslot = ktime_begin(st);
+  const char* form;
 #define SMI_DXS(KK)                                                                        \
   do {                                                                                     \
     if (v4) hipLaunchKernelGGL((dx_smallk_kernel<KK, true>), grid, dim3(kWG), 0, st, g);   \
     else hipLaunchKernelGGL((dx_smallk_kernel<KK, false>), grid, dim3(kWG), 0, st, g);     \
+    form = v4 ? "dx_smallk_kernel<" #KK ",v4>" : "dx_smallk_kernel<" #KK ">";              \
   } while (0)
   const bool a4 = (g.K == 4 || g.K == 8) && g.a_rs % 4 == 0 && al16(g.A);
   if (g.K == 1) SMI_DXS(1);
   else if (g.K <= 2) SMI_DXS(2);
-  else if (g.K == 8 && a4 && v4) hipLaunchKernelGGL((dx_smallk_kernel<8, true, true>), grid, dim3(kWG), 0, st, g);
+  else if (g.K == 8 && a4 && v4) {
+    hipLaunchKernelGGL((dx_smallk_kernel<8, true, true>), grid, dim3(kWG), 0, st, g);
+    form = "dx_smallk_kernel<8,v4,a4>";
+  }
   else if (g.K <= 4) SMI_DXS(4);
   else SMI_DXS(8);
 #undef SMI_DXS
   ktime_end(kslot, KT_GEMM_DX, 2.0 * g.M * (double)g.N * g.K, st);
-  return check_launch("dx_smallk_kernel");
+  return check_launch(form);
 }
 
 // Forwards and input gradients of short batches (M <= 4096 rows: DDPG's 512-row
@@ -2340,7 +2353,7 @@ static int gemm_launch(int epi, GemmArgs g, hipStream_t st) {
     if (epi == EPI_FWD) hipLaunchKernelGGL(gemm_t16_kernel<EPI_FWD>, grid16, dim3(kWG), 0, st, g);
     else hipLaunchKernelGGL(gemm_t16_kernel<EPI_DX>, grid16, dim3(kWG), 0, st, g);
     ktime_end(kslot, epi == EPI_FWD ? KT_GEMM_FWD : KT_GEMM_DX, 2.0 * g.M * (double)g.N * g.K, st);
-    return check_launch("gemm_t16_kernel");
+    return check_launch(epi == EPI_FWD ? "gemm_t16_kernel<fwd>" : "gemm_t16_kernel<dx>");
   }
   if ((epi == EPI_DW && g.K > 4 * GBK) || split_fwd) {
     const int tiles = gm * gn;
@@ -2371,12 +2384,21 @@ static int gemm_launch(int epi, GemmArgs g, hipStream_t st) {
   const int nreal = g.ones_col >= 0 ? g.N - 1 : g.N;
   ktime_end(kslot, epi == EPI_FWD ? KT_GEMM_FWD : epi == EPI_DX ? KT_GEMM_DX : KT_GEMM_DW,
             2.0 * g.M * (double)nreal * g.K + (g.ones_col >= 0 ? (double)g.M * g.K : 0.0), st);
-  int rc = check_launch("gemm_kernel");
+  // (named by epilogue: the operand orientation, and so gemm_kernel's AK / BK
+  // arguments, is fixed per epilogue for the three C-ABI layer calls)
+  int rc = check_launch(dw128 ? "gemm_dw128_kernel" : epi == EPI_FWD ? "gemm_kernel<fwd>"
+                        : epi == EPI_DX ? "gemm_kernel<dx>" : "gemm_kernel<dw>");
   if (rc || S == 1) return rc;
-  return splitk_reduce(g, S, epi, st);
+  // the reducer is the last launch of a split-K GEMM: its name carries the
+  // kernel whose slabs it sums, so smi_last_launch still tells the form
+  return splitk_reduce(g, S, epi, st,
+                       dw128 ? "gemm_splitk_reduce_kernel<gemm_dw128_kernel>"
+                       : epi == EPI_FWD ? "gemm_splitk_reduce_kernel<gemm_kernel<fwd>>"
+                       : epi == EPI_DX ? "gemm_splitk_reduce_kernel<gemm_kernel<dx>>"
+                                       : "gemm_splitk_reduce_kernel<gemm_kernel<dw>>");
 }
 
-static int splitk_reduce(const GemmArgs& g, int S, int epi, hipStream_t st) {
+static int splitk_reduce(const GemmArgs& g, int S, int epi, hipStream_t st, const char* what) {
   const int rslot = ktime_begin(st);
   const int64_t MN = (int64_t)g.M * g.N;
   const int rg = (int)((MN + 63) / 64);
@@ -2385,7 +2407,7 @@ static int splitk_reduce(const GemmArgs& g, int S, int epi, hipStream_t st) {
                      fwd ? g.bias : nullptr, fwd ? g.act : ACT_NONE,
                      epi == EPI_DX ? g.mask : nullptr);
   ktime_end(rslot, KT_GEMM_REDUCE, (double)S * MN, st);
-  return check_launch("gemm_splitk_reduce_kernel");
+  return check_launch(what);
 }
 
 // out[i] = sum_{z < S} part[z][i] in a fixed order (no accumulate)

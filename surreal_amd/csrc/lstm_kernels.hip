@@ -1730,20 +1730,27 @@ static int lstm_valu_r(int B, int H) {
 }
 
 // LDS of the staged x sequence and the precomputed x parts (KX > 0); the fused
-// form is used up to kVxMax (S <= 52 steps at H = 100, x width <= 64)
+// form is used up to kVxMax (at H = 100: S <= 61 steps for x widths <= 48,
+// S <= 60 for <= 64; tests/test_gpu_forms.py runs both sides of the first edge)
 [[maybe_unused]] constexpr size_t kVxMax = 120 * 1024;
 static size_t lstm_fwd_v_lds(int S, int R, int KX, int blk) {
   return ((((size_t)S * R * KX + 3) & ~(size_t)3) + (size_t)S * R * blk) * 4;
 }
 #if SMI_LSTM_VALU_HALF
+// Every dispatcher below returns the literal that names the instantiation it
+// launched (smi_last_launch, include/surreal_mi.h).
 template <int R, int KX>
-static void fwd_v_dispatch_kp(const LstmFwdArgs& a, hipStream_t st) {
+static const char* fwd_v_dispatch_kp(const LstmFwdArgs& a, hipStream_t st) {
   const dim3 grid((a.B + R - 1) / R), blk((4 * a.H + 63) & ~63);
   const size_t lds = KX > 0 ? lstm_fwd_v_lds(a.S, R, KX, blk.x) : 0;
 #define SMI_FV(KP)                                                                 \
   do {                                                                             \
     allow_lds(lstm_fwd_v_kernel<R, KP, KX>, lds);                                  \
     hipLaunchKernelGGL((lstm_fwd_v_kernel<R, KP, KX>), grid, blk, lds, st, a);     \
+    return R == 1 ? (KX == 0 ? "lstm_fwd_v_kernel<1," #KP ",0>"                     \
+                    : KX == 48 ? "lstm_fwd_v_kernel<1," #KP ",48>"                  \
+                               : "lstm_fwd_v_kernel<1," #KP ",64>")                 \
+         : R == 2 ? "lstm_fwd_v_kernel<2," #KP ",0>" : "lstm_fwd_v_kernel<4," #KP ",0>"; \
   } while (0)
   if (a.H <= 64) SMI_FV(64);
   else if (a.H <= 104) SMI_FV(104);
@@ -1753,17 +1760,24 @@ static void fwd_v_dispatch_kp(const LstmFwdArgs& a, hipStream_t st) {
 // x W_ih^T fused only at R = 1 (its W_ih row joins the W_hh row in registers:
 // at R >= 2 the two segments' operands no longer fit next to them); R >= 2
 // reads the xproj GEMM's output (launch_lstm_fwd_x returns SMI_E_NOFIT)
-static void fwd_v_dispatch(const LstmFwdArgs& a, int R, hipStream_t st) {
-  if (R == 1) fwd_v_dispatch_kp<1, 0>(a, st);
-  else if (R == 2) fwd_v_dispatch_kp<2, 0>(a, st);
-  else fwd_v_dispatch_kp<4, 0>(a, st);
+static const char* fwd_v_dispatch(const LstmFwdArgs& a, int R, hipStream_t st) {
+  if (R == 1) return fwd_v_dispatch_kp<1, 0>(a, st);
+  if (R == 2) return fwd_v_dispatch_kp<2, 0>(a, st);
+  return fwd_v_dispatch_kp<4, 0>(a, st);
 }
 template <int R>
-static void bwd_v_dispatch_kp(const LstmBwdArgs& a, hipStream_t st) {
+static const char* bwd_v_dispatch_kp(const LstmBwdArgs& a, hipStream_t st) {
   const dim3 grid((a.B + R - 1) / R), blk((4 * a.H + 63) & ~63);
-  if (a.H <= 64) hipLaunchKernelGGL((lstm_bwd_v_kernel<R, 64>), grid, blk, 0, st, a);
-  else if (a.H <= 104) hipLaunchKernelGGL((lstm_bwd_v_kernel<R, 104>), grid, blk, 0, st, a);
-  else hipLaunchKernelGGL((lstm_bwd_v_kernel<R, 128>), grid, blk, 0, st, a);
+#define SMI_BV(KP)                                                                 \
+  do {                                                                             \
+    hipLaunchKernelGGL((lstm_bwd_v_kernel<R, KP>), grid, blk, 0, st, a);           \
+    return R == 1 ? "lstm_bwd_v_kernel<1," #KP ">"                                 \
+         : R == 2 ? "lstm_bwd_v_kernel<2," #KP ">" : "lstm_bwd_v_kernel<4," #KP ">"; \
+  } while (0)
+  if (a.H <= 64) SMI_BV(64);
+  else if (a.H <= 104) SMI_BV(104);
+  else SMI_BV(128);
+#undef SMI_BV
 }
 
 // the VALU forms' entry points for the launchers (the other half of the file
@@ -1783,7 +1797,7 @@ static bool use_xm() {
 }
 // a1 (optional): the second sequence set of a dual launch (same H / x width)
 template <int XQ>
-static void fwd_q_dispatch(const LstmFwdArgs& a, hipStream_t st, const LstmFwdArgs* a1 = nullptr) {
+static const char* fwd_q_dispatch(const LstmFwdArgs& a, hipStream_t st, const LstmFwdArgs* a1 = nullptr) {
   const dim3 grid(a.B + (a1 ? a1->B : 0)), blk((4 * a.H + 63) & ~63);
   const LstmFwdArgs& a2 = a1 ? *a1 : a;
   const int smax = a1 && a1->S > a.S ? a1->S : a.S;
@@ -1804,17 +1818,25 @@ static void fwd_q_dispatch(const LstmFwdArgs& a, hipStream_t st, const LstmFwdAr
   // quad broadcasts; A/B knob)
   static const bool a4 = [] { const char* e = getenv("SMI_LSTM_A4"); return !(e && e[0] == '0'); }();
   const size_t lds = XQ > 0 ? lstm_fwd_v_lds(smax, 1, 4 * XQ, blk.x) : 0;
+  // <KQ,XQ,xm|xv,wW[,a4]>: xm the matrix-core x parts, xv the VALU ones (and
+  // the xproj input, XQ 0), a4 all four gates in every lane
+#define SMI_FQN(KQ, TAIL)                                                          \
+  (XQ == 0 ? "lstm_fwd_q_kernel<" #KQ ",0," TAIL                                   \
+   : XQ == 12 ? "lstm_fwd_q_kernel<" #KQ ",12," TAIL : "lstm_fwd_q_kernel<" #KQ ",16," TAIL)
 #define SMI_FQ(KQ, W)                                                              \
   do {                                                                             \
     if (xm && a4) {                                                                \
       allow_lds(lstm_fwd_q_kernel<KQ, XQ, true, W, XQ != 0>, lds);                 \
       hipLaunchKernelGGL((lstm_fwd_q_kernel<KQ, XQ, true, W, XQ != 0>), grid, blk, lds, st, a, a2); \
+      return SMI_FQN(KQ, "xm,w" #W ",a4>");                                        \
     } else if (xm) {                                                               \
       allow_lds(lstm_fwd_q_kernel<KQ, XQ, true, W>, lds);                          \
       hipLaunchKernelGGL((lstm_fwd_q_kernel<KQ, XQ, true, W>), grid, blk, lds, st, a, a2);  \
+      return SMI_FQN(KQ, "xm,w" #W ">");                                           \
     } else {                                                                       \
       allow_lds(lstm_fwd_q_kernel<KQ, XQ, false, W>, lds);                         \
       hipLaunchKernelGGL((lstm_fwd_q_kernel<KQ, XQ, false, W>), grid, blk, lds, st, a, a2); \
+      return SMI_FQN(KQ, "xv,w" #W ">");                                           \
     }                                                                              \
   } while (0)
   if (a.H <= 64) {
@@ -1832,22 +1854,22 @@ static void fwd_q_dispatch(const LstmFwdArgs& a, hipStream_t st, const LstmFwdAr
     else SMI_FQ(32, 0);
   }
 #undef SMI_FQ
+#undef SMI_FQN
 }
 // two sequence sets in one launch, one segment per workgroup (fused x parts)
-void lstm_q_fwd_dual(const LstmFwdArgs& a, const LstmFwdArgs& a1, int kx, hipStream_t st) {
-  if (kx <= 48) fwd_q_dispatch<12>(a, st, &a1);
-  else fwd_q_dispatch<16>(a, st, &a1);
+const char* lstm_q_fwd_dual(const LstmFwdArgs& a, const LstmFwdArgs& a1, int kx, hipStream_t st) {
+  if (kx <= 48) return fwd_q_dispatch<12>(a, st, &a1);
+  return fwd_q_dispatch<16>(a, st, &a1);
 }
-void lstm_v_fwd(const LstmFwdArgs& a, int R, int kx, hipStream_t st) {
+const char* lstm_v_fwd(const LstmFwdArgs& a, int R, int kx, hipStream_t st) {
   if (R == 1 && use_q()) {
-    if (kx == 0) fwd_q_dispatch<0>(a, st);
-    else if (kx <= 48) fwd_q_dispatch<12>(a, st);
-    else fwd_q_dispatch<16>(a, st);
-    return;
+    if (kx == 0) return fwd_q_dispatch<0>(a, st);
+    if (kx <= 48) return fwd_q_dispatch<12>(a, st);
+    return fwd_q_dispatch<16>(a, st);
   }
-  if (kx == 0) fwd_v_dispatch(a, R, st);
-  else if (kx <= 48) fwd_v_dispatch_kp<1, 48>(a, st);
-  else fwd_v_dispatch_kp<1, 64>(a, st);
+  if (kx == 0) return fwd_v_dispatch(a, R, st);
+  if (kx <= 48) return fwd_v_dispatch_kp<1, 48>(a, st);
+  return fwd_v_dispatch_kp<1, 64>(a, st);
 }
 // the BPTT's step inputs staged in LDS (SMI_BWD_STAGE=1; A/B knob, off: the
 // staging prologue cost what the loop's per-step vmcnt(0) did -- 128 segments
@@ -1861,7 +1883,7 @@ bool use_bwd_stage() {
 bool lstm_bwd_q_ok(int H, const float* w_hh) {
   return use_q() && H % 4 == 0 && (reinterpret_cast<uintptr_t>(w_hh) & 15) == 0;
 }
-void lstm_v_bwd(const LstmBwdArgs& a, int R, hipStream_t st) {
+const char* lstm_v_bwd(const LstmBwdArgs& a, int R, hipStream_t st) {
   if (R == 1 && lstm_bwd_q_ok(a.H, a.w_hh)) {
     const dim3 grid(a.B), blk((4 * a.H + 63) & ~63);
     // the step inputs staged in LDS when they fit (lstm_bwd_q_body)
@@ -1872,19 +1894,20 @@ void lstm_v_bwd(const LstmBwdArgs& a, int R, hipStream_t st) {
       if (s) {                                                                            \
         allow_lds(lstm_bwd_q_kernel<BR_, true>, stg);                                     \
         hipLaunchKernelGGL((lstm_bwd_q_kernel<BR_, true>), grid, blk, stg, st, a);        \
+        return "lstm_bwd_q_kernel<" #BR_ ",stg>";                                         \
       } else {                                                                            \
         hipLaunchKernelGGL((lstm_bwd_q_kernel<BR_, false>), grid, blk, 0, st, a);         \
+        return "lstm_bwd_q_kernel<" #BR_ ">";                                             \
       }                                                                                   \
     } while (0)
     if (a.H <= 64) SMI_BQ(16);
     else if (a.H <= 100) SMI_BQ(25);
     else SMI_BQ(32);
 #undef SMI_BQ
-    return;
   }
-  if (R == 1) bwd_v_dispatch_kp<1>(a, st);
-  else if (R == 2) bwd_v_dispatch_kp<2>(a, st);
-  else bwd_v_dispatch_kp<4>(a, st);
+  if (R == 1) return bwd_v_dispatch_kp<1>(a, st);
+  if (R == 2) return bwd_v_dispatch_kp<2>(a, st);
+  return bwd_v_dispatch_kp<4>(a, st);
 }
 #ifdef SMI_PROF
 // the VALU half's phase ticks (its own copy of g_lstm_ticks when the file is
@@ -1898,9 +1921,9 @@ extern "C" int smi_lstm_v_phase_ticks(unsigned long long* out /* [8] */) {
 }
 #endif
 #else
-void lstm_v_fwd(const LstmFwdArgs& a, int R, int kx, hipStream_t st);
-void lstm_v_bwd(const LstmBwdArgs& a, int R, hipStream_t st);
-void lstm_q_fwd_dual(const LstmFwdArgs& a, const LstmFwdArgs& a1, int kx, hipStream_t st);
+const char* lstm_v_fwd(const LstmFwdArgs& a, int R, int kx, hipStream_t st);
+const char* lstm_v_bwd(const LstmBwdArgs& a, int R, hipStream_t st);
+const char* lstm_q_fwd_dual(const LstmFwdArgs& a, const LstmFwdArgs& a1, int kx, hipStream_t st);
 #endif  // SMI_LSTM_VALU_HALF
 
 #if SMI_LSTM_MFMA
@@ -1968,10 +1991,7 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
   // algorithmic flops: the recurrent GEMM h W_hh^T of every step
   struct End { int s; hipStream_t st; double f;
                ~End() { ktime_end(s, KT_LSTM_FWD, f, st); } } end_{kslot, st, 8.0 * B * H * (double)H * S};
-  if (const int R = lstm_valu_r(B, H)) {
-    lstm_v_fwd(a, R, 0, st);
-    return check_launch("lstm_fwd_v_kernel");
-  }
+  if (const int R = lstm_valu_r(B, H)) return check_launch(lstm_v_fwd(a, R, 0, st));
   if (H <= 128 && use_r4()) {
     const dim3 g4((B + LR4 - 1) / LR4);
     const size_t wl = r4_wstage_bytes(a, false);
@@ -1981,9 +2001,11 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
     do {                                                                                    \
       if (vf) {                                                                             \
         hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, 0, true>), g4, dim3(kWG8), 0, st, a);   \
+        return check_launch("lstm_fwd_r4_kernel<" #KP_ ",0,vf>");                           \
       } else {                                                                              \
         if (wl) allow_lds(lstm_fwd_r4_kernel<KP_, 0>, wl);                                  \
         hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, 0>), g4, dim3(kWG8), wl, st, a);        \
+        return check_launch("lstm_fwd_r4_kernel<" #KP_ ",0>");                              \
       }                                                                                     \
     } while (0)
     if (H <= 32) SMI_R4F(32);
@@ -1991,7 +2013,6 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
     else if (H <= 104) SMI_R4F(104);
     else SMI_R4F(128);
 #undef SMI_R4F
-    return check_launch("lstm_fwd_r4_kernel");
   }
   const size_t lds = (size_t)lstm_fwd_lds(H);
   const dim3 grid((B + LR - 1) / LR);
@@ -1999,26 +2020,28 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
     const size_t l16 = (size_t)2 * LR * lstm_ld(4 * 16) * 4;
     allow_lds(lstm_fwd_reg_kernel<16>, l16);
     hipLaunchKernelGGL(lstm_fwd_reg_kernel<16>, grid, dim3(kWG8), l16, st, a);
-    return check_launch("lstm_fwd_reg_kernel");
+    return check_launch("lstm_fwd_reg_kernel<16>");
   }
   if (H <= 112) {                      // the reference default H = 100: 112 W regs/lane
     const size_t l28 = (size_t)2 * LR * lstm_ld(4 * 28) * 4;
     allow_lds(lstm_fwd_reg_kernel<28>, l28);
     hipLaunchKernelGGL(lstm_fwd_reg_kernel<28>, grid, dim3(kWG8), l28, st, a);
-    return check_launch("lstm_fwd_reg_kernel");
+    return check_launch("lstm_fwd_reg_kernel<28>");
   }
   const int nut = (H + 15) / 16;
   if (nut <= 4) {
     allow_lds(lstm_fwd_kernel<1>, lds);
     hipLaunchKernelGGL(lstm_fwd_kernel<1>, grid, dim3(kWG), lds, st, a);
-  } else if (nut <= 8) {
+    return check_launch("lstm_fwd_kernel<1>");
+  }
+  if (nut <= 8) {
     allow_lds(lstm_fwd_kernel<2>, lds);
     hipLaunchKernelGGL(lstm_fwd_kernel<2>, grid, dim3(kWG), lds, st, a);
-  } else {
-    allow_lds(lstm_fwd_kernel<4>, lds);
-    hipLaunchKernelGGL(lstm_fwd_kernel<4>, grid, dim3(kWG), lds, st, a);
+    return check_launch("lstm_fwd_kernel<2>");
   }
-  return check_launch("lstm_fwd_kernel");
+  allow_lds(lstm_fwd_kernel<4>, lds);
+  hipLaunchKernelGGL(lstm_fwd_kernel<4>, grid, dim3(kWG), lds, st, a);
+  return check_launch("lstm_fwd_kernel<4>");
 }
 
 // LSTM forward with the input projection fused (din <= 64, H <= 104): returns
@@ -2027,8 +2050,11 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
                       const float* w_hh, const float* b_hh, const float* h0, const float* c0,
                       int S, int B, int H, float* hbuf, float* cbuf, float* gates,
                       hipStream_t st, const int* skip, int keep) {
+  // no step, no launch (the outputs stay untouched): the fused forms' prologues
+  // load x_0 unconditionally, and at S == 0 the K-split form clamps that index
+  // to S * KX - 1 = -1
+  if (B <= 0 || S <= 0) return SMI_OK;
   if (!use_r4() || din < 1 || din > 64 || H < 1 || H > 104) return SMI_E_NOFIT;
-  if (B <= 0 || S < 0) return SMI_OK;
   const int R = lstm_valu_r(B, H);
   if (R > 1) return SMI_E_NOFIT;                 // xproj GEMM + the VALU recurrence
   if (R == 1 && lstm_fwd_v_lds(S, 1, din <= 48 ? 48 : 64, (4 * H + 63) & ~63) > kVxMax)
@@ -2039,10 +2065,7 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
   struct End { int s; hipStream_t st; double f;
                ~End() { ktime_end(s, KT_LSTM_FWD, f, st); } } end_{
       kslot, st, 8.0 * B * H * (double)(H + din) * S};
-  if (R == 1) {
-    lstm_v_fwd(a, 1, din <= 48 ? 48 : 64, st);
-    return check_launch("lstm_fwd_v_kernel");
-  }
+  if (R == 1) return check_launch(lstm_v_fwd(a, 1, din <= 48 ? 48 : 64, st));
   const dim3 g4((B + LR4 - 1) / LR4);
   const size_t wl = r4_wstage_bytes(a, true);
   a.wstage = wl > 0;
@@ -2051,9 +2074,11 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
   do {                                                                                        \
     if (vf) {                                                                                 \
       hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, KX_, true>), g4, dim3(kWG8), 0, st, a);     \
+      return check_launch("lstm_fwd_r4_kernel<" #KP_ "," #KX_ ",vf>");                        \
     } else {                                                                                  \
       if (wl) allow_lds(lstm_fwd_r4_kernel<KP_, KX_>, wl);                                    \
       hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, KX_>), g4, dim3(kWG8), wl, st, a);          \
+      return check_launch("lstm_fwd_r4_kernel<" #KP_ "," #KX_ ">");                           \
     }                                                                                         \
   } while (0)
   if (din <= 48) {
@@ -2064,7 +2089,6 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
     else SMI_R4X(104, 64);
   }
 #undef SMI_R4X
-  return check_launch("lstm_fwd_r4_kernel");
 }
 
 bool lstm_use_q();
@@ -2091,14 +2115,17 @@ bool lstm_fwd_x_dual_fits(int B0, int B1, int S, int H, int din) {
 int launch_lstm_fwd_x_dual(const LstmFwdArgs& a0, const LstmFwdArgs& a1, hipStream_t st) {
   const int H = a0.H, din = a0.din;
   const int smax = a0.S > a1.S ? a0.S : a1.S;
+  // as launch_lstm_fwd_x: no step, no launch; one empty set of two has no form here
+  if (a0.S <= 0 && a1.S <= 0) return SMI_OK;
+  if (a0.S <= 0 || a1.S <= 0) return SMI_E_NOFIT;
   if (a0.H != a1.H || a0.din != a1.din || !lstm_fwd_x_dual_fits(a0.B, a1.B, smax, H, din))
     return SMI_E_NOFIT;
   const int kx = din <= 48 ? 48 : 64;
   const int kslot = ktime_begin(st);
-  lstm_q_fwd_dual(a0, a1, kx, st);
+  const char* form = lstm_q_fwd_dual(a0, a1, kx, st);
   ktime_end(kslot, KT_LSTM_FWD,
             8.0 * H * (double)(H + din) * ((double)a0.B * a0.S + (double)a1.B * a1.S), st);
-  return check_launch("lstm_fwd_q_kernel");
+  return check_launch(form);
 }
 
 int launch_lstm_bwd(const float* dh, const float* gates, const float* cbuf, const float* w_hh,
@@ -2110,19 +2137,22 @@ int launch_lstm_bwd(const float* dh, const float* gates, const float* cbuf, cons
   struct End { int s; hipStream_t st; double f;
                ~End() { ktime_end(s, KT_LSTM_BWD, f, st); } } end_{kslot, st,
                                                                  8.0 * B * H * (double)H * (S - 1)};
-  if (const int R = lstm_valu_r(B, H)) {
-    lstm_v_bwd(a, R, st);
-    return check_launch("lstm_bwd_v_kernel");
-  }
+  if (const int R = lstm_valu_r(B, H)) return check_launch(lstm_v_bwd(a, R, st));
   if (H <= 128 && use_r4()) {
     const int nu = (H + 63) / 64, wpg = 8 / nu;
     const int kw = (4 * H + wpg - 1) / wpg;
     const dim3 g4((B + LR4 - 1) / LR4);
-    if (kw <= 32) hipLaunchKernelGGL(lstm_bwd_r4_kernel<32>, g4, dim3(kWG8), 0, st, a);
-    else if (kw <= 64) hipLaunchKernelGGL(lstm_bwd_r4_kernel<64>, g4, dim3(kWG8), 0, st, a);
-    else if (kw <= 104) hipLaunchKernelGGL(lstm_bwd_r4_kernel<104>, g4, dim3(kWG8), 0, st, a);
-    else hipLaunchKernelGGL(lstm_bwd_r4_kernel<128>, g4, dim3(kWG8), 0, st, a);
-    return check_launch("lstm_bwd_r4_kernel");
+#define SMI_R4B(KW_)                                                              \
+    do {                                                                          \
+      hipLaunchKernelGGL(lstm_bwd_r4_kernel<KW_>, g4, dim3(kWG8), 0, st, a);      \
+      return check_launch("lstm_bwd_r4_kernel<" #KW_ ">");                        \
+    } while (0)
+    // (kw is H / 2 <= 32 for H <= 64 and H >= 65 beyond: <64> is never selected)
+    if (kw <= 32) SMI_R4B(32);
+    else if (kw <= 64) SMI_R4B(64);
+    else if (kw <= 104) SMI_R4B(104);
+    else SMI_R4B(128);
+#undef SMI_R4B
   }
   const size_t lds = (size_t)lstm_bwd_lds(H);
   if (lds > 160 * 1024) return set_error(SMI_E_NOFIT, "lstm: hidden size too large for LDS");
@@ -2130,25 +2160,27 @@ int launch_lstm_bwd(const float* dh, const float* gates, const float* cbuf, cons
   if (H == 64) {
     allow_lds(lstm_bwd_reg_kernel<64>, lds);
     hipLaunchKernelGGL(lstm_bwd_reg_kernel<64>, grid, dim3(kWG8), lds, st, a);
-    return check_launch("lstm_bwd_reg_kernel");
+    return check_launch("lstm_bwd_reg_kernel<64>");
   }
   if (H == 100) {                      // the reference default: KS must equal H
     allow_lds(lstm_bwd_reg_kernel<100>, lds);
     hipLaunchKernelGGL(lstm_bwd_reg_kernel<100>, grid, dim3(kWG8), lds, st, a);
-    return check_launch("lstm_bwd_reg_kernel");
+    return check_launch("lstm_bwd_reg_kernel<100>");
   }
   const int nut = (H + 15) / 16;
   if (nut <= 4) {
     allow_lds(lstm_bwd_kernel<1>, lds);
     hipLaunchKernelGGL(lstm_bwd_kernel<1>, grid, dim3(kWG), lds, st, a);
-  } else if (nut <= 8) {
+    return check_launch("lstm_bwd_kernel<1>");
+  }
+  if (nut <= 8) {
     allow_lds(lstm_bwd_kernel<2>, lds);
     hipLaunchKernelGGL(lstm_bwd_kernel<2>, grid, dim3(kWG), lds, st, a);
-  } else {
-    allow_lds(lstm_bwd_kernel<4>, lds);
-    hipLaunchKernelGGL(lstm_bwd_kernel<4>, grid, dim3(kWG), lds, st, a);
+    return check_launch("lstm_bwd_kernel<2>");
   }
-  return check_launch("lstm_bwd_kernel");
+  allow_lds(lstm_bwd_kernel<4>, lds);
+  hipLaunchKernelGGL(lstm_bwd_kernel<4>, grid, dim3(kWG), lds, st, a);
+  return check_launch("lstm_bwd_kernel<4>");
 }
 
 #endif  // SMI_LSTM_MFMA

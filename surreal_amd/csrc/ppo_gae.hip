@@ -679,7 +679,8 @@ int launch_gae_windows(const float* values, float* values_masked, const float* r
     else if (TPR == 32) hipLaunchKernelGGL(gae_rows_kernel<32>, dim3(grid), dim3(kWG), 0, stream, a);
     else hipLaunchKernelGGL(gae_rows_kernel<64>, dim3(grid), dim3(kWG), 0, stream, a);
     if (n_partials) *n_partials = grid;
-    return check_launch("gae_rows_kernel");
+    return check_launch(TPR == 8 ? "gae_rows_kernel<8>" : TPR == 16 ? "gae_rows_kernel<16>"
+                        : TPR == 32 ? "gae_rows_kernel<32>" : "gae_rows_kernel<64>");
   }
   // lanes per window: split long windows so a block pass keeps every lane busy
   int LG = 1;
@@ -709,7 +710,10 @@ int launch_gae_windows(const float* values, float* values_masked, const float* r
   allow_lds(gae_windows_kernel, lds);
   hipLaunchKernelGGL(gae_windows_kernel, dim3(grid), dim3(kWG), lds, stream, a);
   if (n_partials) *n_partials = grid;
-  return check_launch("gae_windows_kernel");
+  // LG (lanes per window) is a run-time argument of the one kernel: named as a form
+  return check_launch(LG == 1 ? "gae_windows_kernel<lg1>" : LG == 2 ? "gae_windows_kernel<lg2>"
+                      : LG == 4 ? "gae_windows_kernel<lg4>" : LG == 8 ? "gae_windows_kernel<lg8>"
+                                                                      : "gae_windows_kernel<lg16>");
 }
 
 }  // namespace smi

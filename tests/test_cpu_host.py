@@ -53,6 +53,18 @@ def test_error_path_reports_message():
         _lib.check(rc, 'smi_gather_rows')
 
 
+def test_last_launch_is_empty_before_any_launch():
+    """smi_last_launch() in a process that has launched nothing (a fresh one:
+    this process may have run GPU tests on this thread before)."""
+    import subprocess
+    import sys
+    from surreal_amd import _lib
+    code = ('import ctypes, sys; L = ctypes.CDLL(sys.argv[1]); '
+            'L.smi_last_launch.restype = ctypes.c_char_p; '
+            'sys.exit(0 if L.smi_last_launch() == b"" else 1)')
+    assert subprocess.run([sys.executable, '-c', code, _lib.LIB_PATH]).returncode == 0
+
+
 def test_host_sampler_matches_cpython():
     from surreal_amd import _lib
     lib = _lib.lib()
