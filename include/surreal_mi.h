@@ -59,7 +59,13 @@ const char* smi_last_error(void);
  *   gemm_panel_kernel<fwd|dx,C>             C 16-column tiles per column group
  *   gemm_smallk_fwd_kernel<KU>  dx_smallk_kernel<KK[,v4][,a4]>
  *   gemm_t16_kernel<fwd|dx>  gemm_kernel<fwd|dx|dw>  gemm_dw128_kernel
- *   gemm_dwd_kernel  gemm_dwd_group_kernel  gemm_dwt16_kernel  gemm_group_reduce_kernel
+ *   gemm_dwd_kernel  gemm_dwt16_kernel
+ *   gemm_dwd_group_kernel<CLS,...>          the distinct tile classes of the launch's
+ *       entries in entry order: MTxNT 16-wide sub-tiles (1..4 each; below 4 an
+ *       edge fitted to the remainder), a 4 marked v (16-byte loads) or s
+ *       (per-column loads), e.g. <4vx4v,1x4v,4vx3,1x3>
+ *   gemm_group_reduce_kernel<gemm_dwd_group_kernel<CLS,...>>   its reducer (the
+ *       last launch of a flush; bare gemm_group_reduce_kernel: the epilogue task alone)
  *   gemm_splitk_reduce_kernel<PRODUCER>     PRODUCER the split-K kernel's own form
  *   gae_seg_kernel  gae_rows_kernel<TPR>  gae_windows_kernel<lgN>  N lanes per window
  * Other launches report the bare kernel name. */
@@ -640,12 +646,27 @@ int smi_linear_backward_weight(const float* dy, int64_t ldg, int rows, int out_d
                                float* db, int accumulate, void* stream);
 /* Grouped weight gradients: smi_linear_backward_weight calls between
  * smi_dw_group_begin() and smi_dw_group_flush(stream) (row-major operands,
- * outputs <= 512 x 512, at most 6 per group) are queued and run as ONE launch
+ * outputs <= 512 x 512, at most 8 per group) are queued and run as ONE launch
  * (workgroups dealt over every GEMM's tiles x split-K slabs) plus one
  * fixed-order reduce at the flush; the caller keeps their dY / X buffers
  * unchanged until then.  Calls that do not qualify launch immediately. */
 int smi_dw_group_begin(void);
 int smi_dw_group_flush(void* stream);
+/* The plan of one grouped launch as host arithmetic (no device call; CPU
+ * tests): every GEMM cut into its full 64 x 64 tiles, an M edge, an N edge and
+ * their corner (edge tiles fitted to the remainder in 16-wide sub-tiles), and
+ * each rectangle's balanced split-K slabs.
+ *   gemms  ng x {M, N, K, vec (2: 16-byte dY loads | 1: 16-byte X loads | 4: dY
+ *          base 16-byte aligned | 8: X base(s) 16-byte aligned), ones (1: the last column is the bias gradient's), split_col (-1,
+ *          or the first column of a second X source)}
+ *   waves  4 | 8 per workgroup; slots: resident workgroups of the launch;
+ *   cap_floats: workspace for the partials; max_ent: entries allowed (<= 16)
+ *   out    per entry {gemm, m0, n0, M, N, MT, NT, slab rows, slabs, first
+ *          workgroup, first reducer block, partials offset in floats}
+ *   tot    {workgroups, reducer blocks, floats of partials, rows per prefetch window}
+ * Returns the entry count (negative: error). */
+int smi_diag_dw_plan(const int* gemms, int ng, int waves, int slots, int64_t cap_floats,
+                     int max_ent, int64_t* out, int64_t* tot);
 
 /* ------------------------------------------------------- DDPG loss pieces */
 /* critic loss nn.MSELoss()(Q, y) (ddpg.py:306): loss = mean((Q-y)^2), dQ = 2(Q-y)/n */

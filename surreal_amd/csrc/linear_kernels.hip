@@ -700,6 +700,52 @@ constexpr int DWD_P = SMI_DWD_P;   // steps in flight per wave
 // all P steps in flight.  Columns past M / N read clamped addresses; they only
 // reach outputs the epilogue drops.
 
+// Fitted edge tiles (MT or NT of 1..3 sub-tiles: the M / N remainder of a
+// grouped GEMM, dw_plan): lane li reads its MT (NT) consecutive columns with
+// ONE load, a dword / dwordx2 / dwordx3 through a 4-byte-aligned vector type,
+// and sub-tile j takes component j -- an MFMA does not care which output
+// column sits in which tile position.  The run is clamped to end at the
+// operand's last column (lanes past the end repeat earlier columns), so the
+// epilogue derives each position's column from the same clamp (dwd_fit_col)
+// and drops the repeats.  The bias column of a fitted N edge is the first
+// component of the first lane past the data, read from g_dwd_one.
+typedef float dwd_v2 __attribute__((ext_vector_type(2), aligned(4)));
+typedef float dwd_v3 __attribute__((ext_vector_type(3), aligned(4)));
+// W consecutive floats at p (4-byte aligned for W < 4, 16-byte for W == 4) with
+// one load; GLOBAL: through an address-space-1 pointer (dwd_main_fast)
+template <int W, bool GLOBAL>
+__device__ __forceinline__ float4 dwd_ldw(const float* p) {
+#define SMI_LDW(T_) (GLOBAL ? *(const __attribute__((address_space(1))) T_*)p : *(const T_*)p)
+  if constexpr (W == 4) { const f32x4 x = SMI_LDW(f32x4); return float4{x[0], x[1], x[2], x[3]}; }
+  else if constexpr (W == 3) { const dwd_v3 x = SMI_LDW(dwd_v3); return float4{x[0], x[1], x[2], 0.f}; }
+  else if constexpr (W == 2) { const dwd_v2 x = SMI_LDW(dwd_v2); return float4{x[0], x[1], 0.f, 0.f}; }
+  else return float4{SMI_LDW(float), 0.f, 0.f, 0.f};
+#undef SMI_LDW
+}
+
+// the column that position (lane li, component j) of a W-wide fitted edge
+// starting at column c0 holds, data columns [.., lim); -1: none (a repeat)
+template <int W>
+__device__ __forceinline__ int dwd_fit_col(int c0, int lim, int li, int j) {
+  const int cb = c0 + W * li;
+  const int c = min(cb, lim - W) + j;
+  return c >= cb ? c : -1;
+}
+
+// one tile of a grouped launch: rectangle [m0, m0 + M) x [n0, n0 + N) of GEMM
+// gi's output in tiles of MT x NT sub-tiles, S slabs of kchunk rows each
+struct DwEnt {
+  float* part;                   // split-K partials [S][M][N]
+  int gi;                        // the GEMM (DwGroup::g)
+  int m0, n0, M, N;
+  int kchunk, S;
+  int gm, gn;                    // tiles
+  int cls;                       // dw_cls(): tile class MT x NT and the 16-byte operand flags
+};
+__host__ __device__ constexpr int dw_cls(int mt, int nt, bool va, bool vb) {
+  return mt | (nt << 3) | ((mt == 4 && va) << 7) | ((nt >= 4 && vb) << 8);
+}
+
 template <int MT, int NT, bool VA, bool VB, int NB = NT>
 __device__ __forceinline__ void dwd_load(const GemmArgs& g, int r, int ke, int m0, int n0, int bdata,
                                          float (&av)[MT], float (&bv)[NT]) {
@@ -718,9 +764,24 @@ __device__ __forceinline__ void dwd_load(const GemmArgs& g, int r, int ke, int m
     const int c = min(m0 + 4 * li, g.M - 4);
     const float4 x = *reinterpret_cast<const float4*>(Ar + c);
     av[0] = x.x; av[1] = x.y; av[2] = x.z; av[3] = x.w;
+  } else if constexpr (MT == 2 || MT == 3) {
+    const float4 x = dwd_ldw<MT, false>(Ar + min(m0 + MT * li, g.M - MT));
+    av[0] = x.x; av[1] = x.y;
+    if constexpr (MT == 3) av[2] = x.z;
   } else {
 #pragma unroll
     for (int t = 0; t < MT; ++t) av[t] = Ar[min(m0 + MT * li + t, g.M - 1)];
+  }
+  if constexpr (NT < 4) {
+    const int cb = n0 + NT * li;
+    const int c = min(cb, bdata - NT);
+    const float* src = cb < bdata ? (c >= split ? Br2 : Br) + c
+                                  : (g.ones_col >= 0 && cb < bdata + NT ? one : g_dwd_zero);
+    const float4 x = dwd_ldw<NT, false>(src);
+    bv[0] = x.x;
+    if constexpr (NT >= 2) bv[1] = x.y;
+    if constexpr (NT == 3) bv[2] = x.z;
+    return;
   }
 #pragma unroll
   for (int h = 0; h < NB / 4; ++h) {
@@ -757,27 +818,29 @@ __device__ __forceinline__ bool use_dwd_fast() { return SMI_DWD_FAST != 0; }
 template <int MT, int NT, int NB, int RS>
 __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nsteps, int m0, int n0,
                                               int bdata, f32x4 (&acc)[MT][NT]) {
-  static_assert(MT == 4 || MT == 1, "fast dW loop: 4 m sub-tiles (float4 A) or 1 (scalar A)");
-  constexpr int NH = NB / 4;
+  static_assert(NB == NT || (NT == 8 && NB == 4), "fast dW loop: whole tiles or the lower half of 8");
+  constexpr int GW = NT < 4 ? NT : 4;             // columns per B load (NT < 4: the fitted edge's one run)
+  constexpr int NH = NB / GW;
   const int li = threadIdx.x & 15;
-  const float* pa = g.A + (int64_t)rw * g.a_cs + (MT == 4 ? min(m0 + 4 * li, g.M - 4)
-                                                          : min(m0 + li, g.M - 1));
+  const float* pa = g.A + (int64_t)rw * g.a_cs + min(m0 + MT * li, g.M - MT);
   const int64_t sa = (int64_t)RS * g.a_cs;
   const float* pb[NH];
   int64_t sb[NH];
 #pragma unroll
   for (int h = 0; h < NH; ++h) {
-    const int cb = n0 + 64 * h + 4 * li;
+    const int cb = n0 + 64 * h + GW * li;
     if (cb < bdata) {
-      if (g.B2 && cb >= g.split_col) {
-        pb[h] = g.B2 + (int64_t)rw * g.b2_rs + (cb - g.split_col);
+      const int c = NT < 4 ? min(cb, bdata - NT) : cb;   // (a fitted run ends with the data)
+      if (g.B2 && c >= g.split_col) {
+        pb[h] = g.B2 + (int64_t)rw * g.b2_rs + (c - g.split_col);
         sb[h] = (int64_t)RS * g.b2_rs;
       } else {
-        pb[h] = g.B + (int64_t)rw * g.b_rs + cb;
+        pb[h] = g.B + (int64_t)rw * g.b_rs + c;
         sb[h] = (int64_t)RS * g.b_rs;
       }
     } else {
-      pb[h] = cb == g.ones_col ? g_dwd_one : g_dwd_zero;
+      const bool ones = NT < 4 ? g.ones_col >= 0 && cb < bdata + NT : cb == g.ones_col;
+      pb[h] = ones ? g_dwd_one : g_dwd_zero;
       sb[h] = 0;
     }
   }
@@ -785,16 +848,13 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
   // global (addrspace 1) loads spelled out: with the prologue pinned below the
   // compiler no longer infers the address space and emits flat loads, which
   // also count against lgkmcnt
-  using gf4 = const __attribute__((address_space(1))) f32x4;
-  using gf1 = const __attribute__((address_space(1))) float;
-  auto f4 = [](const f32x4 x) { return float4{x[0], x[1], x[2], x[3]}; };
+  // (dwd_ldw: one load instruction per operand per step whatever the width)
   auto load = [&](int p) {
-    if constexpr (MT == 4) av[p] = f4(*(gf4*)pa);
-    else av[p].x = *(gf1*)pa;
+    av[p] = dwd_ldw<MT, true>(pa);
     pa += sa;
 #pragma unroll
     for (int h = 0; h < NH; ++h) {
-      bv[p][h] = f4(*(gf4*)pb[h]);
+      bv[p][h] = dwd_ldw<GW, true>(pb[h]);
       pb[h] += sb[h];
     }
   };
@@ -828,15 +888,20 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
   // replaces: without it the scheduler sinks all DWD_P refills to the end of
   // the unrolled body and the next iteration waits on them (vmcnt(9..0)), i.e.
   // no prefetch distance at all
-  // 16-wide tail tiles (MT == 1) run the longest slabs of a balanced grouped
-  // launch (~2.5x the rows of a full tile's slab): their MFMA chain restarts
-  // every DWD_P steps and the blocks are summed in a second register set, so
-  // a wave's fp32 chain is DWD_P + steps / DWD_P long instead of steps long
-  // (the value head's 1-row gradient sums 21504 rows with heavy cancellation)
+  // 16-wide tail tiles (MT == 1, whatever their width) run the longest slabs
+  // of a balanced grouped launch (~2.5x the rows of a full tile's slab): their
+  // MFMA chain restarts every DWD_P steps and the blocks are summed in a second
+  // register set, so a wave's fp32 chain is DWD_P + steps / DWD_P long instead
+  // of steps long (the value head's 1-row gradient sums 21504 rows with heavy
+  // cancellation).  The other fitted classes share their band's slabs with
+  // the full tiles and keep the full tiles' single chain.
+  constexpr bool kRestart = MT == 1;
   f32x4 tot[MT][NT];
-  if constexpr (MT == 1) {
+  if constexpr (kRestart) {
 #pragma unroll
-    for (int b = 0; b < NT; ++b) tot[0][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int a = 0; a < MT; ++a)
+#pragma unroll
+      for (int b = 0; b < NT; ++b) tot[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int s0 = DWD_P; s0 < nsteps; s0 += DWD_P) {
 #pragma unroll
@@ -847,19 +912,23 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
       if constexpr (SMI_DWD_DIAG != 1) load(p);
       __builtin_amdgcn_sched_barrier(0);
     }
-    if constexpr (MT == 1) {
+    if constexpr (kRestart) {
 #pragma unroll
-      for (int b = 0; b < NB; ++b) {
-        tot[0][b] += acc[0][b];
-        acc[0][b] = f32x4{0.f, 0.f, 0.f, 0.f};
-      }
+      for (int a = 0; a < MT; ++a)
+#pragma unroll
+        for (int b = 0; b < NB; ++b) {
+          tot[a][b] += acc[a][b];
+          acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
     }
   }
 #pragma unroll
   for (int p = 0; p < DWD_P; ++p) step(p);
-  if constexpr (MT == 1) {
+  if constexpr (kRestart) {
 #pragma unroll
-    for (int b = 0; b < NB; ++b) acc[0][b] = tot[0][b] + acc[0][b];
+    for (int a = 0; a < MT; ++a)
+#pragma unroll
+      for (int b = 0; b < NB; ++b) acc[a][b] = tot[a][b] + acc[a][b];
   }
 }
 
@@ -867,12 +936,16 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
 // every WV-th 4-row step of the slab, so a SIMD interleaves two waves' loads
 // and MFMAs; the waves' sums meet in LDS in a fixed tree order)
 template <int MT, int NT, bool VA, bool VB, int WV>
-__device__ __forceinline__ void dwd_tile(const GemmArgs& g, const TileIdx ti, float4* dwd_red) {
+__device__ __forceinline__ void dwd_tile(const GemmArgs& g, const DwEnt& e, const TileIdx ti,
+                                         float4* dwd_red) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int li = lane & 15, lk = lane >> 4;
-  const int m0 = ti.mt * 16 * MT, n0 = ti.nt * 16 * NT;
-  const int kb = ti.z * g.kchunk;
-  const int ke = min(g.K, kb + g.kchunk);
+  // (rows and columns of the GEMM, not of the rectangle: dw_put and the
+  // operand loads take them as they are)
+  const int m0 = e.m0 + ti.mt * 16 * MT, n0 = e.n0 + ti.nt * 16 * NT;
+  const int mend = e.m0 + e.M, nend = e.n0 + e.N;
+  const int kb = ti.z * e.kchunk;
+  const int ke = min(g.K, kb + e.kchunk);
   constexpr int RS = 4 * WV;                      // rows per step of the workgroup
   const int nsteps = (ke - kb + RS - 1) / RS;
   const int bdata = g.ones_col >= 0 ? g.ones_col : g.N;
@@ -906,14 +979,15 @@ __device__ __forceinline__ void dwd_tile(const GemmArgs& g, const TileIdx ti, fl
       }
     }
   };
-  // full slabs of 16-byte operands take the unchecked streaming loop
-  // (MT == 1: scalar A loads, no A alignment needed)
-  constexpr bool kFast = VB && ((VA && MT == 4) || MT == 1);
+  // full slabs whose operands each load with one instruction take the
+  // unchecked streaming loop (4-wide operands: 16-byte loads, VA / VB; fitted
+  // widths 1..3: always)
+  constexpr bool kFast = (VB || NT < 4) && (VA || MT < 4);
   bool fast = false;
   if constexpr (kFast)
     fast = use_dwd_fast() && nsteps >= DWD_P && nsteps % DWD_P == 0 && kb + nsteps * RS <= ke;
   constexpr int NBH = NT > 4 ? 4 : NT;
-  if (NT == 8 && n0 + 64 >= g.N) {
+  if (NT == 8 && n0 + 64 >= nend) {
     if constexpr (kFast) {
       if (fast) dwd_main_fast<MT, NT, NBH, RS>(g, rw, nsteps, m0, n0, bdata, acc);
       else mainloop(std::integral_constant<int, NBH>{});
@@ -961,20 +1035,38 @@ __device__ __forceinline__ void dwd_tile(const GemmArgs& g, const TileIdx ti, fl
   }
   if (wave != 0) return;
   // D(row lk*4+i, col li) of tile (a, b) is dW[m][n] with
-  // m = m0 + MT*(lk*4+i) + a, n = n0 + 64*(b/4) + 4*li + b%4
-  const bool vec_part = g.part && (g.N & 3) == 0;
+  // m = m0 + MT*(lk*4+i) + a, n = n0 + 64*(b/4) + 4*li + b%4 (fitted edges:
+  // the clamped runs of dwd_fit_col; a fitted N edge's bias column is
+  // component 0 of the first lane past the data)
+  auto out = [&](int m, int n, float v) {
+    if (e.part) e.part[((int64_t)ti.z * e.M + (m - e.m0)) * e.N + (n - e.n0)] = v;
+    else dw_put(g, m, n, v);
+  };
+  const bool vec_part = e.part && (e.N & 3) == 0;
 #pragma unroll
   for (int a = 0; a < MT; ++a)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int m = m0 + MT * (lk * 4 + i) + a;
-      if (m >= g.M) continue;
+      int m = m0 + MT * (lk * 4 + i) + a;
+      if constexpr (MT == 2 || MT == 3) m = dwd_fit_col<MT>(m0, g.M, lk * 4 + i, a);
+      if (m < 0 || m >= mend) continue;
+      if constexpr (NT < 4) {
+        const int cb = n0 + NT * li;
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          int n = cb < bdata ? dwd_fit_col<NT>(n0, bdata, li, t)
+                             : (t == 0 && g.ones_col >= 0 && cb < bdata + NT ? g.ones_col : -1);
+          if (n < 0 || n >= nend) continue;
+          out(m, n, acc[a][t][i]);
+        }
+        continue;
+      }
 #pragma unroll
       for (int h = 0; h < NT / 4; ++h) {
         const int nb = n0 + 64 * h + 4 * li;
         if (vec_part) {
-          if (nb < g.N)
-            *reinterpret_cast<float4*>(g.part + ((int64_t)ti.z * g.M + m) * g.N + nb) =
+          if (nb < nend)
+            *reinterpret_cast<float4*>(e.part + ((int64_t)ti.z * e.M + (m - e.m0)) * e.N + (nb - e.n0)) =
                 float4{acc[a][4 * h][i], acc[a][4 * h + 1][i], acc[a][4 * h + 2][i],
                        acc[a][4 * h + 3][i]};
           continue;
@@ -982,10 +1074,8 @@ __device__ __forceinline__ void dwd_tile(const GemmArgs& g, const TileIdx ti, fl
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const int n = nb + t;
-          if (n >= g.N) continue;
-          const float v = acc[a][4 * h + t][i];
-          if (g.part) g.part[((int64_t)ti.z * g.M + m) * g.N + n] = v;
-          else dw_put(g, m, n, v);
+          if (n >= nend) continue;
+          out(m, n, acc[a][4 * h + t][i]);
         }
       }
     }
@@ -996,7 +1086,9 @@ __global__ void __launch_bounds__(64 * WV, WV == 4 ? SMI_DWD_OCC : 1)
 gemm_dwd_kernel(GemmArgs g) {
   if (g.skip && g.skip[0] != 0) return;
   extern __shared__ float4 dwd_red[];            // 2 x [MT*NT][64] float4
-  dwd_tile<MT, NT, VA, VB, WV>(g, gemm_tile_index(), dwd_red);
+  DwEnt e{};                                     // the whole output as one rectangle
+  e.part = g.part; e.M = g.M; e.N = g.N; e.kchunk = g.kchunk;
+  dwd_tile<MT, NT, VA, VB, WV>(g, e, gemm_tile_index(), dwd_red);
 }
 
 // Grouped weight gradients: every dW GEMM of one backward phase (the head's
@@ -1006,18 +1098,23 @@ gemm_dwd_kernel(GemmArgs g) {
 // writes its own split-K partials, and one grouped reducer finishes them all.
 // One launch and one reduce per phase instead of a launch + reduce per layer
 // (and no side stream): the ~20 us fixed cost of a dW launch is paid once.
-constexpr int kDwGroupMax = 8;   // entries of one reducer (two launches' worth)
-constexpr int kDwSplitMax = 6;    // entries of one grouped launch after tail splits
+// Every GEMM is cut into up to four rectangles (DwEnt; dw_plan): its full 64 x
+// 64 tiles, an M edge and an N edge whose tiles are fitted to the remainder in
+// 16-wide sub-tiles, and their corner.  An entry's tiles are all of one class.
+constexpr int kDwGemmMax = 8;     // GEMMs of one reducer (two launches' worth)
+constexpr int kDwGroupMax = 16;   // entries of one reducer (C3: 4 + 4 + 4 + 2 of four GEMMs)
+constexpr int kDwSplitMax = 16;   // entries of one grouped launch
 struct DwGroup {
   DwEpilogue x;                  // optional epilogue task of the reducer (smi_internal.hpp)
-  GemmArgs g[kDwGroupMax];
-  int wg0[kDwGroupMax + 1];      // workgroup prefix
+  GemmArgs g[kDwGemmMax];
+  DwEnt e[kDwGroupMax];
+  int wg0[kDwGroupMax + 1];      // workgroup prefix (by entry; gemm_dwt16_kernel: by GEMM)
   int rb0[kDwGroupMax + 1];      // reducer-block prefix
-  int gm[kDwGroupMax], gn[kDwGroupMax], S[kDwGroupMax];
-  int vec[kDwGroupMax];          // 2*VA + VB
-  int narrow[kDwGroupMax];       // last m-tile is a 16-wide tail (M % 64 in 1..16)
-  int n;
+  int vec[kDwGemmMax];           // 2*VA + VB of each GEMM's 16-byte operand loads
+  int ng, n;                     // GEMMs, entries
 };
+// kernel arguments: 4 KiB (lstm_bwd_dw_kernel passes the BPTT's arguments too)
+static_assert(sizeof(DwGroup) + 128 <= 4096, "DwGroup must fit the kernel-argument segment");
 
 // output tile width of the grouped launch in 16-column sub-tiles, and its
 // occupancy.  Measured (C3 bench, one MI355X, interleaved trials): 64 x 64
@@ -1050,41 +1147,59 @@ extern "C" int smi_diag_dw_trace(void* dst, int n) {
 
 // one workgroup of a grouped launch: orig = its index among the launch's nwg
 // dW workgroups (the XCD-contiguous remap, gemm_tile_index, assumes orig and
-// the hardware's blockIdx agree mod 8); gi / rows report the entry and slab
-// length for the clock trace
+// the hardware's blockIdx agree mod 8); ei / rows report the entry, slab
+// length and tile class for the clock trace
 template <int WV>
 __device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nwg, float4* dwd_red,
-                                              int& gi, int& rows) {
+                                              int& ei, int& rows) {
   int w = orig;
   if (nwg > 8) {                                  // XCD-contiguous runs (gemm_tile_index)
     const int x = orig & 7, q = nwg >> 3, r = nwg & 7;
     w = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
   }
-  gi = 0;
-  while (gi + 1 < G.n && w >= G.wg0[gi + 1]) ++gi;
-  const GemmArgs& g = G.g[gi];
+  ei = 0;
+  while (ei + 1 < G.n && w >= G.wg0[ei + 1]) ++ei;
+  // (copies: the tile bodies below then read these, not G -- with every class
+  // reading the kernel argument itself the compiler stops resolving its uses
+  // to the argument segment and keeps a copy of all of G in scratch)
+  const DwEnt e = G.e[ei];
+  const GemmArgs g = G.g[e.gi];
   if (g.skip && g.skip[0] != 0) return;
-  const int local = w - G.wg0[gi], gn = G.gn[gi], gm = G.gm[gi];
+  const int local = w - G.wg0[ei];
   TileIdx ti;
-  ti.nt = local % gn;
-  ti.mt = (local / gn) % gm;
-  ti.z = local / (gn * gm);
-  rows = (min(g.K, (ti.z + 1) * g.kchunk) - ti.z * g.kchunk) |
-         ((G.narrow[gi] && ti.mt == gm - 1) << 16) | (G.vec[gi] << 17);
-  if (G.narrow[gi] && ti.mt == gm - 1) {
-    // a tail of <= 16 gradient rows (M 8 / 200 / 400 at C3) on one 16-wide
-    // m sub-tile instead of a 64-wide tile that is >= 75 % padding
-    ti.mt *= 4;                                   // m0 = 16 * mt = 64 * (gm - 1)
-    if (G.vec[gi] & 1) dwd_tile<1, DWG_NT, false, true, WV>(g, ti, dwd_red);
-    else dwd_tile<1, DWG_NT, false, false, WV>(g, ti, dwd_red);
-    return;
+  ti.nt = local % e.gn;
+  ti.mt = (local / e.gn) % e.gm;
+  ti.z = local / (e.gn * e.gm);
+  rows = (min(g.K, (ti.z + 1) * e.kchunk) - ti.z * e.kchunk) | (e.cls << 16);
+  // the entry's tile class: MT x NT sub-tiles; VA / VB: 16-byte loads of a
+  // 4-wide operand (fitted widths 1..3 always load with one instruction)
+#define SMI_DWT(MT_, NT_, VA_, VB_) \
+  case dw_cls(MT_, NT_, VA_, VB_): dwd_tile<MT_, NT_, VA_, VB_, WV>(g, e, ti, dwd_red); break;
+#define SMI_DWT3(NT_, VB_) SMI_DWT(1, NT_, false, VB_) SMI_DWT(2, NT_, false, VB_) SMI_DWT(3, NT_, false, VB_)
+  switch (e.cls) {
+    SMI_DWT(4, DWG_NT, true, true) SMI_DWT(4, DWG_NT, true, false)
+    SMI_DWT(4, DWG_NT, false, true) SMI_DWT(4, DWG_NT, false, false)
+    SMI_DWT(1, DWG_NT, false, true) SMI_DWT(1, DWG_NT, false, false)
+    default: break;
   }
-  switch (G.vec[gi]) {
-    case 3: dwd_tile<4, DWG_NT, true, true, WV>(g, ti, dwd_red); break;
-    case 2: dwd_tile<4, DWG_NT, true, false, WV>(g, ti, dwd_red); break;
-    case 1: dwd_tile<4, DWG_NT, false, true, WV>(g, ti, dwd_red); break;
-    default: dwd_tile<4, DWG_NT, false, false, WV>(g, ti, dwd_red); break;
+#if SMI_DWG_NT == 4
+#define SMI_DWT_FIT 1
+#else
+#define SMI_DWT_FIT 0
+#endif
+  // (the fitted classes run on the 4-wave launch only: dw_fit_level)
+  if constexpr (SMI_DWT_FIT && WV == 4) {
+    switch (e.cls) {
+      SMI_DWT(2, DWG_NT, false, true) SMI_DWT(3, DWG_NT, false, true)
+      SMI_DWT(2, DWG_NT, false, false) SMI_DWT(3, DWG_NT, false, false)
+      SMI_DWT(4, 1, true, false) SMI_DWT(4, 2, true, false) SMI_DWT(4, 3, true, false)
+      SMI_DWT(4, 1, false, false) SMI_DWT(4, 2, false, false) SMI_DWT(4, 3, false, false)
+      SMI_DWT3(1, false) SMI_DWT3(2, false) SMI_DWT3(3, false)
+      default: break;
+    }
   }
+#undef SMI_DWT3
+#undef SMI_DWT
 }
 
 template <int WV>
@@ -1289,17 +1404,18 @@ gemm_group_reduce_kernel(DwGroup G) {
     return;
   }
   const int b = (int)blockIdx.x - ep;
-  int gi = 0;
-  while (gi + 1 < G.n && b >= G.rb0[gi + 1]) ++gi;
-  const GemmArgs& g = G.g[gi];
+  int ei = 0;
+  while (ei + 1 < G.n && b >= G.rb0[ei + 1]) ++ei;
+  const DwEnt& en = G.e[ei];
+  const GemmArgs& g = G.g[en.gi];
   if (g.skip && g.skip[0] != 0) return;
-  const int S = G.S[gi];
-  const int64_t MN = (int64_t)g.M * g.N;
+  const int S = en.S;
+  const int64_t MN = (int64_t)en.M * en.N;
   const int el = threadIdx.x & 63, zl = threadIdx.x >> 6;
-  const int64_t eb = (int64_t)(b - G.rb0[gi]) * 64 * U;
+  const int64_t eb = (int64_t)(b - G.rb0[ei]) * 64 * U;
   const float* p[U];
 #pragma unroll
-  for (int u = 0; u < U; ++u) p[u] = g.part + min(eb + el + 64 * u, MN - 1);
+  for (int u = 0; u < U; ++u) p[u] = en.part + min(eb + el + 64 * u, MN - 1);
   float r[U];
   red_slabs<U>(p, MN, S, zl, r);
 #pragma unroll
@@ -1310,8 +1426,8 @@ gemm_group_reduce_kernel(DwGroup G) {
     const int64_t e = eb + i;
     if (e < MN) {
       const float v = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
-      const int m = (int)(e / g.N), n = (int)(e - (int64_t)m * g.N);
-      q += dw_put(g, m, n, v);
+      const int m = (int)(e / en.N), n = (int)(e - (int64_t)m * en.N);
+      q += dw_put(g, en.m0 + m, en.n0 + n, v);
     }
   }
   if (!G.x.sq) return;
@@ -1573,7 +1689,7 @@ static thread_local bool g_grp_missed = false;
 int dw_group_begin() {
   g_grp_on = true;
   g_grp_missed = false;
-  g_grp.n = 0;
+  g_grp.ng = g_grp.n = 0;
   g_grp.x = DwEpilogue{};
   g_grp_flops = 0.0;
   return SMI_OK;
@@ -1591,7 +1707,7 @@ int dw_group_epilogue(const DwEpilogue& x) {
 
 static bool dw_group_add(const GemmArgs& g) {
   if (!g_grp_on) return false;
-  if (g_grp.n >= kDwGroupMax) {
+  if (g_grp.ng >= kDwGemmMax) {
     g_grp_missed = true;
     return false;
   }
@@ -1600,9 +1716,12 @@ static bool dw_group_add(const GemmArgs& g) {
   const bool va = al16(g.A) && g.M >= 4 && g.M % 4 == 0 && g.a_cs % 4 == 0;
   const bool vb = al16(g.B) && bdata >= 4 && bdata % 4 == 0 && g.b_rs % 4 == 0 &&
                   (!g.B2 || (al16(g.B2) && g.b2_rs % 4 == 0 && g.split_col % 4 == 0));
-  const int i = g_grp.n++;
+  const int i = g_grp.ng++;
   g_grp.g[i] = g;
-  g_grp.vec[i] = (va ? 2 : 0) + (vb ? 1 : 0);
+  // (bits 4 / 8: the dY / X bases are 16-byte aligned, the rule for the fitted
+  // edges' 2- and 3-wide loads, which take any row stride and extent)
+  g_grp.vec[i] = (va ? 2 : 0) + (vb ? 1 : 0) + (al16(g.A) ? 4 : 0) +
+                 (al16(g.B) && (!g.B2 || al16(g.B2)) ? 8 : 0);
   const int nreal = (g.ones_col >= 0 ? g.N - 1 : g.N) - (g.B2 ? g.split_col - g.c1_real : 0);
   g_grp_flops += 2.0 * g.M * (double)nreal * g.K + (g.ones_col >= 0 ? (double)g.M * g.K : 0.0);
   return true;
@@ -1662,14 +1781,21 @@ static int dwd_group_slots(size_t lds) {
     slots = dwd_waves() == 8 ? resident_grid(gemm_dwd_group_kernel<8>, 512, lds)
                              : resident_grid(gemm_dwd_group_kernel<4>, 256, lds);
     if (slots < 1) slots = 256;
+    // planned for the occupancy the 4-wave kernel is built for (SMI_DWG_OCC),
+    // not for what a build that happens to need fewer registers could reach:
+    // the slot count sets the slab lengths, and with them every result's
+    // rounding (a leaner build reached 4 per CU and moved every slab)
+    if (dwd_waves() == 4) {
+      int dev = 0, cus = 0;
+      (void)hipGetDevice(&dev);
+      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+          cus > 0 && slots > cus * SMI_DWG_OCC)
+        slots = cus * SMI_DWG_OCC;
+    }
   }
   return slots;
 }
 
-// Tail splits, balanced slabs and the split-K partials of G's entries, placed
-// ws_off floats into the workspace; wv: waves per workgroup of the launch that
-// runs them, slots: its resident workgroups.  Sets G.wg0 / rb0 / S / part and
-// need (floats used from ws_off).
 // 64-element groups per block of the grouped reducer (SMI_RED_U=1: one, the
 // round-5 form; A/B knob)
 static int red_u() {
@@ -1677,66 +1803,143 @@ static int red_u() {
   return u;
 }
 
-static int dw_prepare(DwGroup& G, int wv, int slots, int64_t ws_off, int64_t& need,
-                      int target_fixed = 0) {
-  constexpr int MT = 4, NT = DWG_NT;
+// One GEMM as the planner sees it, and the plan of one grouped launch: pure
+// host arithmetic (no device call, no pointers), so a CPU test can sweep it
+// (smi_diag_dw_plan).
+struct DwPlanGemm {
+  int M, N, K;
+  int vec;                        // 2*VA + VB: 16-byte loads of the 4-wide A / B operands;
+                                  // + 4 / 8: the A / B base pointers are 16-byte aligned
+  int ones;                       // the last column is the bias gradient's all-ones column
+  int split_col;                  // two-source B: first column of the second source, -1: one source
+};
+struct DwPlanEnt {
+  int gi, m0, n0, M, N, mt, nt, cls, gm, gn, kchunk, S;
+  int64_t part_off;               // its partials, floats from the plan's base
+};
+struct DwPlan {
+  DwPlanEnt e[kDwSplitMax];
+  int wg0[kDwSplitMax + 1], rb0[kDwSplitMax + 1];
+  int n;
+  int64_t need;                   // floats of partials
+};
+
+// The rectangles of one GEMM (up to four: interior, M edge, N edge, corner;
+// an empty one is not made).  Edge tiles are fitted to the remainder in 16-
+// wide sub-tiles: MT' = ceil((M mod 64) / 16) and NT' = ceil((N mod 64) / 16),
+// a lane loading its MT' (NT') consecutive columns with one instruction.  A
+// fitted N edge keeps the bias column in a lane of its own (dwd_load), so its
+// data columns must fit 15 lanes; a two-source operand is fitted only where a
+// lane's run cannot straddle the sources (one column per lane, or the edge
+// wholly in the second source); 2- and 3-wide loads want the operand's base
+// 16-byte aligned, as VA / VB do.  An edge that cannot be fitted stays 4 wide
+// (the padded tile, 16-byte or per-column loads as before).  fit 0: the whole
+// GEMM as one rectangle of padded 64 x 64 tiles; fit 1: only an M remainder of
+// <= 16 rows is cut off, as 16-wide tail tiles over padded columns (the classes
+// of the 8-wave launch, dw_fit_level).
+static int dw_plan_rects(const DwPlanGemm& p, int gi, int fit, DwPlanEnt* out) {
+  const bool va = (p.vec & 2) != 0, vb = (p.vec & 1) != 0;
+  auto ent = [&](int m0, int n0, int M, int N, int mt, int nt) {
+    DwPlanEnt e{};
+    e.gi = gi; e.m0 = m0; e.n0 = n0; e.M = M; e.N = N; e.mt = mt; e.nt = nt;
+    e.cls = dw_cls(mt, nt, va, vb);
+    e.gm = (M + 16 * mt - 1) / (16 * mt);
+    e.gn = (N + 16 * nt - 1) / (16 * nt);
+    return e;
+  };
+  const int Mf = p.M / 64 * 64, Me = p.M - Mf, Nf = p.N / 64 * 64, Ne = p.N - Nf;
+  if (fit == 1 && Me >= 1 && Me <= 16) {
+    int k = 0;
+    if (Mf) out[k++] = ent(0, 0, Mf, p.N, 4, DWG_NT);
+    out[k++] = ent(Mf, 0, Me, p.N, 1, DWG_NT);
+    return k;
+  }
+  if (fit < 2) {
+    out[0] = ent(0, 0, p.M, p.N, 4, DWG_NT);
+    return 1;
+  }
+  int mte = (Me + 15) / 16, nte = 0;
+  if ((mte == 2 || mte == 3) && !(p.vec & 4)) mte = 4;
+  if (Ne > 0) {
+    const int R = Ne - (p.ones ? 1 : 0);            // data columns of the edge
+    nte = p.ones ? std::max(1, (R + 14) / 15) : (R + 15) / 16;
+    if (nte > 4) nte = 4;
+    if (p.split_col >= 0 && nte > 1 && Nf < p.split_col) nte = 4;
+    if ((nte == 2 || nte == 3) && !(p.vec & 8)) nte = 4;
+    // (a 16-wide tail's chain restarts in the streaming loop only, which its
+    // padded tiles take with 16-byte X loads only: keep the same loop)
+    if (mte == 1 && !vb) nte = 4;
+  }
+  int n = 0;
+  if (Mf && Nf) out[n++] = ent(0, 0, Mf, Nf, 4, 4);
+  if (Me && Nf) out[n++] = ent(Mf, 0, Me, Nf, mte, 4);
+  if (Mf && Ne) out[n++] = ent(0, Nf, Mf, Ne, 4, nte);
+  if (Me && Ne) out[n++] = ent(Mf, Nf, Me, Ne, mte, nte);
+  return n;
+}
+
+// fitted edge classes on the 4-wave launch (the product's); the 8-wave launch
+// (SMI_DWD_WAVES=8, and the weight gradients that share the BPTT's launch)
+// keeps the 16-wide M tail alone; SMI_DWD_NARROW=0: padded tiles everywhere
+static int dw_fit_level(int wv) {
+  if (!use_dwd_narrow()) return 0;
+  return wv == 4 && DWG_NT == 4 ? 2 : 1;
+}
+
+// Rectangles, slabs and partial offsets of one grouped launch of ng GEMMs: wv
+// waves per workgroup, slots resident workgroups, cap floats of workspace, at
+// most max_ent entries (a GEMM whose rectangles no longer fit is cut less).
+// Returns 0, or -1 when the partials cannot fit cap.
+//
+// Slab lengths decide the VALUE of every output element (which rows meet in
+// one fp32 MFMA chain), the tile geometry does not: an MFMA's output columns
+// are independent.  So the slabs are balanced over ROW BANDS exactly as before
+// the edges were fitted -- a GEMM is one band, or two when its <= 16-row tail
+// is cut off and given longer slabs (a tail tile costs ~0.4 of a full tile per
+// row) -- priced by their padded 64-wide tiles, and every rectangle takes the
+// slabs of its band.  Fitting changes how much of a tile a workgroup computes,
+// never which rows an element sums in which order: results are bit-identical
+// to the padded launch's.
+static int dw_plan(const DwPlanGemm* gemms, int ng, int wv, int slots, int64_t cap, int max_ent,
+                   int target_fixed, DwPlan& P) {
+  constexpr int kBandMax = 6;                       // bands of one launch (tail cuts while there is room)
+  constexpr int NTF = DWG_NT;
   const int rs = 4 * wv * DWD_P;                    // rows per prefetch window
-  auto al16 = [](const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  // A GEMM whose last m-tile is a <= 16-row tail (M 8 / 200 / 400 at C3) is
-  // split, while the group has room, into its full 64-row tiles and a tail
-  // entry: the tail's tiles then get their own, longer slabs (below).  The
-  // tail entry addresses rows m0.. of dY and of every destination.
-  {
-    const int n0 = G.n;
-    DwGroup E = G;
-    int n = 0;
-    for (int i = 0; i < n0; ++i) {
-      const GemmArgs& g = G.g[i];
-      const int tail = g.M % (16 * MT);
-      const bool split = use_dwd_narrow() && tail > 0 && tail <= 16 && g.M > 16 * MT &&
-                         g.a_rs == 1 && n + (n0 - i) + 1 <= kDwSplitMax;
-      E.g[n] = g;
-      E.vec[n] = G.vec[i];
-      if (!split) { ++n; continue; }
-      const int m0 = g.M - tail;
-      E.g[n].M = m0;                                  // the full tiles (vec unchanged)
-      ++n;
-      GemmArgs t = g;
-      t.M = tail;
-      t.A = g.A + m0;
-      if (t.C) t.C = g.C + (int64_t)m0 * g.ldc;
-      if (t.C2) t.C2 = g.C2 + (int64_t)m0 * g.ldc2;
-      if (t.bias_out) t.bias_out = g.bias_out + m0;
-      if (t.bias_out2) t.bias_out2 = g.bias_out2 + m0;
-      const bool va = al16(t.A) && t.M >= 4 && t.M % 4 == 0 && t.a_cs % 4 == 0;
-      E.g[n] = t;
-      E.vec[n] = (va ? 2 : 0) + (G.vec[i] & 1);
-      ++n;
+  if (max_ent > kDwSplitMax) max_ent = kDwSplitMax;
+  struct Band { int gi, m0, M; int64_t tiles; double cost; int64_t kc; };
+  Band band[2 * kDwGemmMax];
+  int nb = 0, tail_band[kDwGemmMax];                // (the GEMM's tail band, -1: one band)
+  int first_band[kDwGemmMax];
+  double work = 0.0, work_u = 0.0;                  // tiles x rows (x cost)
+  for (int i = 0; i < ng; ++i) {
+    const DwPlanGemm& g = gemms[i];
+    const int tail = g.M % 64, gn = (g.N + 16 * NTF - 1) / (16 * NTF);
+    const bool narrow = use_dwd_narrow() && tail > 0 && tail <= 16;
+    const bool cut = narrow && g.M > 64 && nb + (ng - i) + 1 <= kBandMax;
+    first_band[i] = nb;
+    tail_band[i] = -1;
+    if (cut) {
+      band[nb++] = Band{i, 0, g.M - tail, (int64_t)(g.M / 64) * gn, 1.0, 0};
+      tail_band[i] = nb;
+      band[nb++] = Band{i, g.M - tail, tail, gn, dwd_narrow_cost(), 0};
+    } else {
+      const int gm = (g.M + 63) / 64;
+      band[nb++] = Band{i, 0, g.M, (int64_t)gm * gn,
+                        narrow ? ((gm - 1) + dwd_narrow_cost()) / gm : 1.0, 0};
     }
-    E.n = n;
-    G = E;
+  }
+  for (int b = 0; b < nb; ++b) {
+    work_u += (double)band[b].tiles * gemms[band[b].gi].K;
+    work += (double)band[b].tiles * gemms[band[b].gi].K * band[b].cost;
   }
   // Balanced workgroups.  A launch with more work than one resident round
   // (CUs x occupancy) runs as whole rounds (one at C3: a second, partly filled
   // round was the launch's tail — the per-workgroup clock trace showed the
-  // last 40 % of the span at falling concurrency), and each entry's slab
+  // last 40 % of the span at falling concurrency), and each band's slab
   // length is set so that its slabs cost about the same time (tail tiles ~0.4
   // of a full tile per row).  Below one round every workgroup is resident
   // anyway and the span is the longest slab: equal slab lengths (shorter
   // fp32 chains on the tail tiles).
-  double cost[kDwGroupMax], work = 0.0, work_u = 0.0;  // tiles x rows (x cost)
-  int64_t tiles[kDwGroupMax];
-  for (int i = 0; i < G.n; ++i) {
-    const GemmArgs& g = G.g[i];
-    const int tail = g.M % (16 * MT);
-    G.narrow[i] = use_dwd_narrow() && tail > 0 && tail <= 16;
-    G.gm[i] = (g.M + 16 * MT - 1) / (16 * MT);
-    G.gn[i] = (g.N + 16 * NT - 1) / (16 * NT);
-    tiles[i] = (int64_t)G.gm[i] * G.gn[i];
-    cost[i] = G.narrow[i] ? ((G.gm[i] - 1) + dwd_narrow_cost()) / G.gm[i] : 1.0;
-    work_u += (double)tiles[i] * g.K;
-    work += (double)tiles[i] * g.K * cost[i];
-  }
   int target = target_fixed > 0 ? target_fixed : dw_group_target(work_u);
   static const bool env_target = [] {
     const char* e = getenv("SMI_DWD_GROUP_TARGET");
@@ -1753,53 +1956,123 @@ static int dw_prepare(DwGroup& G, int wv, int slots, int64_t ws_off, int64_t& ne
     const int rounds = (int)std::max(1.0, std::ceil(work / (slots * round_rows)));
     target = slots * rounds;
   } else {
-    for (int i = 0; i < G.n; ++i) cost[i] = 1.0;
+    for (int b = 0; b < nb; ++b) band[b].cost = 1.0;
     work = work_u;
   }
-  const int64_t cap = smi_workspace_floats() - ws_off;
   double r0 = work / target;                        // cost-rows per workgroup
-  int64_t kcs[kDwGroupMax];
   // slab lengths are rounded up to whole prefetch windows, so the workgroup
   // count can land a few above the target; in whole rounds every extra
   // workgroup is a second round of its own (the C3 launch was 769 for 768
   // slots: the last workgroup started at 59 us and set the span), so the
   // cost-rows per workgroup grow in small steps until the count fits
   const bool rounds_fit = !fixed_target && target >= slots;
-  need = 0;
   for (int pass = 0; pass < 400; ++pass) {
-    need = 0;
-    int64_t wgs = 0;
-    for (int i = 0; i < G.n; ++i) {
-      const GemmArgs& g = G.g[i];
-      int64_t S = (int64_t)(g.K * cost[i] / r0 + 0.5);
+    int64_t need = 0, wgs = 0;
+    for (int b = 0; b < nb; ++b) {
+      const DwPlanGemm& g = gemms[band[b].gi];
+      int64_t S = (int64_t)(g.K * band[b].cost / r0 + 0.5);
       if (S < 1) S = 1;
       int64_t kc = ((g.K + S - 1) / S + rs - 1) / rs * rs;
       if (kc < 2 * rs) kc = 2 * rs;                 // >= 8 MFMA steps per wave
       if (kc >= g.K) kc = ((int64_t)g.K + rs - 1) / rs * rs;
-      kcs[i] = kc;
-      const int64_t s_i = (g.K + kc - 1) / kc;
-      need += s_i * g.M * g.N;
-      wgs += s_i * tiles[i];
+      band[b].kc = kc;
+      const int64_t s_b = (g.K + kc - 1) / kc;
+      need += s_b * band[b].M * g.N;
+      wgs += s_b * band[b].tiles;
     }
     if (need > cap) { r0 *= 2.0; continue; }         // grow the slabs until the partials fit
     if (rounds_fit && wgs > target && wgs <= 2 * target) { r0 *= 1.005; continue; }
     break;
   }
+  // the rectangles, each on its band's slabs (a fitted tile stands where a
+  // padded one stood: the workgroup count is the bands')
+  P.n = 0;
+  for (int i = 0; i < ng; ++i) {
+    DwPlanEnt r[4];
+    int k = 0;
+    for (int fit = dw_fit_level(wv); fit >= 0; --fit) {
+      k = dw_plan_rects(gemms[i], i, fit, r);
+      if (P.n + k + (ng - 1 - i) <= max_ent) break;
+    }
+    if (k == 0 || P.n + k > max_ent) return -1;
+    for (int j = 0; j < k; ++j) {
+      const int b = tail_band[i] >= 0 && r[j].m0 >= band[tail_band[i]].m0 ? tail_band[i] : first_band[i];
+      r[j].kchunk = (int)band[b].kc;
+      r[j].S = (int)((gemms[i].K + band[b].kc - 1) / band[b].kc);
+      P.e[P.n++] = r[j];
+    }
+  }
+  int64_t off = 0;
+  P.wg0[0] = 0;
+  P.rb0[0] = 0;
+  for (int i = 0; i < P.n; ++i) {
+    DwPlanEnt& e = P.e[i];
+    e.part_off = off;
+    off += ((int64_t)e.S * e.M * e.N + 3) / 4 * 4;   // (every entry's partials 16-byte aligned)
+    P.wg0[i + 1] = P.wg0[i] + e.gm * e.gn * e.S;
+    P.rb0[i + 1] = P.rb0[i] + (int)(((int64_t)e.M * e.N + 64 * red_u() - 1) / (64 * red_u()));
+  }
+  if (off > cap) return -1;
+  P.need = off;
+  return 0;
+}
+
+// the planner over plain integers (CPU tests; no device call): gemms = ng x
+// {M, N, K, vec, ones, split_col}; out = up to max_ent x {gi, m0, n0, M, N,
+// mt, nt, kchunk, S, wg0, rb0, part_off}, tot = {workgroups, reducer blocks,
+// floats of partials, rows per prefetch window}.  Returns the entry count.
+extern "C" int smi_diag_dw_plan(const int* gemms, int ng, int waves, int slots, int64_t cap_floats,
+                                int max_ent, int64_t* out, int64_t* tot) {
+  if (!gemms || !out || !tot || ng < 1 || ng > kDwGemmMax || (waves != 4 && waves != 8) ||
+      slots < 1 || max_ent < 1)
+    return set_error(SMI_E_ARG, "smi_diag_dw_plan: bad arguments");
+  DwPlanGemm pg[kDwGemmMax];
+  for (int i = 0; i < ng; ++i) {
+    pg[i] = DwPlanGemm{gemms[6 * i], gemms[6 * i + 1], gemms[6 * i + 2], gemms[6 * i + 3],
+                       gemms[6 * i + 4], gemms[6 * i + 5]};
+    if (pg[i].M < 1 || pg[i].N < 1 || pg[i].K < 1 || pg[i].M > 512 || pg[i].N > 512)
+      return set_error(SMI_E_ARG, "smi_diag_dw_plan: GEMM outside the grouped kernel's range");
+  }
+  DwPlan P;
+  if (dw_plan(pg, ng, waves, slots, cap_floats, max_ent, 0, P))
+    return set_error(SMI_E_ARG, "smi_diag_dw_plan: the partials do not fit");
+  for (int i = 0; i < P.n; ++i) {
+    const DwPlanEnt& e = P.e[i];
+    const int64_t row[12] = {e.gi, e.m0, e.n0, e.M, e.N, e.mt, e.nt, e.kchunk, e.S,
+                             P.wg0[i], P.rb0[i], e.part_off};
+    for (int j = 0; j < 12; ++j) out[12 * i + j] = row[j];
+  }
+  tot[0] = P.wg0[P.n]; tot[1] = P.rb0[P.n]; tot[2] = P.need; tot[3] = 4 * waves * DWD_P;
+  return P.n;
+}
+
+// Plans G's ng queued GEMMs (dw_plan) and places the partials ws_off floats
+// into the workspace; wv: waves per workgroup of the launch that runs them,
+// slots: its resident workgroups.  Sets G.e / n / wg0 / rb0 and need (floats
+// used from ws_off).
+static int dw_prepare(DwGroup& G, int wv, int slots, int64_t ws_off, int64_t& need, int max_ent,
+                      int target_fixed = 0) {
+  DwPlanGemm pg[kDwGemmMax];
+  for (int i = 0; i < G.ng; ++i) {
+    const GemmArgs& g = G.g[i];
+    pg[i] = DwPlanGemm{g.M, g.N, g.K, G.vec[i], g.ones_col >= 0 ? 1 : 0, g.B2 ? g.split_col : -1};
+  }
+  DwPlan P;
+  if (dw_plan(pg, G.ng, wv, slots, smi_workspace_floats() - ws_off, max_ent, target_fixed, P))
+    return set_error(SMI_E_ARG, "gemm: workspace too small for the grouped dW partials");
+  need = P.need;
   float* base = workspace_f32(ws_off + need);
   if (!base) return set_error(SMI_E_ARG, "gemm: workspace too small for the grouped dW partials");
   base += ws_off;
-  int64_t off = 0;
-  G.wg0[0] = 0;
-  G.rb0[0] = 0;
-  for (int i = 0; i < G.n; ++i) {
-    GemmArgs& g = G.g[i];
-    g.kchunk = (int)kcs[i];
-    G.S[i] = (int)((g.K + kcs[i] - 1) / kcs[i]);
-    g.part = base + off;
-    off += (int64_t)G.S[i] * g.M * g.N;
-    G.wg0[i + 1] = G.wg0[i] + (int)(tiles[i] * G.S[i]);
-    G.rb0[i + 1] = G.rb0[i] + (int)(((int64_t)g.M * g.N + 64 * red_u() - 1) / (64 * red_u()));
+  G.n = P.n;
+  for (int i = 0; i < P.n; ++i) {
+    const DwPlanEnt& p = P.e[i];
+    DwEnt& e = G.e[i];
+    e.part = base + p.part_off;
+    e.gi = p.gi; e.m0 = p.m0; e.n0 = p.n0; e.M = p.M; e.N = p.N;
+    e.kchunk = p.kchunk; e.S = p.S; e.gm = p.gm; e.gn = p.gn; e.cls = p.cls;
   }
+  for (int i = 0; i <= P.n; ++i) { G.wg0[i] = P.wg0[i]; G.rb0[i] = P.rb0[i]; }
   return SMI_OK;
 }
 
@@ -1829,7 +2102,7 @@ gemm_dwt16_kernel(DwGroup G) {
   __shared__ f32x4 red[4][64];
   const int b = blockIdx.x;
   int gi = 0;
-  while (gi + 1 < G.n && b >= G.wg0[gi + 1]) ++gi;
+  while (gi + 1 < G.ng && b >= G.wg0[gi + 1]) ++gi;
   const GemmArgs& g = G.g[gi];
   if (g.skip && g.skip[0] != 0) return;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1896,7 +2169,7 @@ gemm_dwt16_kernel(DwGroup G) {
 
 static void dwt16_prefix(DwGroup& G) {
   G.wg0[0] = 0;
-  for (int i = 0; i < G.n; ++i)
+  for (int i = 0; i < G.ng; ++i)
     G.wg0[i + 1] = G.wg0[i] + ((G.g[i].M + 15) / 16) * ((G.g[i].N + 15) / 16);
 }
 
@@ -1907,6 +2180,31 @@ static thread_local bool g_pre_on = false;
 static thread_local int64_t g_pre_need = 0;
 
 constexpr size_t kDwdLds = (size_t)2 * 4 * DWG_NT * 64 * sizeof(float4);
+
+// the form name of a grouped launch or of its reducer (smi_last_launch): the
+// distinct tile classes of its entries in entry order, MT x NT sub-tiles, a
+// 4-wide operand marked v (16-byte loads) or s (per-column loads), e.g.
+// gemm_group_reduce_kernel<gemm_dwd_group_kernel<4vx4v,1x4v,4vx3,1x3>>
+static const char* dw_group_name(const DwGroup& G, bool reducer) {
+  static thread_local char buf[2][320];
+  char* b = buf[reducer ? 1 : 0];
+  size_t o = (size_t)snprintf(b, sizeof(buf[0]), "%s", reducer ? "gemm_group_reduce_kernel<gemm_dwd_group_kernel<"
+                                                            : "gemm_dwd_group_kernel<");
+  int seen[kDwGroupMax], ns = 0;
+  for (int i = 0; i < G.n; ++i) {
+    const int c = G.e[i].cls;
+    bool dup = false;
+    for (int j = 0; j < ns; ++j) dup = dup || seen[j] == c;
+    if (dup) continue;
+    seen[ns++] = c;
+    const int mt = c & 7, nt = (c >> 3) & 15;
+    o += (size_t)snprintf(b + o, sizeof(buf[0]) - o, "%s%d%sx%d%s", ns > 1 ? "," : "", mt,
+                          mt == 4 ? ((c >> 7) & 1 ? "v" : "s") : "", nt,
+                          nt >= 4 ? ((c >> 8) & 1 ? "v" : "s") : "");
+  }
+  snprintf(b + o, sizeof(buf[0]) - o, "%s", reducer ? ">>" : ">");
+  return b;
+}
 
 int dw_group_flush(hipStream_t st) {
   g_grp_on = false;
@@ -1921,7 +2219,8 @@ int dw_group_flush(hipStream_t st) {
   if (G.x.on && G.x.sq && missed)
     return set_error(SMI_E_ARG, "dw group: a fused sum of squares needs every dW GEMM of the "
                                 "bracket in the group (one ran outside it)");
-  if (G.n == 0 && !pre) {
+  G.n = 0;
+  if (G.ng == 0 && !pre) {
     if (!G.x.on) return SMI_OK;
     if (G.x.sq) return set_error(SMI_E_ARG, "dw group: fused sum of squares over an empty group");
     G.rb0[0] = 0;                                   // the epilogue task alone
@@ -1931,26 +2230,28 @@ int dw_group_flush(hipStream_t st) {
   // short batches (every entry <= 512 rows, one group, no epilogue task):
   // 16 x 16 tiles written directly, no partials and no reducer
   if (!pre && !G.x.on && use_t16()) {
-    bool small = G.n > 0;
-    for (int i = 0; i < G.n; ++i) small = small && G.g[i].K <= 4 * 16 * T16_MAXC;
+    bool small = G.ng > 0;
+    for (int i = 0; i < G.ng; ++i) small = small && G.g[i].K <= 4 * 16 * T16_MAXC;
     if (small) {
       dwt16_prefix(G);
       const int kslot = ktime_begin(st);
-      hipLaunchKernelGGL(gemm_dwt16_kernel, dim3(G.wg0[G.n]), dim3(kWG), 0, st, G);
+      hipLaunchKernelGGL(gemm_dwt16_kernel, dim3(G.wg0[G.ng]), dim3(kWG), 0, st, G);
       ktime_end(kslot, KT_GEMM_DW, g_grp_flops, st);
       return check_launch("gemm_dwt16_kernel");
     }
   }
   int64_t need = 0;
-  if (G.n > 0) {
-    RC_CHECK(dw_prepare(G, dwd_waves(), dwd_group_slots(kDwdLds), 0, need));
+  if (G.ng > 0) {
+    if (pre && g_pre.ng + G.ng > kDwGemmMax) return set_error(SMI_E_ARG, "dw group: too many GEMMs");
+    RC_CHECK(dw_prepare(G, dwd_waves(), dwd_group_slots(kDwdLds), 0, need,
+                        kDwGroupMax - (pre ? g_pre.n : 0)));
     const int kslot = ktime_begin(st);
     if (dwd_waves() == 8)
       hipLaunchKernelGGL(gemm_dwd_group_kernel<8>, dim3(G.wg0[G.n]), dim3(512), kDwdLds, st, G);
     else
       hipLaunchKernelGGL(gemm_dwd_group_kernel<4>, dim3(G.wg0[G.n]), dim3(256), kDwdLds, st, G);
     ktime_end(kslot, KT_GEMM_DW, g_grp_flops, st);
-    RC_CHECK(check_launch("gemm_dwd_group_kernel"));
+    RC_CHECK(check_launch(dw_group_name(G, false)));
   }
   // the reducer sums the partials of the entries launched with the BPTT and
   // of these, in one launch
@@ -1959,12 +2260,14 @@ int dw_group_flush(hipStream_t st) {
     R = g_pre;
     R.x = G.x;
     if (R.n + G.n > kDwGroupMax) return set_error(SMI_E_ARG, "dw group: too many entries");
+    for (int i = 0; i < G.ng; ++i) R.g[R.ng + i] = G.g[i];
     for (int i = 0; i < G.n; ++i) {
       const int j = R.n + i;
-      R.g[j] = G.g[i];
-      R.S[j] = G.S[i];
-      R.rb0[j + 1] = R.rb0[j] + (int)(((int64_t)G.g[i].M * G.g[i].N + 64 * red_u() - 1) / (64 * red_u()));
+      R.e[j] = G.e[i];
+      R.e[j].gi += R.ng;
+      R.rb0[j + 1] = R.rb0[j] + (G.rb0[i + 1] - G.rb0[i]);
     }
+    R.ng += G.ng;
     R.n += G.n;
     need += g_pre_need;
   }
@@ -1976,7 +2279,7 @@ int dw_group_flush(hipStream_t st) {
     hipLaunchKernelGGL(gemm_group_reduce_kernel<1>, dim3(R.rb0[R.n] + (R.x.on ? 1 : 0)), dim3(kWG), 0,
                        st, R);
   ktime_end(rslot, KT_GEMM_REDUCE, (double)need, st);
-  return check_launch("gemm_group_reduce_kernel");
+  return check_launch(dw_group_name(R, true));
 }
 
 // SMI_BWD_DW=0: the BPTT and the heads' weight gradients as separate launches
@@ -1989,7 +2292,7 @@ static bool use_bwd_dw() {
 int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, const float* w_hh,
                        int S, int B, int H, float* dgates, hipStream_t st, const int* skip) {
   const int br = lstm_bwd_q_form(B, H, w_hh);
-  if (!use_bwd_dw() || !g_grp_on || g_pre_on || g_grp.n == 0 || br == 0 || S <= 0 || B <= 0)
+  if (!use_bwd_dw() || !g_grp_on || g_pre_on || g_grp.ng == 0 || br == 0 || S <= 0 || B <= 0)
     return SMI_E_NOFIT;
   int cus = 0, dev = 0;
   (void)hipGetDevice(&dev);
@@ -2000,7 +2303,8 @@ int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, c
   // balanced for the CUs the recurrence leaves idle (a fixed one-round target
   // of cus - B workgroups with equal slabs: 50.6 vs 30.9 us per launch at 128
   // segments — slab rounding pushed the count past one round)
-  RC_CHECK(dw_prepare(Ga, 8, cus - B, 0, need));
+  // (entries: one stays free for every GEMM the group may still queue)
+  RC_CHECK(dw_prepare(Ga, 8, cus - B, 0, need, kDwGroupMax - (kDwGemmMax - Ga.ng)));
   // one workgroup per CU (the LDS request): the recurrence's workgroups keep
   // their CUs to themselves, the weight gradients take the others
   static const bool excl = [] { const char* e = getenv("SMI_BWD_DW_EXCL"); return !(e && e[0] == '0'); }();
@@ -2032,7 +2336,7 @@ int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, c
   g_pre_on = true;
   g_pre_need = need;
   workspace_reserve(need);     // no launch before the flush may reuse these partials
-  g_grp.n = 0;                                      // the group queues the rest
+  g_grp.ng = g_grp.n = 0;                           // the group queues the rest
   g_grp_flops = 0.0;                                // (its launch times the rest only)
   return SMI_OK;
 }
