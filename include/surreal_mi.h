@@ -753,6 +753,22 @@ int smi_mt_randint(uint32_t* dev_state625, int64_t n, int64_t batch,
 int smi_gather_rows(const float* table, int64_t cols, const int64_t* idx,
                     int64_t batch, float* out, void* stream);
 
+/* Pixel replay gather, one launch: for every i < batch
+ *   pix_out[i]      = frames[idx[i]]        (frame_bytes uint8 each)
+ *   pix_next_out[i] = frames_next[idx[i]]
+ *   rows_out[i]     = table[idx[i]]         (cols floats; skipped when cols == 0,
+ *                                            table and rows_out may then be NULL)
+ * Source offsets are 64-bit (rings beyond 4 GiB).  Frames move as 16-byte
+ * vectors when frame_bytes % 16 == 0 and the four pixel pointers are 16-byte
+ * aligned, as bytes otherwise (any size, any alignment).  Indices are trusted
+ * (0 <= idx[i] < ring slots), as in smi_gather_rows.  batch == 0 returns SMI_OK
+ * without a launch; NULL pixel pointers or idx, frame_bytes outside [1, 2^31),
+ * batch < 0, cols < 0, or cols > 0 with a NULL table / rows_out are SMI_E_ARG. */
+int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
+                      const uint8_t* frames_next, int64_t frame_bytes, const int64_t* idx,
+                      int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -185,6 +185,7 @@ _SIGS = {
     'smi_mt_randint_host': (c_int, [P, c_i64, c_i64, P]),
     'smi_mt_randint': (c_int, [P, c_i64, c_i64, P, P]),
     'smi_gather_rows': (c_int, [P, c_i64, P, c_i64, P, P]),
+    'smi_replay_gather': (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, P]),
     'smi_lstm_param_count': (c_i64, [c_int, c_int]),
     'smi_kernel_timing': (c_int, [c_int]),
     'smi_kernel_timing_report': (c_int, [c_int, P]),

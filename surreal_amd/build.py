@@ -70,7 +70,9 @@ VARIANTS = {None: [], 'prof': ['-DSMI_PROF'], 'noinl': ['-DSMI_DENSE_NOINLINE'],
             'fault': ['-DSMI_FAULT_INJECTION'],
             # round 6 A/B: the BPTT's recurrent dot product in the round-5 two
             # FMA chains (product: four; 128 segments 2.919 -> 2.908 ms)
-            'ch2': ['-DSMI_BPTT_CH4=0']}
+            'ch2': ['-DSMI_BPTT_CH4=0'],
+            # replay_gather A/B: nontemporal loads / stores / both (product: plain)
+            'rgnt1': ['-DSMI_RG_NT=1'], 'rgnt2': ['-DSMI_RG_NT=2'], 'rgnt3': ['-DSMI_RG_NT=3']}
 
 
 def lib_path(variant=None):

@@ -152,6 +152,8 @@ void mt_seed_host(uint64_t, uint32_t*);
 int mt_randint_host(uint32_t*, int64_t, int64_t, int64_t*);
 int launch_mt_randint(uint32_t*, int64_t, int64_t, int64_t*, hipStream_t);
 int launch_gather_rows(const float*, int64_t, const int64_t*, int64_t, float*, hipStream_t);
+int launch_replay_gather(const float*, int64_t, const uint8_t*, const uint8_t*, int64_t,
+                         const int64_t*, int64_t, float*, uint8_t*, uint8_t*, hipStream_t);
 int launch_zfilter_accumulate(const float*, const float*, int, float, float*, float*, float*,
                               hipStream_t);
 
@@ -627,6 +629,20 @@ int smi_gather_rows(const float* table, int64_t cols, const int64_t* idx, int64_
                     float* out, void* stream) {
   REQUIRE(table && idx && out && cols > 0 && batch >= 0, "gather_rows: bad args");
   return launch_gather_rows(table, cols, idx, batch, out, SMI_STREAM(stream));
+}
+
+int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
+                      const uint8_t* frames_next, int64_t frame_bytes, const int64_t* idx,
+                      int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
+                      void* stream) {
+  REQUIRE(frames && frames_next && pix_out && pix_next_out && idx,
+          "replay_gather: null frames, output or index pointer");
+  REQUIRE(frame_bytes >= 1 && frame_bytes < ((int64_t)1 << 31) && batch >= 0 && cols >= 0,
+          "replay_gather: frame_bytes outside [1, 2^31), batch < 0 or cols < 0");
+  REQUIRE(cols == 0 || (table && rows_out), "replay_gather: cols > 0 needs table and rows_out");
+  if (batch == 0) return SMI_OK;
+  return launch_replay_gather(table, cols, frames, frames_next, frame_bytes, idx, batch, rows_out,
+                              pix_out, pix_next_out, SMI_STREAM(stream));
 }
 
 

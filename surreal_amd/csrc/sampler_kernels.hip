@@ -1,5 +1,6 @@
 // sampler_kernels.hip — CPython-exact uniform replay index sampling and the
-// replay row gather (UniformReplay.sample, surreal/replay/uniform_replay.py:43-47).
+// replay row gather (UniformReplay.sample, surreal/replay/uniform_replay.py:43-47),
+// and the pixel replay's fused frame + row gather (UniformReplay.sample_batch).
 //
 // The reference draws [random.randint(0, n-1) for _ in range(B)] from the
 // Python stdlib generator: MT19937 (Matsumoto & Nishimura 1998) seeded by
@@ -241,6 +242,125 @@ int launch_gather_rows(const float* table, int64_t cols, const int64_t* idx, int
   if (g < 1) g = 1;
   hipLaunchKernelGGL(gather_rows_kernel, dim3((int)g), dim3(kWG), 0, s, table, cols, idx, batch, out);
   return check_launch("gather_rows_kernel");
+}
+
+// ------------------------------------------------- replay gather (frames)
+// Pixel replay sample: pix_out[i] = frames[idx[i]], pix_next_out[i] =
+// frames_next[idx[i]] (uint8 frames of frame_bytes each) and, when a table is
+// given, rows_out[i] = table[idx[i]], in one launch.
+//
+// A work item is (sample, side, chunk): one workgroup moves one 16 KiB chunk
+// (kRgU 16-byte vectors per lane) of one frame, so idx[i] and both base
+// addresses are workgroup-uniform (scalar loads and arithmetic), every lane
+// issues its kRgU loads before its first store (32 waves per CU x 4 KiB = 128
+// KiB in flight per CU), and source offsets are 64-bit (the reference ring,
+// 333,333 x 63,504 B, is 21 GB per side).  Items are dealt to a capped 1-D
+// grid.  The float side rows follow in the same launch through gather_body.
+//
+// SMI_RG_NT (developer A/B, build.py variants rgnt1-3): nontemporal loads (bit
+// 0) and / or stores (bit 1).  The product is plain loads and stores (B = 512
+// of 9 x 84 x 84, one MI355X: plain 25.8-26.0 us, loads 26.3, stores 28.5, both
+// 27.7): the frames are read by the conv forward right after
+// this launch.
+#ifndef SMI_RG_NT
+#define SMI_RG_NT 0
+#endif
+constexpr int kRgU = 4;
+constexpr int kRgChunk = kWG * kRgU;   // 16-byte vectors (VEC) or bytes x 16 per work item
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ void gather_rows_side(const float* __restrict__ table, int64_t cols,
+                                                 const int64_t* __restrict__ idx, int64_t batch,
+                                                 float* __restrict__ out) {
+  // element width and index width chosen as gather_rows_kernel chooses them
+  const uintptr_t al = reinterpret_cast<uintptr_t>(table) | reinterpret_cast<uintptr_t>(out);
+  const bool v4 = (cols & 3) == 0 && (al & 15) == 0;
+  const bool v2 = !v4 && (cols & 1) == 0 && (al & 7) == 0;
+  const int64_t c = v4 ? cols >> 2 : v2 ? cols >> 1 : cols;
+  const int64_t total = batch * c;
+  if (total < ((int64_t)1 << 31)) {
+    if (v4) gather_body<float4, uint32_t>(reinterpret_cast<const float4*>(table), (uint32_t)c, idx,
+                                          (uint32_t)total, reinterpret_cast<float4*>(out));
+    else if (v2) gather_body<float2, uint32_t>(reinterpret_cast<const float2*>(table), (uint32_t)c,
+                                               idx, (uint32_t)total, reinterpret_cast<float2*>(out));
+    else gather_body<float, uint32_t>(table, (uint32_t)c, idx, (uint32_t)total, out);
+  } else {
+    if (v4) gather_body<float4, int64_t>(reinterpret_cast<const float4*>(table), c, idx, total,
+                                         reinterpret_cast<float4*>(out));
+    else if (v2) gather_body<float2, int64_t>(reinterpret_cast<const float2*>(table), c, idx, total,
+                                              reinterpret_cast<float2*>(out));
+    else gather_body<float, int64_t>(table, c, idx, total, out);
+  }
+}
+
+// VEC: frame_bytes % 16 == 0 and all four pixel pointers 16-byte aligned;
+// otherwise bytes (correct for any size and alignment; no learner-valid frame
+// takes it, cnn_check demands C*H*W % 16 == 0).  cpf = chunks per frame.
+template <bool VEC>
+__global__ void __launch_bounds__(kWG)
+replay_gather_kernel(const float* __restrict__ table, int64_t cols,
+                     const uint8_t* __restrict__ frames, const uint8_t* __restrict__ frames_next,
+                     int64_t frame_bytes, const int64_t* __restrict__ idx, int64_t batch,
+                     float* __restrict__ rows_out, uint8_t* __restrict__ pix_out,
+                     uint8_t* __restrict__ pix_next_out, int64_t cpf) {
+  const int64_t items = batch * 2 * cpf;
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int64_t s = it / cpf, chunk = it - s * cpf;
+    const int64_t i = s >> 1;
+    const bool nxt = (s & 1) != 0;
+    const uint8_t* src = (nxt ? frames_next : frames) + idx[i] * frame_bytes;
+    uint8_t* dst = (nxt ? pix_next_out : pix_out) + i * frame_bytes;
+    if constexpr (VEC) {
+      const u32x4* s4 = reinterpret_cast<const u32x4*>(src);
+      u32x4* d4 = reinterpret_cast<u32x4*>(dst);
+      // frame_bytes < 2^31 (checked by the entry point): in-frame offsets are int.
+      // Tail lanes load the frame's last vector (in bounds, unconditional, so
+      // the kRgU loads issue back to back) and skip the store.
+      const int nvec = (int)(frame_bytes >> 4);
+      const int v0 = (int)chunk * kRgChunk + (int)threadIdx.x;
+      u32x4 v[kRgU];
+#pragma unroll
+      for (int u = 0; u < kRgU; ++u) {
+        const int e = min(v0 + u * kWG, nvec - 1);
+        if constexpr ((SMI_RG_NT & 1) != 0) v[u] = __builtin_nontemporal_load(s4 + e);
+        else v[u] = s4[e];
+      }
+#pragma unroll
+      for (int u = 0; u < kRgU; ++u) {
+        const int e = v0 + u * kWG;
+        if (e < nvec) {
+          if constexpr ((SMI_RG_NT & 2) != 0) __builtin_nontemporal_store(v[u], d4 + e);
+          else d4[e] = v[u];
+        }
+      }
+    } else {
+      const int64_t b0 = chunk * kRgChunk * 16;
+      const int64_t b1 = b0 + kRgChunk * 16 < frame_bytes ? b0 + kRgChunk * 16 : frame_bytes;
+      for (int64_t b = b0 + threadIdx.x; b < b1; b += kWG) dst[b] = src[b];
+    }
+  }
+  if (cols > 0) gather_rows_side(table, cols, idx, batch, rows_out);
+}
+
+int launch_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
+                         const uint8_t* frames_next, int64_t frame_bytes, const int64_t* idx,
+                         int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
+                         hipStream_t s) {
+  if (batch <= 0) return SMI_OK;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(frames) | reinterpret_cast<uintptr_t>(frames_next) |
+                       reinterpret_cast<uintptr_t>(pix_out) | reinterpret_cast<uintptr_t>(pix_next_out);
+  const bool vec = (frame_bytes & 15) == 0 && (al & 15) == 0;
+  const int64_t cpf = (frame_bytes + kRgChunk * 16 - 1) / (kRgChunk * 16);
+  int64_t g = batch * 2 * cpf;
+  if (g > 4096) g = 4096;
+  if (vec)
+    hipLaunchKernelGGL(replay_gather_kernel<true>, dim3((int)g), dim3(kWG), 0, s, table, cols, frames,
+                       frames_next, frame_bytes, idx, batch, rows_out, pix_out, pix_next_out, cpf);
+  else
+    hipLaunchKernelGGL(replay_gather_kernel<false>, dim3((int)g), dim3(kWG), 0, s, table, cols,
+                       frames, frames_next, frame_bytes, idx, batch, rows_out, pix_out,
+                       pix_next_out, cpf);
+  return check_launch("replay_gather_kernel");
 }
 
 }  // namespace smi

@@ -5,7 +5,10 @@ a device-resident ring of fixed-width rows (obs | action | reward | obs_next |
 done) in HBM and the index draw done by the CPython-exact MT19937 HIP kernel
 (smi_mt_randint), so `sample()` returns exactly the rows the reference's
 `[random.randint(0, len-1) for _ in range(B)]` would pick after
-`random.seed(seed)`.  FIFOReplay mirrors fifo_replay.py:6-49 (host deque; the
+`random.seed(seed)`.  With camera observations (a 'pixel' entry in the obs
+spec) the ring also holds the uint8 frames of both observations on the device
+and `sample_batch()` gathers rows and frames in one launch (smi_replay_gather)
+into the batch form DDPGLearner.learn() takes.  FIFOReplay mirrors fifo_replay.py:6-49 (host deque; the
 PPO path consumes batches in insertion order).
 """
 import ctypes
@@ -42,11 +45,66 @@ class CPythonRandom(object):
         return out
 
 
+def _camera_u8(cam, shape):
+    """camera0 of one observation -> uint8 (C, H, W); a list of per-frame arrays
+    is concatenated along channels (frame_stack_concatenate_on_env: False), and
+    a non-uint8 array must hold integral values in [0, 255] (the rule of
+    DDPGAgentBatch._camera)"""
+    if isinstance(cam, (list, tuple)):
+        cam = np.concatenate([np.asarray(f) for f in cam], axis=0)
+    a = np.asarray(cam)
+    if a.dtype != np.uint8:
+        if not (np.all(a == np.round(a)) and a.min() >= 0 and a.max() <= 255):
+            raise TypeError('camera observations must hold uint8 pixel values')
+        a = a.astype(np.uint8)
+    if tuple(a.shape) != tuple(shape):
+        raise ValueError(f'camera0 has shape {tuple(a.shape)}, the obs spec says {tuple(shape)}')
+    return a
+
+
+def _low_dim(obs):
+    return np.concatenate([np.ravel(v) for v in obs['low_dim'].values()])
+
+
+def pack_pixel_exps(exps, obs_dim, act_dim, camera_shape):
+    """SSAR experience dicts {'obs': [o0, o1], 'action', 'reward', 'done'} with
+    camera observations -> (rows float32 [n, W], pix uint8 [n, C, H, W],
+    pix_next uint8 [n, C, H, W]) on the host; W = 2 * obs_dim + act_dim + 2 and
+    the row layout is UniformReplay's (obs_dim 0: [action | reward | done])."""
+    D, A = int(obs_dim), int(act_dim)
+    shape = tuple(int(c) for c in camera_shape)
+    n = len(exps)
+    rows = np.zeros((n, 2 * D + A + 2), dtype=np.float32)
+    pix = np.zeros((n,) + shape, dtype=np.uint8)
+    pix_next = np.zeros((n,) + shape, dtype=np.uint8)
+    for i, e in enumerate(exps):
+        o0, o1 = e['obs']
+        if D:
+            rows[i, :D] = _low_dim(o0)
+            rows[i, D + A + 1:2 * D + A + 1] = _low_dim(o1)
+        rows[i, D:D + A] = e['action']
+        rows[i, D + A] = e['reward']
+        rows[i, 2 * D + A + 1] = float(e['done'])
+        pix[i] = _camera_u8(o0['pixel']['camera0'], shape)
+        pix_next[i] = _camera_u8(o1['pixel']['camera0'], shape)
+    return rows, pix, pix_next
+
+
 class UniformReplay(object):
     """Ring buffer with CPython-exact uniform sampling (uniform_replay.py:36-47).
 
     Rows are fixed-width float32 records laid out [obs(D) | action(A) |
-    reward(1) | obs_next(D) | done(1)] in one (memory_size, W) device tensor."""
+    reward(1) | obs_next(D) | done(1)] in one (memory_size, W) device tensor.
+
+    Pixel mode (a 'pixel' entry in env_config['obs_spec']; only camera0 is
+    read, as DDPGModel does): two more device rings, `frames` and
+    `frames_next`, uint8 (memory_size, C, H, W), hold the camera observation
+    before and after each transition; D is the low-dim width and may be 0
+    (W = A + 2).  The three rings always advance together.  The frame rings
+    take 2 * memory_size * C*H*W bytes: 42 GB at the reference defaults
+    (memory_size 333,333, 9 x 84 x 84).  Every transition stores both of its
+    frames; sharing a frame between consecutive transitions (the reference
+    sender's hash dedup) is out of scope."""
 
     def __init__(self, learner_config, env_config, session_config=None, index=0, seed=0,
                  device=None):
@@ -54,26 +112,43 @@ class UniformReplay(object):
         self.learner_config = learner_config
         self.memory_size = int(learner_config['replay']['memory_size'])
         self.sampling_start_size = int(learner_config['replay']['sampling_start_size'])
-        self.obs_dim = int(sum(v[0] for v in env_config['obs_spec']['low_dim'].values()))
+        spec = env_config['obs_spec']
+        self.is_pixel = 'pixel' in spec
+        if self.is_pixel:
+            self.camera_shape = tuple(int(c) for c in spec['pixel']['camera0'])
+            self.obs_dim = int(sum(v[0] for v in spec['low_dim'].values())) if 'low_dim' in spec else 0
+        else:
+            self.obs_dim = int(sum(v[0] for v in spec['low_dim'].values()))
         self.act_dim = int(env_config['action_spec']['dim'][0])
         self.width = 2 * self.obs_dim + self.act_dim + 2
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.table = torch.zeros(self.memory_size, self.width, dtype=torch.float32,
                                  device=self.device)
+        if self.is_pixel:
+            self.frame_bytes = int(np.prod(self.camera_shape))
+            self.frames = torch.zeros((self.memory_size,) + self.camera_shape, dtype=torch.uint8,
+                                      device=self.device)
+            self.frames_next = torch.zeros_like(self.frames)
         self._len = 0
         self._next_idx = 0
         self.rng = CPythonRandom(seed, self.device)
         self._idx = None
+        self._out = None
 
     def __len__(self):
         return self._len
 
     def insert(self, exp_dict):
         """uniform_replay.py:36-41 for one SSAR experience dict."""
+        if self.is_pixel:
+            self.insert_rows(*self.pack([exp_dict]))
+            return
         row = self.pack([exp_dict])
         self.insert_rows(row)
 
     def pack(self, exps):
+        if self.is_pixel:
+            return pack_pixel_exps(exps, self.obs_dim, self.act_dim, self.camera_shape)
         D, A = self.obs_dim, self.act_dim
         out = np.zeros((len(exps), self.width), dtype=np.float32)
         for i, e in enumerate(exps):
@@ -86,15 +161,32 @@ class UniformReplay(object):
             out[i, 2 * D + A + 1] = float(e['done'])
         return out
 
-    def insert_rows(self, rows):
-        """Bulk ring insert of packed rows (same slot sequence as repeated insert)."""
+    def insert_rows(self, rows, pix=None, pix_next=None):
+        """Bulk ring insert of packed rows (same slot sequence as repeated insert);
+        pixel mode: with their uint8 (n, C, H, W) frames."""
         rows = torch.as_tensor(rows, dtype=torch.float32)
         n = rows.shape[0]
+        if self.is_pixel:
+            if pix is None or pix_next is None:
+                raise ValueError('a pixel replay inserts rows together with pix and pix_next')
+            pix, pix_next = torch.as_tensor(pix), torch.as_tensor(pix_next)
+            for name, t in (('pix', pix), ('pix_next', pix_next)):
+                if t.dtype != torch.uint8 or tuple(t.shape) != (n,) + self.camera_shape:
+                    raise ValueError(f'{name} must be uint8 {(n,) + self.camera_shape}, got '
+                                     f'{t.dtype} {tuple(t.shape)}')
+            if tuple(rows.shape) != (n, self.width):
+                raise ValueError(f'rows must be ({n}, {self.width}), got {tuple(rows.shape)}')
+        elif pix is not None or pix_next is not None:
+            raise ValueError('this replay has no pixel observations (no "pixel" in the obs spec)')
         # more rows than slots: only the last memory_size survive a sequence of
         # single inserts; scatter just those (no duplicate slot indices)
         skip = max(0, n - self.memory_size)
         slots = (self._next_idx + np.arange(skip, n)) % self.memory_size
-        self.table[torch.as_tensor(slots, device=self.device)] = rows[skip:].to(self.device)
+        slots = torch.as_tensor(slots, device=self.device)
+        self.table[slots] = rows[skip:].to(self.device)
+        if self.is_pixel:
+            self.frames[slots] = pix[skip:].to(self.device)
+            self.frames_next[slots] = pix_next[skip:].to(self.device)
         self._len = min(self.memory_size, self._len + n)
         self._next_idx = int((self._next_idx + n) % self.memory_size)
 
@@ -116,6 +208,9 @@ class UniformReplay(object):
         (uniform_replay.py:43-47) -- and gather only their own slice of
         batch_size / world rows: the sampling stays bit-exact and the shards
         concatenate to the single learner's batch."""
+        if self.is_pixel:
+            raise ValueError('a pixel replay samples rows together with their frames: '
+                             'use sample_batch()')
         if world < 1 or not 0 <= rank < world or batch_size % world:
             raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
         idx = self.sample_indices(batch_size)
@@ -128,6 +223,42 @@ class UniformReplay(object):
         L.call('smi_gather_rows', L.ptr(self.table), self.width, L.ptr(mine), n, L.ptr(out),
                L.stream(self.device))
         return mine, out
+
+    def sample_batch(self, batch_size, rank=0, world=1):
+        """Returns (indices, batch): the draw of sample() (same CPython-exact
+        stream, same rank slicing) gathered into the batch DDPGLearner.learn()
+        takes.  Low-dim: split(rows), one smi_gather_rows.  Pixel: one
+        smi_replay_gather moves this rank's rows and both frames of each;
+        batch = {'obs': {'pixel': {'camera0': u8 [n, C, H, W]}, 'low_dim':
+        {'flat_inputs': [n, D]}}, 'obs_next': likewise, 'actions', 'rewards',
+        'dones'} ('low_dim' omitted when D == 0).  The output buffers are
+        allocated once per n and overwritten by the next call."""
+        if world < 1 or not 0 <= rank < world or batch_size % world:
+            raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
+        n = batch_size // world
+        if self._out is None or self._out[0].shape[0] != n:
+            rows = torch.empty(n, self.width, dtype=torch.float32, device=self.device)
+            self._out = (rows,)
+            if self.is_pixel:
+                self._out = (rows,
+                             torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device),
+                             torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device))
+        if not self.is_pixel:
+            mine, rows = self.sample(batch_size, out=self._out[0], rank=rank, world=world)
+            return mine, self.split(rows)
+        rows, pix, pix_next = self._out
+        idx = self.sample_indices(batch_size)
+        mine = idx[rank * n:(rank + 1) * n]
+        L.call('smi_replay_gather', L.ptr(self.table), self.width, L.ptr(self.frames),
+               L.ptr(self.frames_next), self.frame_bytes, L.ptr(mine), n, L.ptr(rows), L.ptr(pix),
+               L.ptr(pix_next), L.stream(self.device))
+        flat = self.split(rows)
+        obs, obs_next = {'pixel': {'camera0': pix}}, {'pixel': {'camera0': pix_next}}
+        if self.obs_dim:
+            obs['low_dim'] = {'flat_inputs': flat['obs']}
+            obs_next['low_dim'] = {'flat_inputs': flat['obs_next']}
+        return mine, {'obs': obs, 'obs_next': obs_next, 'actions': flat['actions'],
+                      'rewards': flat['rewards'], 'dones': flat['dones']}
 
     def split(self, rows):
         D, A = self.obs_dim, self.act_dim

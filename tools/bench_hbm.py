@@ -17,6 +17,9 @@ the algorithmic bytes are the §8(d) per-unit figures:
                                     the Infinity Cache
   adam_noclip                       p,g,m,v read 16 B + p,m,v written 12 B per param
   gather_rows (W=42 floats)         8 idx + 2 x 4 W B per gathered row
+  replay_gather (9x84x84 u8, W=42)  8 idx + 2 sides x 2 x 63504 B + 2 x 4 W B per sample (B = 512,
+                                    8,192-slot rings); replay_gather_baseline3 is the same
+                                    gather as two torch.index_select + one smi_gather_rows
   moments                           4 B per element
 
 peak = 8000 GB/s (MI355X HBM3E spec, MI355X_MICROARCH.md).  Prints one JSON line
@@ -38,7 +41,7 @@ from surreal_amd import _lib as L  # noqa: E402
 PEAK = 8000.0
 
 
-def timed(fn, iters, warm=3):
+def timed(fn, iters, warm=3, spread=False):
     for _ in range(warm):
         fn()
     torch.cuda.synchronize()
@@ -51,7 +54,7 @@ def timed(fn, iters, warm=3):
         evs.append((s, e))
     torch.cuda.synchronize()
     ts = sorted(s.elapsed_time(e) for s, e in evs)
-    return ts[len(ts) // 2]
+    return ts if spread else ts[len(ts) // 2]     # spread: every repeat, sorted
 
 
 def report(name, nbytes, ms, **extra):
@@ -155,6 +158,56 @@ def main():
         report('gather_rows', batch * (8 + 8 * W), timed(fn, args.iters), table_rows=n_tab,
                cols=W, batch=batch)
         del tab, idx, out
+
+    if want('replay_gather'):
+        # the pixel DDPG sample: B = 512 transitions of 9 x 84 x 84 frames (both
+        # observations) + the 42-float side row, from 8,192-slot rings (520 MB per
+        # side, beyond the Infinity Cache).  Successive launches draw disjoint
+        # index sets that sweep the whole ring, so no launch finds its frames
+        # cached by an earlier one.  Fused launch against what the tree had
+        # before it: two torch.index_select + one smi_gather_rows.
+        slots, batch, W = 8192, 512, 42
+        fb = 9 * 84 * 84
+        fr = torch.randint(0, 256, (slots, fb), device=dev, generator=g, dtype=torch.uint8)
+        fn_ = torch.randint(0, 256, (slots, fb), device=dev, generator=g, dtype=torch.uint8)
+        tab = torch.randn(slots, W, device=dev, generator=g)
+        sets = torch.randperm(slots, device=dev, generator=g).view(slots // batch, batch)
+        turn = [0]
+
+        def draw():
+            turn[0] = (turn[0] + 1) % sets.shape[0]
+            return sets[turn[0]]
+        rows = torch.empty(batch, W, device=dev)
+        po = torch.empty(batch, fb, dtype=torch.uint8, device=dev)
+        pn = torch.empty(batch, fb, dtype=torch.uint8, device=dev)
+        nbytes = batch * (8 + 2 * 2 * fb + 8 * W)
+
+        def fused():
+            idx = draw()
+            L.call('smi_replay_gather', P(tab), W, P(fr), P(fn_), fb, P(idx), batch, P(rows), P(po),
+                   P(pn), st)
+
+        def three():
+            idx = draw()
+            torch.index_select(fr, 0, idx, out=po)
+            torch.index_select(fn_, 0, idx, out=pn)
+            L.call('smi_gather_rows', P(tab), W, P(idx), batch, P(rows), st)
+
+        # bench.py's calibrated stream (float4 read + write over 2 x 1 GiB), same process
+        n = 1 << 28
+        x, y = torch.rand(n, device=dev, generator=g), torch.empty(n, device=dev)
+        calib = 8.0 * n / (timed(lambda: L.call('smi_calib_stream', P(x), P(y), n, st), 5,
+                                 spread=True)[0] * 1e-3) / 1e9
+        del x, y
+        for name, fn in (('replay_gather', fused), ('replay_gather_baseline3', three)):
+            ts = timed(fn, max(args.iters, 20), spread=True)
+            med = ts[len(ts) // 2]
+            report(name, nbytes, med, slots=slots, batch=batch, frame_bytes=fb, cols=W,
+                   repeats=len(ts), min_ms=round(ts[0], 4), p25_ms=round(ts[len(ts) // 4], 4),
+                   p75_ms=round(ts[(3 * len(ts)) // 4], 4), max_ms=round(ts[-1], 4),
+                   calib_stream_GBs=round(calib, 1),
+                   frac_of_calib_stream=round(nbytes / (med * 1e-3) / 1e9 / calib, 4))
+        del fr, fn_, tab, sets, rows, po, pn
 
     if want('moments'):
         n = 1 << 27
