@@ -47,14 +47,13 @@ const char* smi_last_error(void);
  * ("Dispatch coverage", lists what selects each):
  *   lstm_fwd_q_kernel<KQ,XQ,xm|xv,wW[,a4]>  KQ 16|26|28|32 k per lane, XQ 0|12|16
  *       x columns per lane (0: xproj input), xm / xv matrix-core / VALU x
- *       parts, wW the W_hh load layout 0|1|2, a4 every gate in every lane
+ *       parts, wW the W_hh load layout 0|1|2, a4 (with xm) every gate in every lane
  *   lstm_fwd_r4_kernel<KP,KX[,vf]>          KP 32|64|104|128, KX 0|48|64 fused x
  *       width (0: xproj input), vf the fixed-width row loads
- *   lstm_fwd_kernel<U>  lstm_fwd_reg_kernel<KS>  lstm_fwd_v_kernel<R,KP,KX>
- *   lstm_bwd_q_kernel<BR[,stg]>  lstm_bwd_v_kernel<R,KP>  lstm_bwd_r4_kernel<KW>
- *   lstm_bwd_kernel<U>  lstm_bwd_reg_kernel<KS>
- *   head_fwd_kernel<N1,N2,rt1|rt2[,ps]>     layer-1 / layer-2 width slots, row
- *       tiles per workgroup, ps the statistics epilogue
+ *   lstm_fwd_kernel<4>  lstm_bwd_kernel<4>  (H 129..256)
+ *   lstm_bwd_q_kernel<BR>  lstm_bwd_v_kernel<1,KP>  lstm_bwd_r4_kernel<KW>
+ *   head_fwd_kernel<N1,N2,rt1|rt2>          layer-1 / layer-2 width slots, row
+ *       tiles per workgroup
  *   head_bwd_kernel<NA,NB,rt1|rt2[,pg]>     h1 / dX width slots, pg the policy prologue
  *   gemm_panel_kernel<fwd|dx,C>             C 16-column tiles per column group
  *   gemm_smallk_fwd_kernel<KU>  dx_smallk_kernel<KK[,v4][,a4]>

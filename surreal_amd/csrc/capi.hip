@@ -135,9 +135,7 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
                           const float* W3, const float* b3, int out, int tanh_out, float* HA1,
                           float* HA2, float* Y, int64_t ldy, float* W1T, float* W2T,
                           hipStream_t st, const int* skip, const float* vret = nullptr,
-                          float* vgrad = nullptr, float vscale = 0.f,
-                          const PolRowArgs* ps = nullptr, double* vpart = nullptr);
-bool head_fwd_ps_ok(int h1, int h2, int out);
+                          float* vgrad = nullptr, float vscale = 0.f, double* vpart = nullptr);
 int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W3,
                           const float* W2T, const float* W1T, int h1, int h2, int dx0, int dxn,
                           const float* HA1, const float* HA2, float* dH2, float* dH1, float* dX,

@@ -57,9 +57,6 @@ __host__ __device__ inline int64_t lds_img_bytes(const CnnGeom& g) { return (g.i
 // per-thread 16-byte chunk counts of an 84 x 84 frame's staging (image, A1,
 // dA2), register arrays of the forward's batched image loads and the
 // backward's next-image prefetch (larger frames: a tail loop / PF off)
-#ifndef SMI_CNN_FWD_KB
-#define SMI_CNN_FWD_KB 6
-#endif
 template <int C> struct CnnPf {
   static constexpr int KI = C <= 3 ? 6 : 16;     // uint4 of the uint8 image
   static constexpr int KA = 7;                   // float4 of A1 (16 x P1)
@@ -100,7 +97,7 @@ cnn_fwd_kernel(const float* __restrict__ prm, PixRows pr, int H, int W, int64_t 
       typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
       // (batches of KB chunks: the RGB kernel's 3-waves/SIMD register budget
       // spills weights with more staging registers live)
-      constexpr int KB = SMI_CNN_FWD_KB;
+      constexpr int KB = 6;
       const u32x4* src = reinterpret_cast<const u32x4*>(pix_of(pr, n));
       u32x4* dst = reinterpret_cast<u32x4*>(img);
       const int nv = (int)(g.img >> 4);
@@ -464,12 +461,11 @@ int cnn_backward(const float* prm, const PixRows& pr, int C, int H, int W, int F
                                 dA2, g.flat, st, skip));
   const size_t lds = cnn_bwd_lds(g);
   // next-image prefetch when the frame fits its register arrays (84 x 84 does)
-  static const bool pf_on = [] { const char* e = getenv("SMI_CNN_PF"); return !(e && e[0] == '0'); }();
   auto fits = [&](auto pf) {
     using P = decltype(pf);
     return (g.img >> 4) <= (int64_t)P::KI * kWG && 4 * g.P1 <= P::KA * kWG && (g.flat >> 2) <= P::KD * kWG;
   };
-  const bool pf = pf_on && (C == 9 ? fits(CnnPf<9>{}) : fits(CnnPf<3>{}));
+  const bool pf = (C == 9 ? fits(CnnPf<9>{}) : fits(CnnPf<3>{}));
   auto k = C == 9 ? (pf ? cnn_bwd_kernel<9, true> : cnn_bwd_kernel<9, false>)
                   : (pf ? cnn_bwd_kernel<3, true> : cnn_bwd_kernel<3, false>);
   allow_lds(k, lds);

@@ -59,10 +59,6 @@ struct HeadFwdArgs {
   // vscale * (Y[r] - vret[r]), the MSE gradient the learner's value_rows pass
   // would compute from Y (same fp32 ops), written by the forward itself
   const float* vret; float* vgrad; float vscale;
-  // policy statistics epilogue (head_fwd_kernel<..., PS>, adapt mode, out ==
-  // 8): the rows' sums of policy_rows_stats_kernel's pass from the means the
-  // forward just formed, one PS_N partial per workgroup at ps.part
-  PolRowArgs ps;
   // with vgrad: the value statistics of the last value epoch (ppo.py:324-331,
   // value_rows_kernel's sums {sum (V-R)^2, sum (R-V), sum (R-V)^2, sum R,
   // sum R^2}), five fp64 per workgroup at vpart[blockIdx.x * 5 ..] (nullable)
@@ -137,18 +133,12 @@ __device__ __forceinline__ void hc_sync() {
 // first two chunks, which need nothing from the layer's input: a layer's init
 // runs before the previous layer's epilogue and barrier, so those reads are
 // in flight meanwhile; hc_run issues the rest of the ring.
-#ifndef SMI_HC_DEPTH
-#define SMI_HC_DEPTH 2
-#endif
 // chunks in flight per wave; measured (C3 bench, one MI355X, interleaved
 // trials): 2 -> 8.45 ms, 3 -> 8.59, 4 -> 8.67 per learn: the deeper rings cost
 // occupancy (124 -> 184 VGPRs) and gain nothing
-constexpr int HC_D = SMI_HC_DEPTH;
+constexpr int HC_D = 2;
 // 16-byte X loads per thread in flight while staging the forward's input rows
-#ifndef SMI_HC_XB
-#define SMI_HC_XB 4
-#endif
-constexpr int HC_XB = SMI_HC_XB;
+constexpr int HC_XB = 4;
 static_assert(HC_D >= 2, "ring of at least two chunks");
 template <int NT>
 struct HcStream {
@@ -396,7 +386,7 @@ __device__ __forceinline__ void hc_transpose_tile(const float* __restrict__ W, i
 // LDS floats of the forward's last-layer partials / transpose tile
 __host__ __device__ constexpr int hc_sr(int RT) { return RT * 1024 > HC_SR ? RT * 1024 : HC_SR; }
 
-template <int NT1, int NT2, int RT, bool PS>
+template <int NT1, int NT2, int RT>
 __global__ void __launch_bounds__(kWG)
 head_fwd_kernel(HeadFwdArgs a) {
   if (a.skip && a.skip[0] != 0) return;
@@ -477,24 +467,6 @@ head_fwd_kernel(HeadFwdArgs a) {
     hc_sync();
     HEAD_TICK(0, 5);                              // epilogue 2 + barrier
     hc_copy_out<RT>(s2, a.ld2, a.h2, a.HA2, r0, a.rows);
-    // PS: thread t < R's row inputs of the statistics pass, in flight through
-    // layer 3
-    constexpr int R_ = HC_R * RT, PA = 8;
-    __shared__ float smu[PS ? R_ * PA : 1];
-    float prm[PS ? PA : 1], pac[PS ? PA : 1], pbl = 1.f, prbd = 0.f, padv = 0.f, pret = 0.f;
-    const int64_t prow = r0 + threadIdx.x;
-    const bool pown = PS && (int)threadIdx.x < R_ && prow < a.rows;
-    if constexpr (PS) {
-      if (pown) {
-        const int64_t N = (int64_t)a.ps.E * a.ps.B;
-        ld_row<PA>(prm, a.ps.refmu + prow * PA, PA);
-        ld_fields<PA>(pac, a.ps.rowin, N, prow, 0, PA);
-        padv = a.ps.rowin[rin_idx(row_w(PA), prow, rin_adv(PA))];
-        pbl = a.ps.rowin[rin_idx(row_w(PA), prow, rin_bl(PA))];
-        prbd = a.ps.rowin[rin_idx(row_w(PA), prow, rin_rbd(PA))];
-        pret = a.ps.ret_tm[prow];
-      }
-    }
     {   // layer 3 (out <= 16): the waves split the k chunks, fixed-order sum
       const float bn = a.b3[li < a.out ? li : a.out - 1];
       // the value targets of the lane's rows (value-gradient epilogue), in
@@ -544,7 +516,6 @@ head_fwd_kernel(HeadFwdArgs a) {
                 vs[3] += (double)rv; vs[4] += (double)rv * (double)rv;
               }
             }
-            if constexpr (PS) smu[r * PA + li] = y;
           }
       }
       if (a.vpart && wave == 0) {        // lanes li >= out hold zeros
@@ -552,35 +523,6 @@ head_fwd_kernel(HeadFwdArgs a) {
         for (int k = 0; k < 5; ++k) {
           const double t = wave_sum_d(vs[k]);
           if (lane == 0) a.vpart[(int64_t)blockIdx.x * 5 + k] = t;
-        }
-      }
-    }
-    if constexpr (PS) {
-      // the statistics of the workgroup's rows (pol_rows.hpp: the stats
-      // kernel's adapt-mode ops), summed over the rows on wave 0 in a fixed
-      // butterfly order, one PS_N partial per workgroup
-      hc_sync();
-      double acc[PS_N];
-#pragma unroll
-      for (int k = 0; k < PS_N; ++k) acc[k] = 0.0;
-      if (pown) {
-        float sg[PA], lsg[PA], rsg[PA], mu[PA];
-#pragma unroll
-        for (int j = 0; j < PA; ++j) {
-          sg[j] = expf(a.ps.lv[j]);                // builders.py:127 std = exp(log_var)
-          lsg[j] = logf(sg[j]);
-          rsg[j] = expf(a.ps.ref_lv[j]);
-          mu[j] = smu[threadIdx.x * PA + j];
-        }
-        const PolStatsCols<PA> cols(sg, lsg, rsg, PA);
-        const AdvNorm nadv(a.ps);
-        pol_stats_row_adapt<PA>(a.ps, cols, nadv, mu, prm, pac, pbl, prbd, padv, pret, acc);
-      }
-      if (wave == 0) {
-#pragma unroll
-        for (int k = 0; k < PS_N; ++k) {
-          const double v = wave_sum_d(acc[k]);
-          if (lane == 0) a.ps.part[(int64_t)blockIdx.x * PS_N + k] = v;
         }
       }
     }
@@ -792,15 +734,6 @@ extern "C" int smi_head_phase_ticks(unsigned long long* out /* [2][10] */) {
 #endif
 
 // ------------------------------------------------------------------ host side
-static int use_head_fused() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SMI_HEAD_FUSED");
-    u = (e && e[0] == '0') ? 0 : 1;
-  }
-  return u;
-}
-
 static int hc_nt(int n) {                        // tiles per wave, rounded to an instantiation
   const int t = (((n + 15) >> 4) + 3) >> 2;
   return t <= 2 ? 2 : t <= 4 ? t : t <= 5 ? 5 : 8;     // 2, 3, 4, 5, 8
@@ -812,24 +745,14 @@ static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) =
 // otherwise); the backward additionally needs dxn <= 320 (its dX tiles)
 bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
                    const float* W1, const float* W2, const float* W3) {
-  return use_head_fused() && in >= 4 && in <= 320 && in % 4 == 0 && ldx % 4 == 0 &&
+  return in >= 4 && in <= 320 && in % 4 == 0 && ldx % 4 == 0 &&
          h1 >= 4 && h1 <= HC_MAXK && h1 % 4 == 0 && h2 >= 4 && h2 <= HC_MAXK && h2 % 4 == 0 &&
          out >= 1 && out <= 16 && al16(X) && al16(W1) && al16(W2) && al16(W3);
 }
 
 // row tiles per workgroup: 2 (32 rows: the weight chunks feed twice the MFMAs)
 // once the batch leaves at least ~2 workgroups per CU of them, else 1
-// (SMI_HEAD_RT = 1 | 2 forces one: A/B knob)
-static int hc_rt(int64_t rows) {
-  static int force = -1;
-  if (force < 0) {
-    const char* e = getenv("SMI_HEAD_RT");
-    force = e ? atoi(e) : 0;
-    if (force != 1 && force != 2) force = 0;
-  }
-  if (force) return force;
-  return rows >= 16384 ? 2 : 1;
-}
+static int hc_rt(int64_t rows) { return rows >= 16384 ? 2 : 1; }
 
 // workgroups of a fused head launch over rows (the policy prologue writes one
 // log_var partial per workgroup)
@@ -838,22 +761,17 @@ int head_bwd_blocks(int64_t rows) {
   return (int)((rows + R - 1) / R);
 }
 
-// the statistics epilogue's instantiation (C3 / C5 widths)
-bool head_fwd_ps_ok(int h1, int h2, int out) { return hc_nt(h1) == 5 && hc_nt(h2) == 4 && out == 8; }
-
 int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, const float* W1,
                           const float* b1, int h1, const float* W2, const float* b2, int h2,
                           const float* W3, const float* b3, int out, int tanh_out, float* HA1,
                           float* HA2, float* Y, int64_t ldy, float* W1T, float* W2T,
                           hipStream_t st, const int* skip, const float* vret, float* vgrad,
-                          float vscale, const PolRowArgs* ps, double* vpart) {
+                          float vscale, double* vpart) {
   if (rows <= 0) return SMI_OK;
   if (vgrad && (out != 1 || !vret)) return set_error(SMI_E_ARG, "head_forward: value epilogue needs out == 1");
   if (vpart && !vgrad) return set_error(SMI_E_ARG, "head_forward: value statistics need the value epilogue");
-  if (ps && !head_fwd_ps_ok(h1, h2, out)) return set_error(SMI_E_ARG, "head_forward: statistics epilogue shape");
   HeadFwdArgs a{X, ldx, in, W1, b1, W2, b2, W3, b3, h1, h2, out, tanh_out, HA1, HA2, Y, ldy,
                 W1T, W2T, rows, skip, hc_ld(in), hc_ld(h1), hc_ld(h2), vret, vgrad, vscale};
-  if (ps) a.ps = *ps;
   a.vpart = vpart;
   const int rt = hc_rt(rows);
   const int R = HC_R * rt;
@@ -862,25 +780,18 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
   const int n1 = hc_nt(h1), n2 = hc_nt(h2);
   const int kslot = ktime_begin(st);
   const char* form = "head_fwd_kernel";          // the instantiation launched (smi_last_launch)
-#define SMI_HFP(A, B, P)                                                                \
+#define SMI_HF(A, B)                                                                    \
   do {                                                                                  \
     if (rt == 2) {                                                                      \
-      allow_lds(head_fwd_kernel<A, B, 2, P>, lds);                                      \
-      hipLaunchKernelGGL((head_fwd_kernel<A, B, 2, P>), grid, dim3(kWG), lds, st, a);   \
-      form = P ? "head_fwd_kernel<" #A "," #B ",rt2,ps>" : "head_fwd_kernel<" #A "," #B ",rt2>"; \
+      allow_lds(head_fwd_kernel<A, B, 2>, lds);                                         \
+      hipLaunchKernelGGL((head_fwd_kernel<A, B, 2>), grid, dim3(kWG), lds, st, a);      \
+      form = "head_fwd_kernel<" #A "," #B ",rt2>";                                      \
     } else {                                                                            \
-      allow_lds(head_fwd_kernel<A, B, 1, P>, lds);                                      \
-      hipLaunchKernelGGL((head_fwd_kernel<A, B, 1, P>), grid, dim3(kWG), lds, st, a);   \
-      form = P ? "head_fwd_kernel<" #A "," #B ",rt1,ps>" : "head_fwd_kernel<" #A "," #B ",rt1>"; \
+      allow_lds(head_fwd_kernel<A, B, 1>, lds);                                         \
+      hipLaunchKernelGGL((head_fwd_kernel<A, B, 1>), grid, dim3(kWG), lds, st, a);      \
+      form = "head_fwd_kernel<" #A "," #B ",rt1>";                                      \
     }                                                                                   \
   } while (0)
-#define SMI_HF(A, B) SMI_HFP(A, B, false)
-  if (ps) {                        // the statistics epilogue: 300 x 200 heads, 8 actions
-    SMI_HFP(5, 4, true);
-    ktime_end(kslot, KT_GEMM_FWD,
-              2.0 * (double)rows * ((double)in * h1 + (double)h1 * h2 + (double)h2 * out), st);
-    return check_launch(form);
-  }
   // layer-1 slots {2, 5, 8} x layer-2 slots {2, 3, 4, 5, 8} (C3 / C5: 300 x 200 -> 5, 4)
   const int m1 = n1 <= 2 ? 2 : n1 <= 5 ? 5 : 8;
 #define SMI_HF2(A)                                        \
@@ -898,7 +809,6 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
   else SMI_HF2(8);
 #undef SMI_HF2
 #undef SMI_HF
-#undef SMI_HFP
   ktime_end(kslot, KT_GEMM_FWD,
             2.0 * (double)rows * ((double)in * h1 + (double)h1 * h2 + (double)h2 * out), st);
   return check_launch(form);

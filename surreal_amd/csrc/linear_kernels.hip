@@ -21,7 +21,6 @@
 // and are zeroed afterwards (no predicated loads: see cdna_hip_programming.md).
 #include <cmath>
 #include <algorithm>
-#include <stdlib.h>
 #include <type_traits>
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
@@ -678,21 +677,8 @@ gemm_dw128_kernel(GemmArgs g) {
 // steps prefetched in registers) and are combined through LDS in a fixed
 // order; slabs go to the split-K partials.  Row-major dY/X of the heads, the
 // LSTM input/recurrent weights and the DDPG nets all take this path.
-#ifndef SMI_DWD_DIAG
-#define SMI_DWD_DIAG 0
-#endif
-// per-workgroup clock trace of the grouped launch (bench_dwgroup only; the
-// `dwtrace` builds), independent of the DIAG mode
-#ifndef SMI_DWD_TRACE
-#define SMI_DWD_TRACE (SMI_DWD_DIAG == 3)
-#endif
-#ifndef SMI_DWD_P
-#define SMI_DWD_P 4
-#endif
-#ifndef SMI_DWD_OCC
-#define SMI_DWD_OCC 2
-#endif
-constexpr int DWD_P = SMI_DWD_P;   // steps in flight per wave
+constexpr int DWD_P = 4;           // steps in flight per wave
+constexpr int DWD_OCC = 2;         // workgroups per CU gemm_dwd_kernel is built for
 
 // Rows past the slab and the synthesised bias column are selected by ADDRESS
 // (a zero row / a {1, 0, 0, 0} vector in device memory), never by masking the
@@ -810,11 +796,6 @@ __device__ __forceinline__ void dwd_load(const GemmArgs& g, int r, int ke, int m
 // branches (the checked loop spends ~40 VALU/SALU ops per step on them).
 // The last DWD_P steps are peeled without loads (no reads past the slab).
 // Same MFMA chains in the same order as the checked loop: bit-identical.
-#ifndef SMI_DWD_FAST
-#define SMI_DWD_FAST 1
-#endif
-__device__ __forceinline__ bool use_dwd_fast() { return SMI_DWD_FAST != 0; }
-
 template <int MT, int NT, int NB, int RS>
 __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nsteps, int m0, int n0,
                                               int bdata, f32x4 (&acc)[MT][NT]) {
@@ -860,12 +841,6 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
   };
   auto step = [&](int p) {
     const float a4[4] = {av[p].x, av[p].y, av[p].z, av[p].w};
-#if SMI_DWD_DIAG == 2
-    // diagnostic (bench_dwgroup A/B only): the operand stream without the MFMAs
-    acc[0][0][0] += (a4[0] + a4[1]) + (a4[2] + a4[3]);
-#pragma unroll
-    for (int h = 0; h < NH; ++h) acc[0][0][1] += (bv[p][h].x + bv[p][h].y) + (bv[p][h].z + bv[p][h].w);
-#else
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
       const float4 q = bv[p][b >> 2];
@@ -873,7 +848,6 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
 #pragma unroll
       for (int a = 0; a < MT; ++a) acc[a][b] = mfma4(a4[a], bb, acc[a][b]);
     }
-#endif
   };
   // the prologue's loads are pinned in step order too: the loop header's
   // vmcnt is the merge of the preheader and the back edge, so one prologue
@@ -907,9 +881,7 @@ __device__ __forceinline__ void dwd_main_fast(const GemmArgs& g, int rw, int nst
 #pragma unroll
     for (int p = 0; p < DWD_P; ++p) {
       step(p);
-      // diagnostic SMI_DWD_DIAG 1 (bench_dwgroup A/B only): the MFMAs without
-      // the operand stream (the first DWD_P steps' operands reused)
-      if constexpr (SMI_DWD_DIAG != 1) load(p);
+      load(p);
       __builtin_amdgcn_sched_barrier(0);
     }
     if constexpr (kRestart) {
@@ -985,7 +957,7 @@ __device__ __forceinline__ void dwd_tile(const GemmArgs& g, const DwEnt& e, cons
   constexpr bool kFast = (VB || NT < 4) && (VA || MT < 4);
   bool fast = false;
   if constexpr (kFast)
-    fast = use_dwd_fast() && nsteps >= DWD_P && nsteps % DWD_P == 0 && kb + nsteps * RS <= ke;
+    fast = nsteps >= DWD_P && nsteps % DWD_P == 0 && kb + nsteps * RS <= ke;
   constexpr int NBH = NT > 4 ? 4 : NT;
   if (NT == 8 && n0 + 64 >= nend) {
     if constexpr (kFast) {
@@ -1081,14 +1053,14 @@ __device__ __forceinline__ void dwd_tile(const GemmArgs& g, const DwEnt& e, cons
     }
 }
 
-template <int MT, int NT, bool VA, bool VB, int WV>
-__global__ void __launch_bounds__(64 * WV, WV == 4 ? SMI_DWD_OCC : 1)
+template <int MT, int NT, bool VA, bool VB>
+__global__ void __launch_bounds__(256, DWD_OCC)
 gemm_dwd_kernel(GemmArgs g) {
   if (g.skip && g.skip[0] != 0) return;
   extern __shared__ float4 dwd_red[];            // 2 x [MT*NT][64] float4
   DwEnt e{};                                     // the whole output as one rectangle
   e.part = g.part; e.M = g.M; e.N = g.N; e.kchunk = g.kchunk;
-  dwd_tile<MT, NT, VA, VB, WV>(g, e, gemm_tile_index(), dwd_red);
+  dwd_tile<MT, NT, VA, VB, 4>(g, e, gemm_tile_index(), dwd_red);
 }
 
 // Grouped weight gradients: every dW GEMM of one backward phase (the head's
@@ -1124,40 +1096,20 @@ static_assert(sizeof(DwGroup) + 128 <= 4096, "DwGroup must fit the kernel-argume
 // operand-stream latency (the launch waits on memory ~60 % of its wave
 // cycles, PMC SQ_WAIT_INST_ANY / SQ_WAVE_CYCLES) than the halved MFMA reuse
 // per loaded byte costs.
-#ifndef SMI_DWG_NT
-#define SMI_DWG_NT 4
-#endif
-#ifndef SMI_DWG_OCC
-#define SMI_DWG_OCC (SMI_DWG_NT == 4 ? 3 : 2)
-#endif
-constexpr int DWG_NT = SMI_DWG_NT;
-
-#if SMI_DWD_TRACE
-// diagnostic (bench_dwgroup only): per-workgroup {start, end, HW_ID, XCC_ID |
-// group << 8} in 100 MHz wall-clock ticks plus {start, end} of the shader
-// clock (clock64: the in-kernel clock is its delta over the wall delta),
-// read back by smi_diag_dw_trace
-constexpr int kDwTraceMax = 8192;
-__device__ unsigned long long g_dw_trace[kDwTraceMax][6];
-extern "C" int smi_diag_dw_trace(void* dst, int n) {
-  if (n > kDwTraceMax) n = kDwTraceMax;
-  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_dw_trace), (size_t)n * 48, 0, hipMemcpyDeviceToHost) == hipSuccess ? n : -1;
-}
-#endif
+constexpr int DWG_NT = 4;
+constexpr int DWG_OCC = 3;
 
 // one workgroup of a grouped launch: orig = its index among the launch's nwg
 // dW workgroups (the XCD-contiguous remap, gemm_tile_index, assumes orig and
-// the hardware's blockIdx agree mod 8); ei / rows report the entry, slab
-// length and tile class for the clock trace
+// the hardware's blockIdx agree mod 8)
 template <int WV>
-__device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nwg, float4* dwd_red,
-                                              int& ei, int& rows) {
+__device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nwg, float4* dwd_red) {
   int w = orig;
   if (nwg > 8) {                                  // XCD-contiguous runs (gemm_tile_index)
     const int x = orig & 7, q = nwg >> 3, r = nwg & 7;
     w = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (orig >> 3);
   }
-  ei = 0;
+  int ei = 0;
   while (ei + 1 < G.n && w >= G.wg0[ei + 1]) ++ei;
   // (copies: the tile bodies below then read these, not G -- with every class
   // reading the kernel argument itself the compiler stops resolving its uses
@@ -1170,7 +1122,6 @@ __device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nw
   ti.nt = local % e.gn;
   ti.mt = (local / e.gn) % e.gm;
   ti.z = local / (e.gn * e.gm);
-  rows = (min(g.K, (ti.z + 1) * e.kchunk) - ti.z * e.kchunk) | (e.cls << 16);
   // the entry's tile class: MT x NT sub-tiles; VA / VB: 16-byte loads of a
   // 4-wide operand (fitted widths 1..3 always load with one instruction)
 #define SMI_DWT(MT_, NT_, VA_, VB_) \
@@ -1182,13 +1133,8 @@ __device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nw
     SMI_DWT(1, DWG_NT, false, true) SMI_DWT(1, DWG_NT, false, false)
     default: break;
   }
-#if SMI_DWG_NT == 4
-#define SMI_DWT_FIT 1
-#else
-#define SMI_DWT_FIT 0
-#endif
   // (the fitted classes run on the 4-wave launch only: dw_fit_level)
-  if constexpr (SMI_DWT_FIT && WV == 4) {
+  if constexpr (WV == 4) {
     switch (e.cls) {
       SMI_DWT(2, DWG_NT, false, true) SMI_DWT(3, DWG_NT, false, true)
       SMI_DWT(2, DWG_NT, false, false) SMI_DWT(3, DWG_NT, false, false)
@@ -1202,29 +1148,10 @@ __device__ __forceinline__ void dwd_group_run(const DwGroup& G, int orig, int nw
 #undef SMI_DWT
 }
 
-template <int WV>
-__global__ void __launch_bounds__(64 * WV, WV == 4 ? SMI_DWG_OCC : 1)
+__global__ void __launch_bounds__(256, DWG_OCC)
 gemm_dwd_group_kernel(DwGroup G) {
   extern __shared__ float4 dwd_red[];
-  int gi = 0, rows = 0;
-#if SMI_DWD_TRACE
-  const unsigned long long t_start = wall_clock64(), c_start = clock64();
-#endif
-  dwd_group_run<WV>(G, blockIdx.x, gridDim.x, dwd_red, gi, rows);
-#if SMI_DWD_TRACE
-  __syncthreads();
-  if (threadIdx.x == 0 && blockIdx.x < kDwTraceMax) {
-    g_dw_trace[blockIdx.x][0] = t_start;
-    g_dw_trace[blockIdx.x][1] = wall_clock64();
-    g_dw_trace[blockIdx.x][2] = __builtin_amdgcn_s_getreg((31 << 11) | 4);
-    g_dw_trace[blockIdx.x][3] = __builtin_amdgcn_s_getreg((31 << 11) | 20) | (gi << 8) |
-                                ((unsigned long long)rows << 16);
-    g_dw_trace[blockIdx.x][4] = c_start;
-    g_dw_trace[blockIdx.x][5] = clock64();
-  }
-#else
-  (void)gi; (void)rows;
-#endif
+  dwd_group_run<4>(G, blockIdx.x, gridDim.x, dwd_red);
 }
 
 // BPTT of the one-segment-per-workgroup VALU form (workgroups < la.B) and
@@ -1232,16 +1159,15 @@ gemm_dwd_group_kernel(DwGroup G) {
 // others) in ONE launch: the heads' gradients need nothing from the BPTT, so
 // they run on the CUs the recurrence leaves idle (la.B segments on one CU
 // each) instead of after it
-template <int BR, bool STG>
+template <int BR>
 __global__ void __launch_bounds__(kVT, 1)
 lstm_bwd_dw_kernel(LstmBwdArgs la, DwGroup G) {
-  extern __shared__ float4 dwd_red[];             // (the BPTT workgroups: their staged step inputs)
+  extern __shared__ float4 dwd_red[];
   if ((int)blockIdx.x < la.B) {
-    lstm_bwd_q_body<BR, SMI_BPTT_CH4 != 0, STG>(la, blockIdx.x, reinterpret_cast<float*>(dwd_red));
+    lstm_bwd_q_body<BR>(la, blockIdx.x);
     return;
   }
-  int gi = 0, rows = 0;
-  dwd_group_run<8>(G, blockIdx.x - la.B, gridDim.x - la.B, dwd_red, gi, rows);
+  dwd_group_run<8>(G, blockIdx.x - la.B, gridDim.x - la.B, dwd_red);
 }
 
 // the partials of every GEMM of a group, each element summed over its slabs in
@@ -1389,7 +1315,7 @@ __device__ __forceinline__ void red_slabs(const float* const (&p)[U], int64_t MN
 // of wave zl sums slabs zl, zl + 4, ... of elements el + 64 u).  Every element
 // gets the additions of gemm_splitk_reduce_kernel in the same order whatever
 // U is; U = 4 dispatches a quarter of the workgroups with 4x the loads in
-// flight per thread (SMI_RED_U, host side)
+// flight per thread (kRedU, host side; U = 1: the epilogue task alone)
 template <int U>
 __global__ void __launch_bounds__(kWG)
 gemm_group_reduce_kernel(DwGroup G) {
@@ -1564,16 +1490,8 @@ gemm_panel_kernel(GemmArgs g) {
 
 float* workspace_f32(int64_t nfloats);
 
-// split-K target workgroup count (SMI_SPLITK_TARGET overrides; tuning knob)
-static int smi_splitk_target() {
-  static int t = 0;
-  if (!t) {
-    const char* e = getenv("SMI_SPLITK_TARGET");
-    t = e ? atoi(e) : 512;
-    if (t < 64) t = 64;
-  }
-  return t;
-}
+// split-K target workgroup count
+constexpr int kSplitkTarget = 512;
 
 template <int EPI>
 static void gemm_dispatch(const GemmArgs& g, dim3 grid, bool ak, bool bk, hipStream_t st) {
@@ -1583,34 +1501,19 @@ static void gemm_dispatch(const GemmArgs& g, dim3 grid, bool ak, bool bk, hipStr
   else hipLaunchKernelGGL((gemm_kernel<EPI, false, false>), grid, dim3(kWG), 0, st, g);
 }
 
-static int use_dwd() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SMI_DWD");
-    u = (e && e[0] == '0') ? 0 : 1;
-  }
-  return u;
-}
+// waves per dW workgroup, one per SIMD (measured: 8 waves, two per SIMD, 5-10 %
+// slower per launch and 6 % slower end to end at C3; the weight gradients that
+// share the BPTT's launch run in its 8-wave workgroups)
+constexpr int kDwdWaves = 4;
 
-template <int MT, int NT, int WV>
+template <int MT, int NT>
 static void dwd_dispatch(const GemmArgs& g, dim3 grid, bool va, bool vb, hipStream_t st) {
   const size_t lds = (size_t)2 * MT * NT * 64 * sizeof(float4);
-  const dim3 blk(64 * WV);
-  if (va && vb) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, true, true, WV>), grid, blk, lds, st, g);
-  else if (va) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, true, false, WV>), grid, blk, lds, st, g);
-  else if (vb) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, false, true, WV>), grid, blk, lds, st, g);
-  else hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, false, false, WV>), grid, blk, lds, st, g);
-}
-
-// waves per dW workgroup (SMI_DWD_WAVES=4|8; measured: 8 waves, two per
-// SIMD, 5-10 % slower per launch and 6 % slower end to end at C3)
-static int dwd_waves() {
-  static int w = 0;
-  if (!w) {
-    const char* e = getenv("SMI_DWD_WAVES");
-    w = (e && atoi(e) == 8) ? 8 : 4;
-  }
-  return w;
+  const dim3 blk(64 * kDwdWaves);
+  if (va && vb) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, true, true>), grid, blk, lds, st, g);
+  else if (va) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, true, false>), grid, blk, lds, st, g);
+  else if (vb) hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, false, true>), grid, blk, lds, st, g);
+  else hipLaunchKernelGGL((gemm_dwd_kernel<MT, NT, false, false>), grid, blk, lds, st, g);
 }
 
 // what: "gemm_splitk_reduce_kernel<the producer's form>" (smi_last_launch)
@@ -1626,14 +1529,9 @@ static int dwd_launch(GemmArgs g, hipStream_t st) {
                   (!g.B2 || (al16(g.B2) && g.b2_rs % 4 == 0 && g.split_col % 4 == 0));
   const int gm = (g.M + 16 * MT - 1) / (16 * MT), gn = (g.N + 16 * NT - 1) / (16 * NT);
   const int tiles = gm * gn;
-  static int target = 0;
-  if (!target) {    // measured: ~1 workgroup per CU beats deeper splits (partials)
-    const char* e = getenv("SMI_DWD_TARGET");
-    target = e ? atoi(e) : 256;
-    if (target < 16) target = 16;
-  }
-  int S = (target + tiles - 1) / tiles;
-  const int smax = (g.K + 32 * dwd_waves() - 1) / (32 * dwd_waves());   // >= 8 steps per wave
+  constexpr int kDwdTarget = 256;   // measured: ~1 workgroup per CU beats deeper splits (partials)
+  int S = (kDwdTarget + tiles - 1) / tiles;
+  const int smax = (g.K + 32 * kDwdWaves - 1) / (32 * kDwdWaves);   // >= 8 steps per wave
   if (S > smax) S = smax;
   const int64_t cap = smi_workspace_floats() / ((int64_t)g.M * g.N);
   if (S > cap) S = (int)cap;
@@ -1641,7 +1539,7 @@ static int dwd_launch(GemmArgs g, hipStream_t st) {
   g.part = nullptr;
   g.kchunk = g.K;
   if (S > 1) {
-    const int rs = 4 * dwd_waves() * DWD_P;        // rows per prefetch window
+    const int rs = 4 * kDwdWaves * DWD_P;          // rows per prefetch window
     g.kchunk = ((g.K + S - 1) / S + rs - 1) / rs * rs;
     S = (g.K + g.kchunk - 1) / g.kchunk;
   }
@@ -1651,17 +1549,10 @@ static int dwd_launch(GemmArgs g, hipStream_t st) {
   }
   const dim3 grid(gm, gn, S);
   const int kslot = ktime_begin(st);
-  if (dwd_waves() == 8) {
-    if (MT == 4 && NT == 8) dwd_dispatch<4, 8, 8>(g, grid, va, vb, st);
-    else if (MT == 4) dwd_dispatch<4, 4, 8>(g, grid, va, vb, st);
-    else if (NT == 8) dwd_dispatch<1, 8, 8>(g, grid, false, vb, st);
-    else dwd_dispatch<1, 4, 8>(g, grid, false, vb, st);
-  } else {
-    if (MT == 4 && NT == 8) dwd_dispatch<4, 8, 4>(g, grid, va, vb, st);
-    else if (MT == 4) dwd_dispatch<4, 4, 4>(g, grid, va, vb, st);
-    else if (NT == 8) dwd_dispatch<1, 8, 4>(g, grid, false, vb, st);
-    else dwd_dispatch<1, 4, 4>(g, grid, false, vb, st);
-  }
+  if (MT == 4 && NT == 8) dwd_dispatch<4, 8>(g, grid, va, vb, st);
+  else if (MT == 4) dwd_dispatch<4, 4>(g, grid, va, vb, st);
+  else if (NT == 8) dwd_dispatch<1, 8>(g, grid, false, vb, st);
+  else dwd_dispatch<1, 4>(g, grid, false, vb, st);
   const int nreal = (g.ones_col >= 0 ? g.N - 1 : g.N) -
                     (g.B2 ? g.split_col - g.c1_real : 0);      // padding columns do no work
   ktime_end(kslot, KT_GEMM_DW,
@@ -1674,7 +1565,7 @@ static int dwd_launch(GemmArgs g, hipStream_t st) {
 // ---- grouped weight gradients (gemm_dwd_group_kernel) ----------------------
 // whether an M x N weight gradient over row-major operands joins an open group
 // (gemm_launch's rule; the dW2 / bias column included in N by the caller)
-bool dw_group_takes(int M, int N) { return use_dwd() && M >= 1 && N >= 1 && M <= 512 && N <= 512; }
+bool dw_group_takes(int M, int N) { return M >= 1 && N >= 1 && M <= 512 && N <= 512; }
 
 // the queue of the calling thread (begin ... flush bracket one call sequence)
 static thread_local DwGroup g_grp;
@@ -1727,8 +1618,7 @@ static bool dw_group_add(const GemmArgs& g) {
   return true;
 }
 
-// target workgroups of a grouped launch for `work` tile-rows (SMI_DWD_GROUP_TARGET
-// overrides; tuning knob).  Measured at C3 (bench, one MI355X), 21504 rows:
+// target workgroups of a grouped launch for `work` tile-rows.  Measured at C3 (bench, one MI355X), 21504 rows:
 // 256 -> 4.44 ms of dW per learn, 512 -> 3.71, 768 -> 3.17, 1024 -> 2.83
 // (45 TF/s), 1536 -> 3.32, 3072 -> 4.43; at 2688 rows (one rank of eight,
 // tools/bench_dwgroup.py --segments 128): 1024 -> 65 us per launch (128-row
@@ -1740,68 +1630,36 @@ static bool dw_group_add(const GemmArgs& g) {
 // 22.9 / 21.1 / 21.3 us; the whole group at 512 vs 458: 26.5 vs 28.0 us —
 // work / 256.
 static int dw_group_target(double work) {
-  static int t = -1;
-  if (t < 0) {
-    const char* e = getenv("SMI_DWD_GROUP_TARGET");
-    t = (e && e[0]) ? atoi(e) : 0;
-    if (e && e[0] && t < 64) t = 64;
-  }
-  if (t > 0) return t;
   const double w = work / 256.0;
   return w >= 1536.0 ? 1536 : w <= 128.0 ? 128 : (int)w;
 }
 
-// narrow 16-wide tail tiles in grouped launches (SMI_DWD_NARROW=0: off; A/B knob)
-static int use_dwd_narrow() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SMI_DWD_NARROW");
-    u = (e && e[0] == '0') ? 0 : 1;
-  }
-  return u;
-}
-
 // relative time per row of a 16-wide tail tile against a full 64 x 64 tile
-// (per-workgroup clock trace of the C3 launch, tools/bench_dwgroup.py with the
-// `dwtrace` build: 832-row slabs took 18.3 us on tail tiles, 47 us on full ones)
-static double dwd_narrow_cost() {
-  static double c = -1.0;
-  if (c < 0.0) {
-    const char* e = getenv("SMI_DWD_NARROW_COST");
-    c = (e && e[0]) ? atof(e) : 0.4;
-    if (c <= 0.0 || c > 1.0) c = 0.4;
-  }
-  return c;
-}
+// (per-workgroup clock trace of the C3 launch: 832-row slabs took 18.3 us on
+// tail tiles, 47 us on full ones)
+constexpr double kDwdNarrowCost = 0.4;
 
 // Workgroups of one grouped launch resident at once (CUs x occupancy).
 static int dwd_group_slots(size_t lds) {
   static int slots = 0;
   if (!slots) {
-    slots = dwd_waves() == 8 ? resident_grid(gemm_dwd_group_kernel<8>, 512, lds)
-                             : resident_grid(gemm_dwd_group_kernel<4>, 256, lds);
+    slots = resident_grid(gemm_dwd_group_kernel, 256, lds);
     if (slots < 1) slots = 256;
-    // planned for the occupancy the 4-wave kernel is built for (SMI_DWG_OCC),
+    // planned for the occupancy the kernel is built for (DWG_OCC),
     // not for what a build that happens to need fewer registers could reach:
     // the slot count sets the slab lengths, and with them every result's
     // rounding (a leaner build reached 4 per CU and moved every slab)
-    if (dwd_waves() == 4) {
-      int dev = 0, cus = 0;
-      (void)hipGetDevice(&dev);
-      if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
-          cus > 0 && slots > cus * SMI_DWG_OCC)
-        slots = cus * SMI_DWG_OCC;
-    }
+    int dev = 0, cus = 0;
+    (void)hipGetDevice(&dev);
+    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess &&
+        cus > 0 && slots > cus * DWG_OCC)
+      slots = cus * DWG_OCC;
   }
   return slots;
 }
 
-// 64-element groups per block of the grouped reducer (SMI_RED_U=1: one, the
-// round-5 form; A/B knob)
-static int red_u() {
-  static const int u = [] { const char* e = getenv("SMI_RED_U"); return e && e[0] == '1' ? 1 : 4; }();
-  return u;
-}
+// 64-element groups per block of the grouped reducer
+constexpr int kRedU = 4;
 
 // One GEMM as the planner sees it, and the plan of one grouped launch: pure
 // host arithmetic (no device call, no pointers), so a CPU test can sweep it
@@ -1878,13 +1736,9 @@ static int dw_plan_rects(const DwPlanGemm& p, int gi, int fit, DwPlanEnt* out) {
   return n;
 }
 
-// fitted edge classes on the 4-wave launch (the product's); the 8-wave launch
-// (SMI_DWD_WAVES=8, and the weight gradients that share the BPTT's launch)
-// keeps the 16-wide M tail alone; SMI_DWD_NARROW=0: padded tiles everywhere
-static int dw_fit_level(int wv) {
-  if (!use_dwd_narrow()) return 0;
-  return wv == 4 && DWG_NT == 4 ? 2 : 1;
-}
+// fitted edge classes on the 4-wave launch; the 8-wave launch (the weight
+// gradients that share the BPTT's launch) keeps the 16-wide M tail alone
+static int dw_fit_level(int wv) { return wv == 4 ? 2 : 1; }
 
 // Rectangles, slabs and partial offsets of one grouped launch of ng GEMMs: wv
 // waves per workgroup, slots resident workgroups, cap floats of workspace, at
@@ -1914,18 +1768,18 @@ static int dw_plan(const DwPlanGemm* gemms, int ng, int wv, int slots, int64_t c
   for (int i = 0; i < ng; ++i) {
     const DwPlanGemm& g = gemms[i];
     const int tail = g.M % 64, gn = (g.N + 16 * NTF - 1) / (16 * NTF);
-    const bool narrow = use_dwd_narrow() && tail > 0 && tail <= 16;
+    const bool narrow = tail > 0 && tail <= 16;
     const bool cut = narrow && g.M > 64 && nb + (ng - i) + 1 <= kBandMax;
     first_band[i] = nb;
     tail_band[i] = -1;
     if (cut) {
       band[nb++] = Band{i, 0, g.M - tail, (int64_t)(g.M / 64) * gn, 1.0, 0};
       tail_band[i] = nb;
-      band[nb++] = Band{i, g.M - tail, tail, gn, dwd_narrow_cost(), 0};
+      band[nb++] = Band{i, g.M - tail, tail, gn, kDwdNarrowCost, 0};
     } else {
       const int gm = (g.M + 63) / 64;
       band[nb++] = Band{i, 0, g.M, (int64_t)gm * gn,
-                        narrow ? ((gm - 1) + dwd_narrow_cost()) / gm : 1.0, 0};
+                        narrow ? ((gm - 1) + kDwdNarrowCost) / gm : 1.0, 0};
     }
   }
   for (int b = 0; b < nb; ++b) {
@@ -1941,19 +1795,11 @@ static int dw_plan(const DwPlanGemm* gemms, int ng, int wv, int slots, int64_t c
   // anyway and the span is the longest slab: equal slab lengths (shorter
   // fp32 chains on the tail tiles).
   int target = target_fixed > 0 ? target_fixed : dw_group_target(work_u);
-  static const bool env_target = [] {
-    const char* e = getenv("SMI_DWD_GROUP_TARGET");
-    return e && e[0];
-  }();
-  const bool fixed_target = env_target || target_fixed > 0;
+  const bool fixed_target = target_fixed > 0;
   if (!fixed_target && target >= slots) {
-    // whole rounds of at most ~2048 cost-rows per workgroup (SMI_DWD_ROUND_ROWS)
-    static const double round_rows = [] {
-      const char* e = getenv("SMI_DWD_ROUND_ROWS");
-      const double v = (e && e[0]) ? atof(e) : 2048.0;
-      return v >= 256.0 ? v : 2048.0;
-    }();
-    const int rounds = (int)std::max(1.0, std::ceil(work / (slots * round_rows)));
+    // whole rounds of at most ~2048 cost-rows per workgroup
+    constexpr double kDwdRoundRows = 2048.0;
+    const int rounds = (int)std::max(1.0, std::ceil(work / (slots * kDwdRoundRows)));
     target = slots * rounds;
   } else {
     for (int b = 0; b < nb; ++b) band[b].cost = 1.0;
@@ -2010,7 +1856,7 @@ static int dw_plan(const DwPlanGemm* gemms, int ng, int wv, int slots, int64_t c
     e.part_off = off;
     off += ((int64_t)e.S * e.M * e.N + 3) / 4 * 4;   // (every entry's partials 16-byte aligned)
     P.wg0[i + 1] = P.wg0[i] + e.gm * e.gn * e.S;
-    P.rb0[i + 1] = P.rb0[i] + (int)(((int64_t)e.M * e.N + 64 * red_u() - 1) / (64 * red_u()));
+    P.rb0[i + 1] = P.rb0[i] + (int)(((int64_t)e.M * e.N + 64 * kRedU - 1) / (64 * kRedU));
   }
   if (off > cap) return -1;
   P.need = off;
@@ -2079,11 +1925,6 @@ static int dw_prepare(DwGroup& G, int wv, int slots, int64_t ws_off, int64_t& ne
 // short-batch 16 x 16-tile kernels (gemm_t16_kernel, gemm_dwt16_kernel): 16-k
 // chunks per wave, K <= 4 * 16 * 8 = 512
 constexpr int T16_MAXC = 8;
-// SMI_GEMM_T16=0: the split-K / grouped forms for short batches instead (A/B knob)
-static bool use_t16() {
-  static const bool on = [] { const char* e = getenv("SMI_GEMM_T16"); return !(e && e[0] == '0'); }();
-  return on;
-}
 
 // Weight gradients of short batches without split-K: one 16 x 16 tile of one
 // group entry per workgroup, the four waves splitting the rows in 16-row
@@ -2229,7 +2070,7 @@ int dw_group_flush(hipStream_t st) {
   }
   // short batches (every entry <= 512 rows, one group, no epilogue task):
   // 16 x 16 tiles written directly, no partials and no reducer
-  if (!pre && !G.x.on && use_t16()) {
+  if (!pre && !G.x.on) {
     bool small = G.ng > 0;
     for (int i = 0; i < G.ng; ++i) small = small && G.g[i].K <= 4 * 16 * T16_MAXC;
     if (small) {
@@ -2243,13 +2084,10 @@ int dw_group_flush(hipStream_t st) {
   int64_t need = 0;
   if (G.ng > 0) {
     if (pre && g_pre.ng + G.ng > kDwGemmMax) return set_error(SMI_E_ARG, "dw group: too many GEMMs");
-    RC_CHECK(dw_prepare(G, dwd_waves(), dwd_group_slots(kDwdLds), 0, need,
+    RC_CHECK(dw_prepare(G, kDwdWaves, dwd_group_slots(kDwdLds), 0, need,
                         kDwGroupMax - (pre ? g_pre.n : 0)));
     const int kslot = ktime_begin(st);
-    if (dwd_waves() == 8)
-      hipLaunchKernelGGL(gemm_dwd_group_kernel<8>, dim3(G.wg0[G.n]), dim3(512), kDwdLds, st, G);
-    else
-      hipLaunchKernelGGL(gemm_dwd_group_kernel<4>, dim3(G.wg0[G.n]), dim3(256), kDwdLds, st, G);
+    hipLaunchKernelGGL(gemm_dwd_group_kernel, dim3(G.wg0[G.n]), dim3(256), kDwdLds, st, G);
     ktime_end(kslot, KT_GEMM_DW, g_grp_flops, st);
     RC_CHECK(check_launch(dw_group_name(G, false)));
   }
@@ -2272,27 +2110,16 @@ int dw_group_flush(hipStream_t st) {
     need += g_pre_need;
   }
   const int rslot = ktime_begin(st);
-  if (red_u() == 4)
-    hipLaunchKernelGGL(gemm_group_reduce_kernel<4>, dim3(R.rb0[R.n] + (R.x.on ? 1 : 0)), dim3(kWG), 0,
-                       st, R);
-  else
-    hipLaunchKernelGGL(gemm_group_reduce_kernel<1>, dim3(R.rb0[R.n] + (R.x.on ? 1 : 0)), dim3(kWG), 0,
-                       st, R);
+  hipLaunchKernelGGL(gemm_group_reduce_kernel<kRedU>, dim3(R.rb0[R.n] + (R.x.on ? 1 : 0)), dim3(kWG), 0,
+                     st, R);
   ktime_end(rslot, KT_GEMM_REDUCE, (double)need, st);
   return check_launch(dw_group_name(R, true));
-}
-
-// SMI_BWD_DW=0: the BPTT and the heads' weight gradients as separate launches
-// (A/B knob); SMI_BWD_DW_EXCL=0: let the two kinds of workgroups share CUs
-static bool use_bwd_dw() {
-  static const bool on = [] { const char* e = getenv("SMI_BWD_DW"); return !(e && e[0] == '0'); }();
-  return on;
 }
 
 int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, const float* w_hh,
                        int S, int B, int H, float* dgates, hipStream_t st, const int* skip) {
   const int br = lstm_bwd_q_form(B, H, w_hh);
-  if (!use_bwd_dw() || !g_grp_on || g_pre_on || g_grp.ng == 0 || br == 0 || S <= 0 || B <= 0)
+  if (!g_grp_on || g_pre_on || g_grp.ng == 0 || br == 0 || S <= 0 || B <= 0)
     return SMI_E_NOFIT;
   int cus = 0, dev = 0;
   (void)hipGetDevice(&dev);
@@ -2307,24 +2134,14 @@ int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, c
   RC_CHECK(dw_prepare(Ga, 8, cus - B, 0, need, kDwGroupMax - (kDwGemmMax - Ga.ng)));
   // one workgroup per CU (the LDS request): the recurrence's workgroups keep
   // their CUs to themselves, the weight gradients take the others
-  static const bool excl = [] { const char* e = getenv("SMI_BWD_DW_EXCL"); return !(e && e[0] == '0'); }();
-  size_t lds = excl ? std::max(kDwdLds, (size_t)84 * 1024) : kDwdLds;
-  // the BPTT workgroups stage their step inputs in the same dynamic LDS
-  const size_t stg = (size_t)lstm_bwd_stage_floats(S, H) * 4;
-  const bool stage = use_bwd_stage() && stg <= kBwdStageMax;
-  if (stage) lds = std::max(lds, stg);
+  const size_t lds = std::max(kDwdLds, (size_t)84 * 1024);
   LstmBwdArgs la{dh, gates, cbuf, w_hh, S, B, H, dgates, skip};
   const dim3 grid((unsigned)(B + Ga.wg0[Ga.n]));
   const int kslot = ktime_begin(st);
 #define SMI_BD(BR_)                                                                          \
   do {                                                                                       \
-    if (stage) {                                                                             \
-      allow_lds(lstm_bwd_dw_kernel<BR_, true>, lds);                                         \
-      hipLaunchKernelGGL((lstm_bwd_dw_kernel<BR_, true>), grid, dim3(kVT), lds, st, la, Ga); \
-    } else {                                                                                 \
-      allow_lds(lstm_bwd_dw_kernel<BR_, false>, lds);                                        \
-      hipLaunchKernelGGL((lstm_bwd_dw_kernel<BR_, false>), grid, dim3(kVT), lds, st, la, Ga);\
-    }                                                                                        \
+    allow_lds(lstm_bwd_dw_kernel<BR_>, lds);                                                 \
+    hipLaunchKernelGGL((lstm_bwd_dw_kernel<BR_>), grid, dim3(kVT), lds, st, la, Ga);         \
   } while (0)
   if (br == 16) SMI_BD(16);
   else if (br == 25) SMI_BD(25);
@@ -2339,15 +2156,6 @@ int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, c
   g_grp.ng = g_grp.n = 0;                           // the group queues the rest
   g_grp_flops = 0.0;                                // (its launch times the rest only)
   return SMI_OK;
-}
-
-static int use_panel() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SMI_PANEL");
-    u = (e && e[0] == '0') ? 0 : 1;
-  }
-  return u;
 }
 
 // returns the launched instantiation's name (smi_last_launch)
@@ -2370,27 +2178,20 @@ static const char* panel_dispatch(const GemmArgs& g, dim3 grid, int ntw, hipStre
 // tall forward / input-gradient GEMMs with 16-byte operands: gemm_panel_kernel
 static bool panel_ok(int epi, const GemmArgs& g) {
   auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  // below panel_min_rows the row panels cannot fill the GPU and their serial K
+  // below kPanelMinRows the row panels cannot fill the GPU and their serial K
   // loop is the latency: the tiled kernel with split-K takes those (measured at
   // 128 segments per GPU, 2688 / 3328 rows: forwards + input gradients 2.43 ->
-  // 1.69 ms per learn, +0.72 ms of split-K reduces, learn 6.10 -> 5.81 ms;
-  // SMI_PANEL_MIN_ROWS overrides)
-  static const int panel_min_rows = [] {
-    const char* e = getenv("SMI_PANEL_MIN_ROWS");
-    return e ? atoi(e) : 4096;
-  }();
-  if (!use_panel() || g.M < panel_min_rows || g.N > 640 || g.K > 1024 || g.K < 1) return false;
+  // 1.69 ms per learn, +0.72 ms of split-K reduces, learn 6.10 -> 5.81 ms)
+  constexpr int kPanelMinRows = 4096;
+  if (g.M < kPanelMinRows || g.N > 640 || g.K > 1024 || g.K < 1) return false;
   if (g.a_cs != 1 || g.a_rs % 4 || g.K % 4 || !al16(g.A) || !al16(g.B)) return false;
   if (epi == EPI_FWD) return g.b_rs == 1 && g.b_cs % 4 == 0;
   // input gradients: the transposing LDS stage costs more than it saves below
   // ~96 output columns (in the C3 learner 300->100 runs 16 % faster here than
-  // on gemm_kernel; SMI_PANEL_DX_MIN overrides)
-  static const int dx_min = [] {
-    const char* e = getenv("SMI_PANEL_DX_MIN");
-    return e ? atoi(e) : 96;
-  }();
+  // on gemm_kernel)
+  constexpr int kPanelDxMin = 96;
   if (epi == EPI_DX)
-    return g.b_cs == 1 && g.b_rs % 4 == 0 && g.N % 4 == 0 && g.N >= dx_min;
+    return g.b_cs == 1 && g.b_rs % 4 == 0 && g.N % 4 == 0 && g.N >= kPanelDxMin;
   return false;
 }
 
@@ -2419,7 +2220,7 @@ static int panel_launch(int epi, const GemmArgs& g, hipStream_t st) {
 // the MFMA tiles (which pad K to 16/32).  Per element: the k-ordered fmaf
 // chain from 0 (for K = 1 bit-identical to the tiled path).  A thread owns 4
 // consecutive columns of 4 rows (the W slice in registers, 16-byte mask reads
-// and stores, coalesced along the row).  SMI_DX_SMALLK=0 disables it.
+// and stores, coalesced along the row).
 template <int KK, bool V4, bool A4 = false>
 __global__ void __launch_bounds__(kWG)
 dx_smallk_kernel(GemmArgs g) {
@@ -2482,15 +2283,6 @@ dx_smallk_kernel(GemmArgs g) {
       }
     }
   }
-}
-
-static int use_dx_smallk() {
-  static int u = -1;
-  if (u < 0) {
-    const char* e = getenv("SMI_DX_SMALLK");
-    u = (e && e[0] == '0') ? 0 : 1;
-  }
-  return u;
 }
 
 static int dx_smallk_launch(const GemmArgs& g, hipStream_t st) {
@@ -2608,11 +2400,11 @@ gemm_t16_kernel(GemmArgs g) {
 static int gemm_launch(int epi, GemmArgs g, hipStream_t st) {
   if (g.M <= 0 || g.N <= 0) return SMI_OK;
   g.part = nullptr;
-  if (epi == EPI_DX && use_dx_smallk() && g.K >= 1 && g.K <= 8 && g.a_cs == 1 && g.b_cs == 1)
+  if (epi == EPI_DX && g.K >= 1 && g.K <= 8 && g.a_cs == 1 && g.b_cs == 1)
     return dx_smallk_launch(g, st);
   if (epi != EPI_DW && !g.xsrc && panel_ok(epi, g)) return panel_launch(epi, g, st);
   if (epi == EPI_DW) {
-    const bool grp_ok = use_dwd() && g.a_rs == 1 && g.b_cs == 1 && g.K >= 1 &&
+    const bool grp_ok = g.a_rs == 1 && g.b_cs == 1 && g.K >= 1 &&
                         (g.ones_col >= 0 ? g.ones_col : g.N) >= 1 && g.M <= 512 && g.N <= 512;
     if (grp_ok && dw_group_add(g)) return SMI_OK;
     if (g_grp_on) g_grp_missed = true;     // runs outside the open group
@@ -2642,15 +2434,12 @@ static int gemm_launch(int epi, GemmArgs g, hipStream_t st) {
   // output has too few tiles to fill the GPU over K >= 128 (the pixel stem's
   // 2592 -> 256 FC; DDPG's 512-row layers: 40 tiles, a serial K loop per tile
   // otherwise; C4 +20 %).  The reducer applies bias/activation or the ReLU mask.
-  static const int fwd_split_min = [] {
-    const char* e = getenv("SMI_FWD_SPLITK_MIN");
-    return e ? atoi(e) : 4 * GBK;
-  }();
+  constexpr int kFwdSplitkMin = 4 * GBK;
   const bool split_fwd = (epi == EPI_FWD || epi == EPI_DX) && gm * gn < 256 &&
-                         g.K >= fwd_split_min;
+                         g.K >= kFwdSplitkMin;
   // the short-batch kernel for every forward / input gradient whose 64 x 64
   // tiling leaves the GPU mostly idle (< 256 tiles), split-K or not
-  if ((epi == EPI_FWD || epi == EPI_DX) && gm * gn < 256 && use_t16() && g.M <= 4096 &&
+  if ((epi == EPI_FWD || epi == EPI_DX) && gm * gn < 256 && g.M <= 4096 &&
       g.K <= 4 * 16 * T16_MAXC) {
     const dim3 grid16((g.M + 15) / 16, (g.N + 15) / 16);
     const int kslot = ktime_begin(st);
@@ -2661,7 +2450,7 @@ static int gemm_launch(int epi, GemmArgs g, hipStream_t st) {
   }
   if ((epi == EPI_DW && g.K > 4 * GBK) || split_fwd) {
     const int tiles = gm * gn;
-    S = (smi_splitk_target() + tiles - 1) / tiles;    // ~2-4 workgroups per CU
+    S = (kSplitkTarget + tiles - 1) / tiles;    // ~2-4 workgroups per CU
     const int smax = (g.K + 4 * GBK - 1) / (4 * GBK);   // >= 4 K-steps per slab
     if (S > smax) S = smax;
     const int64_t cap = smi_workspace_floats() / ((int64_t)g.M * g.N);
@@ -2747,7 +2536,7 @@ int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,
                           int64_t lds, int xcols, hipStream_t st) {
   const int gm = (M + GBM - 1) / GBM, gn = (N + GBN - 1) / GBN;
-  const bool t16 = !(K >= 1 && K <= 64 && N >= 32 && N <= 512 && M >= 2048) && use_t16() &&
+  const bool t16 = !(K >= 1 && K <= 64 && N >= 32 && N <= 512 && M >= 2048) &&
                    gm * gn < 256 && M <= 4096 && K <= 4 * 16 * T16_MAXC && M > 0;
   if (!t16) {
     RC_CHECK(launch_linear_fwd(X, ldx, M, K, W, ldw, b, N, act, Y, ldy, st));
@@ -2791,7 +2580,7 @@ int launch_linear_bwd_dw2(const float* dY, int64_t ldg, int M, int N, const floa
   g.B2 = X2; g.b2_rs = ldx2; g.split_col = K1p; g.c1_real = K1;
   g.C = dW1; g.ldc = ld1; g.C2 = dW2; g.ldc2 = ld2;
   g.ones_col = K1p + K2; g.bias_out = db1; g.bias_out2 = db2; g.skip = skip;
-  if (!(g.a_rs == 1 && g.b_cs == 1 && use_dwd() && g.M <= 512 && g.N <= 512))
+  if (!(g.a_rs == 1 && g.b_cs == 1 && g.M <= 512 && g.N <= 512))
     return set_error(SMI_E_ARG, "bwd_dw2: shape not supported");
   if (dw_group_add(g)) return SMI_OK;
   if (g_grp_on) g_grp_missed = true;

@@ -1,5 +1,5 @@
 // lstm_cell.hpp — LSTM cell arithmetic shared by the sequence kernels
-// (lstm_kernels.hip) and the BPTT + weight-gradient launch (linear_kernels.hip):
+// (lstm_mfma.hip, lstm_valu.hip) and the BPTT + weight-gradient launch (linear_kernels.hip):
 // the activations, the kernel argument blocks, the lane-quad exchanges and the
 // one-segment-per-workgroup BPTT body (lstm_bwd_q_body).
 #pragma once
@@ -21,9 +21,6 @@ namespace smi {
 __device__ __forceinline__ float sigm(float x) {
   return __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(-1.4426950408889634f * x));
 }
-#ifdef SMI_OLD_TANH
-__device__ __forceinline__ float ftanh(float x) { return 2.f * sigm(2.f * x) - 1.f; }
-#else
 __device__ __forceinline__ float ftanh(float x) {
   const float ax = fabsf(x);
   const float z = x * x;
@@ -33,7 +30,6 @@ __device__ __forceinline__ float ftanh(float x) {
   const float e = 1.f - 2.f * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(2.8853900817779268f * ax));
   return ax < 0.625f ? p : copysignf(e, x);
 }
-#endif
 
 struct LstmFwdArgs {
   const float* xproj;     // [S][B][4H] = x W_ih^T + b_ih
@@ -57,10 +53,6 @@ struct LstmFwdArgs {
   // over more steps than a backward needs (the GAE critic pass over T + 1
   // steps serves as the first policy forward over its first E steps)
   int keep;
-  // r4 MFMA forward (round 6): W_ih and W_hh reach the lanes' row registers
-  // through LDS (coalesced global reads) instead of a row per lane from global
-  // memory; set by the launcher with the dynamic LDS it sized for it
-  int wstage;
 };
 
 struct LstmBwdArgs {
@@ -72,6 +64,44 @@ struct LstmBwdArgs {
   float* dgates;          // [S][B][4H] dL/d(pre-activation gates)
   const int* skip;
 };
+
+// Developer phase timer (build variant 'prof', -DSMI_PROF): workgroup 0, wave
+// 0 accumulates wall-clock ticks (100 MHz) per step phase into the g_lstm_ticks
+// of the unit it is compiled in (lstm_mfma.hip, lstm_valu.hip):
+//   [0] fwd MFMA (incl. LDS operand reads)  [1] fwd epilogue  [2] fwd barrier
+//   [3] bwd element-wise + stores           [4] bwd barrier   [5] bwd MFMA
+#ifdef SMI_PROF
+#define LSTM_T0() unsigned long long t_prev_ = wall_clock64()
+#define LSTM_TICK(id)                                                       \
+  do {                                                                      \
+    if (blockIdx.x == 0 && threadIdx.x == 0) {                              \
+      const unsigned long long n_ = wall_clock64();                         \
+      g_lstm_ticks[id] += n_ - t_prev_;                                     \
+      t_prev_ = n_;                                                         \
+    }                                                                       \
+  } while (0)
+#else
+#define LSTM_T0() (void)0
+#define LSTM_TICK(id) (void)0
+#endif
+
+// The one-segment VALU forms' entry points (lstm_valu.hip) for the launchers
+// (lstm_mfma.hip); each returns the literal that names the instantiation it
+// launched (smi_last_launch).  kx 0 = xproj input, else the fused x projection
+// with x widths <= kx (48 / 64).
+const char* lstm_v_fwd(const LstmFwdArgs& a, int kx, hipStream_t st);
+const char* lstm_v_bwd(const LstmBwdArgs& a, hipStream_t st);
+// two sequence sets in one launch (fused x parts)
+const char* lstm_q_fwd_dual(const LstmFwdArgs& a, const LstmFwdArgs& a1, int kx, hipStream_t st);
+// the BPTT's K-split form loads W_hh as float4 runs (lstm_bwd_q_body)
+bool lstm_bwd_q_ok(int H, const float* w_hh);
+// LDS of the staged x sequence and the precomputed x parts (KX > 0); the fused
+// form is used up to kVxMax (at H = 100: S <= 61 steps for x widths <= 48,
+// S <= 60 for <= 64; tests/test_gpu_forms.py runs both sides of the first edge)
+constexpr size_t kVxMax = 120 * 1024;
+inline size_t lstm_fwd_v_lds(int S, int KX, int blk) {
+  return ((((size_t)S * KX + 3) & ~(size_t)3) + (size_t)S * blk) * 4;
+}
 
 typedef float vf2 __attribute__((ext_vector_type(2)));
 constexpr int kVT = 512;      // threads of the VALU recurrence workgroups (4H <= 512)
@@ -94,31 +124,14 @@ __device__ __forceinline__ float dpp_ror8(float v) {          // row_ror:8
 }
 
 // BPTT of one segment (b) at one segment per workgroup (the K-split form,
-// lstm_kernels.hip): BR rows of W_hh per lane of a 16-lane row (16 BR >= 4H),
+// lstm_valu.hip): BR rows of W_hh per lane of a 16-lane row (16 BR >= 4H),
 // BRP their padding to whole b128 reads
-// CH4: the recurrent dot product in four FMA chains instead of two (build
-// knob SMI_BPTT_CH4, default on; variant 'ch2' of surreal_amd/build.py is the
-// round-5 form: 128 segments 2.919 vs 2.908 ms per learn, interleaved pairs)
-#ifndef SMI_BPTT_CH4
-#define SMI_BPTT_CH4 1
-#endif
-// Floats of the BPTT's staged per-step inputs (lstm_bwd_q_body with a
-// stage): gates [S][4H], cell states [S+1][H], dh [S][H] of one segment
-__host__ __device__ inline int64_t lstm_bwd_stage_floats(int S, int H) {
-  return (int64_t)S * 4 * H + (int64_t)(S + 1) * H + (int64_t)S * H;
-}
-
-// STG: stage = LDS of lstm_bwd_stage_floats(S, H) floats, 16-byte aligned
-// (a compile-time choice: a run-time one leaves the global-load path's waits
-// in the loop).  With it every step input (activated gates, c_t, c_{t-1}, dh_t) is
-// copied to LDS in the prologue and the step loop issues no global load
-// (without it the loop header waits vmcnt(0) every step: the inputs fetched
-// two steps ahead, and the previous step's dgates store, stores counting in
-// vmcnt on gfx950).  Measured neutral-to-worse (the staging prologue costs
-// what the waits did): an A/B knob, SMI_BWD_STAGE=1 (round 6)
-template <int BR, bool CH4 = false, bool STG = false>
-__device__ __forceinline__ void lstm_bwd_q_body(const LstmBwdArgs& a, int b,
-                                                float* __restrict__ stage = nullptr) {
+// The step inputs (activated gates, c_t, c_{t-1}, dh_t) are fetched two steps
+// ahead (staging them all in LDS in the prologue cost what the loop's
+// per-step vmcnt(0) did: 128 segments 2.771-2.777 vs 2.764-2.765 ms per learn,
+// profiles/r06/ab/bwd_stage_*)
+template <int BR>
+__device__ __forceinline__ void lstm_bwd_q_body(const LstmBwdArgs& a, int b) {
   if (a.skip && a.skip[0] != 0) return;
   constexpr int BRP = (BR + 3) & ~3;
   __shared__ __attribute__((aligned(16))) float dG[2][16 * BRP];
@@ -151,51 +164,11 @@ __device__ __forceinline__ void lstm_bwd_q_body(const LstmBwdArgs& a, int b,
   const int dgi = (g / BR) * BRP + g % BR;        // this lane's dgate in the padded image
   float gq, ct, ctm, dho, gqn, ctn, ctmn, dhon;
   if (a.S <= 0) return;
-  float* sG = stage;                                // [S][4H]
-  float* sC = STG ? sG + (int64_t)a.S * G4 : nullptr;       // [S+1][H]
-  float* sD = STG ? sC + (int64_t)(a.S + 1) * H : nullptr;  // [S][H]
-  if constexpr (STG) {
-    // rows of 4H / H floats, float4 runs (H % 4 == 0: lstm_bwd_q_ok), eight
-    // float4 loads per thread in flight per trip, then their LDS stores
-    const int q4 = H >> 2, g4 = 4 * q4;
-    const int ng = a.S * g4, nc = (a.S + 1) * q4, nd = a.S * q4;
-    const int n4 = ng + nc + nd, NT = blockDim.x;
-    auto src = [&](int e) -> const float4* {
-      if (e < ng) {
-        const int t = e / g4, j = e - t * g4;
-        return reinterpret_cast<const float4*>(a.gates + ((int64_t)t * B + b) * G4) + j;
-      }
-      e -= ng;
-      if (e < nc) {
-        const int t = e / q4, j = e - t * q4;
-        return reinterpret_cast<const float4*>(a.cbuf + (int64_t)t * BH + (int64_t)b * H) + j;
-      }
-      e -= nc;
-      const int t = e / q4, j = e - t * q4;
-      return reinterpret_cast<const float4*>(a.dh + (int64_t)t * BH + (int64_t)b * H) + j;
-    };
-    float4* s4 = reinterpret_cast<float4*>(stage);
-    for (int e0 = tid; e0 < n4; e0 += 8 * NT) {
-      float4 v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = *src(min(e0 + j * NT, n4 - 1));
-#pragma unroll
-      for (int j = 0; j < 8; ++j) s4[min(e0 + j * NT, n4 - 1)] = v[j];   // (a clamped index writes its owner's value)
-    }
-    __syncthreads();
-  }
   auto fetch = [&](int t, float& G, float& C, float& CM, float& DH) {
-    if constexpr (STG) {
-      G = sG[t * G4 + g];
-      C = sC[(t + 1) * H + uc];
-      CM = sC[t * H + uc];
-      DH = sD[t * H + uc];
-    } else {
-      G = a.gates[((int64_t)t * B + b) * G4 + g];
-      C = a.cbuf[(int64_t)(t + 1) * BH + (int64_t)b * H + uc];
-      CM = a.cbuf[(int64_t)t * BH + (int64_t)b * H + uc];
-      DH = a.dh[(int64_t)t * BH + (int64_t)b * H + uc];
-    }
+    G = a.gates[((int64_t)t * B + b) * G4 + g];
+    C = a.cbuf[(int64_t)(t + 1) * BH + (int64_t)b * H + uc];
+    CM = a.cbuf[(int64_t)t * BH + (int64_t)b * H + uc];
+    DH = a.dh[(int64_t)t * BH + (int64_t)b * H + uc];
   };
   fetch(a.S - 1, gq, ct, ctm, dho);
   fetch(a.S >= 2 ? a.S - 2 : 0, gqn, ctn, ctmn, dhon);
@@ -236,32 +209,23 @@ __device__ __forceinline__ void lstm_bwd_q_body(const LstmBwdArgs& a, int b,
 #pragma unroll
     for (int i = 0; i < BRP / 4; ++i) dv[i] = dp[i];
     vf2 p01 = {0.f, 0.f}, p23 = {0.f, 0.f};
-    if constexpr (CH4) {
-      // four FMA chains (even / odd rows), half as long, summed at the end
-      vf2 q01 = {0.f, 0.f}, q23 = {0.f, 0.f};
+    // four FMA chains (even / odd rows), half as long as two, summed at the
+    // end (two chains: 128 segments 2.919 vs 2.908 ms per learn)
+    vf2 q01 = {0.f, 0.f}, q23 = {0.f, 0.f};
 #pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        const float d = (i & 3) == 0 ? dv[i >> 2].x : (i & 3) == 1 ? dv[i >> 2].y
-                      : (i & 3) == 2 ? dv[i >> 2].z : dv[i >> 2].w;
-        if (i & 1) {
-          q01 = __builtin_elementwise_fma(vf2{d, d}, w01[i], q01);
-          q23 = __builtin_elementwise_fma(vf2{d, d}, w23[i], q23);
-        } else {
-          p01 = __builtin_elementwise_fma(vf2{d, d}, w01[i], p01);
-          p23 = __builtin_elementwise_fma(vf2{d, d}, w23[i], p23);
-        }
-      }
-      p01 = p01 + q01;
-      p23 = p23 + q23;
-    } else {
-#pragma unroll
-      for (int i = 0; i < BR; ++i) {
-        const float d = (i & 3) == 0 ? dv[i >> 2].x : (i & 3) == 1 ? dv[i >> 2].y
-                      : (i & 3) == 2 ? dv[i >> 2].z : dv[i >> 2].w;
+    for (int i = 0; i < BR; ++i) {
+      const float d = (i & 3) == 0 ? dv[i >> 2].x : (i & 3) == 1 ? dv[i >> 2].y
+                    : (i & 3) == 2 ? dv[i >> 2].z : dv[i >> 2].w;
+      if (i & 1) {
+        q01 = __builtin_elementwise_fma(vf2{d, d}, w01[i], q01);
+        q23 = __builtin_elementwise_fma(vf2{d, d}, w23[i], q23);
+      } else {
         p01 = __builtin_elementwise_fma(vf2{d, d}, w01[i], p01);
         p23 = __builtin_elementwise_fma(vf2{d, d}, w23[i], p23);
       }
     }
+    p01 = p01 + q01;
+    p23 = p23 + q23;
     float pu[4] = {p01.x, p01.y, p23.x, p23.y};
 #pragma unroll
     for (int k = 0; k < 4; ++k) {

@@ -742,8 +742,8 @@ int launch_moments(const float* x, int64_t n, const double* part, int np, double
 int launch_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, int* step,
                      const float* lr, float b1, float b2, float eps, float wd, float max_norm,
                      float clip_value, const int* skip, float* norm_out, hipStream_t st) {
-  static const int gcap = [] { const char* e = getenv("SMI_ADAM_GRID"); return e ? atoi(e) : 2048; }();
-  const int grid = grid_for((n + 3) / 4, gcap > 0 && gcap <= 2048 ? gcap : 2048);
+  constexpr int kAdamGrid = 2048;
+  const int grid = grid_for((n + 3) / 4, kAdamGrid);
   const bool need_norm = max_norm > 0.f || norm_out != nullptr;
   double* part = nullptr;
   if (need_norm) {
@@ -753,17 +753,12 @@ int launch_adam_clip(float* p, const float* g, float* m, float* v, int64_t n, in
     const int rc0 = check_launch("sumsq_partial_kernel");
     if (rc0) return rc0;
   }
-  // nontemporal loads and stores of p, g, m, v from SMI_ADAM_NT_MIN (2^24)
-  // parameters: streams read and written once per launch, past the caches.
+  // nontemporal loads and stores of p, g, m, v from kAdamNtMin parameters: streams read and written once per launch, past the caches.
   // Measured (67 M parameters, tools/bench_hbm.py, one MI355X): plain 0.61 /
   // 0.61 of HBM (clip / no clip), nontemporal stores 0.62 / 0.62, both 0.75 /
-  // 0.67.  A/B knob SMI_ADAM_NT: 0 plain, 1 stores, 2 loads, 3 both (default).
-  static const int nt_v = [] { const char* e = getenv("SMI_ADAM_NT"); return e ? atoi(e) & 3 : 3; }();
-  static const int64_t nt_min = [] {
-    const char* e = getenv("SMI_ADAM_NT_MIN"); return e ? (int64_t)atoll(e) : (int64_t)1 << 24; }();
-  const int ntv = n >= nt_min ? nt_v : 0;
-  auto kfn = ntv == 1 ? adam_kernel<1> : ntv == 2 ? adam_kernel<2> : ntv == 3 ? adam_kernel<3>
-                                                                    : adam_kernel<0>;
+  // 0.67.
+  constexpr int64_t kAdamNtMin = (int64_t)1 << 24;
+  auto kfn = n >= kAdamNtMin ? adam_kernel<3> : adam_kernel<0>;
   hipLaunchKernelGGL(kfn, dim3(grid), dim3(kWG), 0, st, p, g, m, v, n, step, lr, b1, b2,
                      eps, wd, max_norm, clip_value, part, need_norm ? grid : 0, skip, norm_out);
   int rc = check_launch("adam_kernel");

@@ -18,14 +18,8 @@
 
 namespace smi {
 
-#ifndef SMI_FWG
-#define SMI_FWG 256
-#endif
-#ifndef SMI_ADAM_PER
-#define SMI_ADAM_PER 24
-#endif
-constexpr int kFWG = SMI_FWG;          // threads of the epoch workgroups (4 waves, 1 per SIMD)
-constexpr int kAdamPer = SMI_ADAM_PER; // parameters per thread held in registers
+constexpr int kFWG = 256;      // threads of the epoch workgroups (4 waves, 1 per SIMD)
+constexpr int kAdamPer = 24;   // parameters per thread held in registers
 
 // Developer phase timer (tools/fused_breakdown.py --phases): built only with
 // -DSMI_PROF; accumulates wall-clock ticks (100 MHz) per phase and workgroup.
@@ -212,9 +206,7 @@ __device__ inline void ctx_init(FusedCtx& c, const smi_ppo_args& args, float* sm
 // actor forward of one 64-row tile into the policy buffers
 // Every epoch-loop helper is force-inlined: an out-of-line call passes the
 // context structs through scratch and saves/restores registers around it.
-#ifndef SMI_INL
 #define SMI_INL __device__ __attribute__((always_inline))
-#endif
 
 SMI_INL void policy_fwd_tile(const FusedCtx& c, const MlpView& V, int tile,
                                 const float* zm, const float* zs) {

@@ -550,12 +550,10 @@ static bool try_gae_seg(const GaeWinArgs& a, int* n_partials, hipStream_t stream
   static int cap = 0;
   if (!cap) {
     cap = resident_grid(k, SEG, G::LDS);
-    if (cap > 1024) cap = 1024;
-    // SMI_GAE_GRID: workgroups of the grid-stride loop (each block's loads
-    // prefetched behind the previous block's rows; A/B knob)
-    const char* e = getenv("SMI_GAE_GRID");
-    const int g = e && e[0] ? atoi(e) : 0;
-    if (g > 0 && g < cap) cap = g;
+    // workgroups of the grid-stride loop (each block's loads prefetched behind
+    // the previous block's rows)
+    constexpr int kGaeGrid = 1024;
+    if (cap > kGaeGrid) cap = kGaeGrid;
   }
   const int grid = (int)(nblk < cap ? nblk : cap);
   hipLaunchKernelGGL(k, dim3(grid), dim3(SEG), G::LDS, stream, a, nblk);
@@ -653,10 +651,8 @@ int launch_gae_windows(const float* values, float* values_masked, const float* r
     // the reference defaults: RNN n_step 25 / horizon 5; non-RNN n_step 50
     // 64-segment workgroups (19.5 KB of LDS, one wave: several resident per
     // CU, so one block's stores overlap another's loads; 16 blocks at C3
-    // instead of 4); SMI_GAE_SEG=256: the round-5 256-segment blocks (A/B)
-    static const int seg = [] { const char* e = getenv("SMI_GAE_SEG"); return e && atoi(e) == 256 ? 256 : 64; }();
-    if (seg == 64 && try_gae_seg<25, 5, 64>(a, n_partials, stream, &rc)) return rc;
-    if (try_gae_seg<25, 5, 256>(a, n_partials, stream, &rc)) return rc;
+    // instead of 4)
+    if (try_gae_seg<25, 5, 64>(a, n_partials, stream, &rc)) return rc;
     if (try_gae_seg<50, 50, 128>(a, n_partials, stream, &rc)) return rc;
   }
   if (T + 1 <= 64 && (a.E == 1 || H <= 16) && (!faulted || a.H <= 16)) {

@@ -8,7 +8,6 @@
 // inputs.  Data-dependent control (KL early stop, adapt penalty branch) is a
 // device flag that turns later phases into no-ops: the host issues the same
 // launches on every call and every rank, and never waits for the device.
-#include <stdlib.h>
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "pol_rows.hpp"
@@ -109,13 +108,6 @@ static int64_t part_doubles(const RnnDims& d) {
   const int64_t v = 5 * (int64_t)head_bwd_blocks(d.NE);
   return v > 65536 ? v : 65536;
 }
-// the last value epoch's statistics from the critic head forward's epilogue
-// (SMI_VALUE_STATS_HEAD=0: value_rows_kernel; A/B knob)
-static bool use_value_stats_head() {
-  static const bool on = [] { const char* e = getenv("SMI_VALUE_STATS_HEAD"); return !(e && e[0] == '0'); }();
-  return on;
-}
-
 static RnnScratch rnn_scratch(const RnnDims& d, void* base) {
   RnnScratch s{};
   float* p = static_cast<float*>(base);
@@ -650,7 +642,7 @@ __global__ void __launch_bounds__(kWG)
 row_pack_kernel(PolRowArgs a, float* __restrict__ rowin, float* __restrict__ ret_tm) {
   constexpr int AM = AT > 0 ? AT : 32;
   const int A = AT > 0 ? AT : a.A;
-  float lrsig[AM], s02[AM];                        // PolStatsCols' reference-std terms
+  float lrsig[AM], s02[AM];                        // the reference std's per-column terms
 #pragma unroll
   for (int j = 0; j < (AT > 0 ? AT : A); ++j) {
     const float rsig = expf(a.ref_lv[j]);
@@ -1172,63 +1164,13 @@ __global__ void rnn_final_kernel(FinalArgs a) {
 // workgroups of the statistics pass: at most one resident round (its register
 // count leaves 3 one-wave blocks per SIMD, so the 4096-block cap of rnn_nblk
 // ran a second, partly filled round: 0.34 of HBM at 65536 segments)
-// adapt mode, 8 actions: the statistics pass with its per-column terms in
-// LDS and one row in flight per thread (168 -> 118 VGPRs: four waves per SIMD
-// instead of three, to cover the rows' cold HBM reads)
-template <int NT>
-__global__ void __launch_bounds__(NT)
-policy_rows_stats_lean_kernel(PolRowArgs a) {
-  if (a.skip && a.skip[0] != 0) return;
-  constexpr int AT = 8;
-  __shared__ PolStatsColsLds sc;
-  __shared__ double scr[NT / 64][PS_N];
-  pol_stats_cols_fill(sc, a.lv, a.ref_lv, AT);
-  __syncthreads();
-  double acc[PS_N];
-#pragma unroll
-  for (int k = 0; k < PS_N; ++k) acc[k] = 0.0;
-  const int64_t N = (int64_t)a.E * a.B;
-  const AdvNorm nadv(a);
-  for (int64_t n = (int64_t)blockIdx.x * NT + threadIdx.x; n < N; n += (int64_t)gridDim.x * NT) {
-    float m[AT], rm[AT], ac[AT];
-    ld_row<AT>(m, a.mu + n * AT, AT);
-    ld_row<AT>(rm, a.refmu + n * AT, AT);
-    ld_fields<AT>(ac, a.rowin, N, n, 0, AT);
-    const float adv = a.rowin[rin_idx(row_w(AT), n, rin_adv(AT))];
-    const float bl = a.rowin[rin_idx(row_w(AT), n, rin_bl(AT))];
-    const float rbd = a.rowin[rin_idx(row_w(AT), n, rin_rbd(AT))];
-    pol_stats_row_adapt<AT>(a, sc, nadv, m, rm, ac, bl, rbd, adv, a.ret_tm[n], acc);
-  }
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < PS_N; ++k) {
-    const double v = wave_sum_d(acc[k]);
-    if (lane == 0) scr[wave][k] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x < PS_N) {
-    double t = 0.0;
-#pragma unroll
-    for (int w = 0; w < NT / 64; ++w) t += scr[w][threadIdx.x];
-    a.part[(int64_t)blockIdx.x * PS_N + threadIdx.x] = t;
-  }
-}
-
-// off unless SMI_STATS_LEAN=1: at 65536 segments 0.381 vs 0.377 of HBM (the
-// pass reads its rows cold either way)
-static bool use_stats_lean() {
-  static const bool on = [] { const char* e = getenv("SMI_STATS_LEAN"); return e && e[0] == '1'; }();
-  return on;
-}
-
 template <bool FUSE>
 static int pol_stats_blocks(int A, int64_t rows) {
   static int cap[2][9] = {};
   const int ai = A >= 1 && A <= 8 ? A : 0;
   int& c = cap[FUSE][ai];
   if (!c) {
-    if (!FUSE && ai == 8 && use_stats_lean()) c = resident_grid(policy_rows_stats_lean_kernel<kRowNT>, kRowNT, 0);
-    else switch (ai) {
+    switch (ai) {
       case 1: c = resident_grid(policy_rows_stats_kernel<kRowNT, 1, FUSE>, kRowNT, 0); break;
       case 2: c = resident_grid(policy_rows_stats_kernel<kRowNT, 2, FUSE>, kRowNT, 0); break;
       case 3: c = resident_grid(policy_rows_stats_kernel<kRowNT, 3, FUSE>, kRowNT, 0); break;
@@ -1247,10 +1189,6 @@ static int pol_stats_blocks(int A, int64_t rows) {
 
 template <bool FUSE>
 static void launch_pol_stats(int A, int nb, const PolRowArgs& p, hipStream_t st) {
-  if (!FUSE && A == 8 && use_stats_lean()) {
-    hipLaunchKernelGGL((policy_rows_stats_lean_kernel<kRowNT>), dim3(nb), dim3(kRowNT), 0, st, p);
-    return;
-  }
   switch (A) {   // compile-time action widths 1..8 (registers); others generic
     case 1: hipLaunchKernelGGL((policy_rows_stats_kernel<kRowNT, 1, FUSE>), dim3(nb), dim3(kRowNT), 0, st, p); break;
     case 2: hipLaunchKernelGGL((policy_rows_stats_kernel<kRowNT, 2, FUSE>), dim3(nb), dim3(kRowNT), 0, st, p); break;
@@ -1305,19 +1243,13 @@ static int launch_zf_tmajor(const float* obs, const float* obs_next, int B, int 
                       2 * ((size_t)round4(kZfSeg * T * D) + round4(kZfSeg * D))) * 4;
   const bool pipe_ok = pad4_ok && kZfSeg * T * D <= 4 * kZfNR * kWG && kZfSeg * D <= 4 * kWG &&
                        tlp <= 150 * 1024;
-  // SMI_ZF_PIPE=0: the one-shot padded-row tile (A/B)
-  static const bool pipe_on = [] { const char* e = getenv("SMI_ZF_PIPE"); return !(e && e[0] == '0'); }();
-  static const bool tile_on = [] { const char* e = getenv("SMI_ZF_TILE"); return !(e && e[0] == '0'); }();
-  static const bool force = [] { const char* e = getenv("SMI_ZF_TILE_FORCE"); return e && e[0] == '1'; }();
-  // SMI_ZF_TILE4=0: the float2 tile (A/B)
-  static const bool t4_on = [] { const char* e = getenv("SMI_ZF_TILE4"); return !(e && e[0] == '0'); }();
   if (form == 0) {
     // (from 4096 segments: at C3's 1024 the 128 tile workgroups took 14.5 us
     // against 9.7 for the row kernel; at 65536, 146 against 169 us)
     form = 1;
-    if (tile_on && (B >= 4096 || force)) {
-      if (t4_on && pad_ok && pipe_on && pipe_ok) form = 4;
-      else if (t4_on && pad_ok && pad4_ok) form = 5;
+    if (B >= 4096) {
+      if (pad_ok && pipe_ok) form = 4;
+      else if (pad_ok && pad4_ok) form = 5;
       else if (tile_ok) form = 2;
       else if (tile4_ok) form = 3;
     }
@@ -1372,9 +1304,7 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
                           const float* W3, const float* b3, int out, int tanh_out, float* HA1,
                           float* HA2, float* Y, int64_t ldy, float* W1T, float* W2T,
                           hipStream_t st, const int* skip, const float* vret = nullptr,
-                          float* vgrad = nullptr, float vscale = 0.f,
-                          const PolRowArgs* ps = nullptr, double* vpart = nullptr);
-bool head_fwd_ps_ok(int h1, int h2, int out);
+                          float* vgrad = nullptr, float vscale = 0.f, double* vpart = nullptr);
 int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W3,
                           const float* W2T, const float* W1T, int h1, int h2, int dx0, int dxn,
                           const float* HA1, const float* HA2, float* dH2, float* dH1, float* dX,
@@ -1392,12 +1322,10 @@ static bool head_fused(const Head& h, const float* X, int64_t ldx) {
 // for a fused backward of the same parameters
 // vret / vgrad / vscale: the value-loss gradient written by the fused forward
 // (out == 1); *vdone tells whether it was (the layer-GEMM path does not)
-// ps: the policy statistics epilogue (the fused path only: head_fwd_ps_ok)
 static int head_fwd(const Head& h, const float* X, int64_t ldx, int64_t rows, float* HA1,
                     float* HA2, float* Y, hipStream_t st, const int* skip, float* wT = nullptr,
                     const float* vret = nullptr, float* vgrad = nullptr, float vscale = 0.f,
-                    bool* vdone = nullptr, const PolRowArgs* ps = nullptr,
-                    double* vpart = nullptr, bool keep_act = true) {
+                    bool* vdone = nullptr, double* vpart = nullptr, bool keep_act = true) {
   const MlpLayout& L = h.L;
   if (vdone) *vdone = false;
   if (head_fused(h, X, ldx)) {
@@ -1411,10 +1339,9 @@ static int head_fwd(const Head& h, const float* X, int64_t ldx, int64_t rows, fl
     return launch_head_fwd_fused(X, ldx, rows, h.in, h.P + L.fW1, h.P + L.fb1, h.h1, h.P + L.fW2,
                                  h.P + L.fb2, h.h2, h.P + L.fW3, h.P + L.fb3, h.out, h.tanh_out,
                                  HA1, HA2, Y, h.out, wT, wT ? wT + (int64_t)h.in * h.h1 : nullptr,
-                                 st, skip, ve ? vret : nullptr, ve ? vgrad : nullptr, vscale, ps,
+                                 st, skip, ve ? vret : nullptr, ve ? vgrad : nullptr, vscale,
                                  ve ? vpart : nullptr);
   }
-  if (ps) return set_error(SMI_E_ARG, "head_forward: the statistics epilogue needs the fused head");
   const int M = (int)rows;
   RC(launch_linear_fwd(X, ldx, M, h.in, h.P + h.L.fW1, h.in, h.P + h.L.fb1, h.h1, ACT_RELU, HA1,
                        h.h1, st, skip));
@@ -1537,7 +1464,6 @@ static int lstm_backward(const RnnDims& d, const float* P, float* G, const RnnSc
                          hipStream_t st, const int* skip) {
   const int64_t BH = (int64_t)d.B * d.H;
   const int M = (int)d.NE;
-  static const int fused = [] { const char* e = getenv("SMI_LSTM_DW2"); return e ? atoi(e) : 1; }();
   for (int l = d.L - 1; l >= 0; --l) {
     const LstmP lp = lstm_layer(d, P, l);
     float* dg = dgates_of(d, s, l);
@@ -1563,15 +1489,10 @@ static int lstm_backward(const RnnDims& d, const float* P, float* G, const RnnSc
     float* gWhh = gWih + (int64_t)4 * d.H * din;
     float* gbih = gWhh + (int64_t)4 * d.H * d.H;
     float* gbhh = gbih + d.G4;
-    if (!fused) {     // A/B: the two launches over the layer input and hbuf
-      RC(launch_linear_bwd_dw(dg, d.G4, M, d.G4, Xl, ldx, din, gWih, din, gbih, 0, st, skip));
-      RC(launch_linear_bwd_dw(dg, d.G4, M, d.G4, hb, d.H, d.H, gWhh, d.H, gbhh, 0, st, skip));
-    } else {
-      // W_ih over x_t, W_hh over h_{t-1} (hbuf[0..E-1], hbuf[0] = h0) and the
-      // shared bias gradient in ONE launch over [x_t | h_{t-1}]
-      RC(launch_linear_bwd_dw2(dg, d.G4, M, d.G4, Xl, ldx, din, hb, d.H, d.H, gWih, din, gWhh,
-                               d.H, gbih, gbhh, st, skip));
-    }
+    // W_ih over x_t, W_hh over h_{t-1} (hbuf[0..E-1], hbuf[0] = h0) and the
+    // shared bias gradient in ONE launch over [x_t | h_{t-1}]
+    RC(launch_linear_bwd_dw2(dg, d.G4, M, d.G4, Xl, ldx, din, hb, d.H, d.H, gWih, din, gWhh,
+                             d.H, gbih, gbhh, st, skip));
     if (l > 0)        // dh of layer l-1's outputs (steps 1..E) = dgates_l W_ih_l
       RC(launch_linear_bwd_dx(dg, d.G4, M, d.G4, lp.Wih, d.H, d.H, nullptr, 0, s.dh, d.H, st, skip));
   }
@@ -1682,8 +1603,7 @@ static PolRowArgs pol_rows(const smi_ppo_rnn_args& a, const RnnDims& d, const Rn
 // (dw_group_takes: heads wider than 511 or 4H > 512 run outside it); the flush
 // also fails loudly if one ran outside an open bracket with the fused norm.
 static bool fused_clip_norm(const smi_ppo_rnn_args& a, const RnnDims& d) {
-  static const bool off = [] { const char* e = getenv("SMI_FUSED_NORM"); return e && e[0] == '0'; }();
-  if (off || a.B_global != a.B || d.F != 0 || d.L > 3 || fault() != 0) return false;
+  if (a.B_global != a.B || d.F != 0 || d.L > 3 || fault() != 0) return false;
   const bool heads = dw_group_takes(d.h1, d.Hin + 1) && dw_group_takes(d.h2, d.h1 + 1) &&
                      dw_group_takes(d.A, d.h2 + 1) && dw_group_takes(d.c1, d.Hin + 1) &&
                      dw_group_takes(d.c2, d.c1 + 1) && dw_group_takes(1, d.c2 + 1);
@@ -1698,57 +1618,37 @@ static bool fused_clip_norm(const smi_ppo_rnn_args& a, const RnnDims& d) {
 // segments, PREP issued after GAE on the same stream (a.prep_independent == 0:
 // the caller's explicit statement, no environment read here); GAE then also
 // forms PREP's z-filtered input and PREP runs the reference head only.
-// SMI_GAE_DUAL=0: two launches (A/B knob)
 static bool gae_prep_dual(const smi_ppo_rnn_args& a, const RnnDims& d) {
-  static const bool off = [] { const char* e = getenv("SMI_GAE_DUAL"); return e && e[0] == '0'; }();
-  return !off && a.prep_independent == 0 && d.H > 0 && d.L == 1 && d.F == 0 &&
+  return a.prep_independent == 0 && d.H > 0 && d.L == 1 && d.F == 0 &&
          lstm_fwd_x_dual_fits(d.B, d.B, d.S1 > d.E ? d.S1 : d.E, d.H, d.Din);
 }
 
 // adapt mode with the LSTM stem, 8 actions and the fused head chain at a
 // rank's batch (< 16384 rows: one row tile per workgroup): the policy-gradient
-// row pass runs as that chain's prologue (head_kernels.hip, pol_rows.hpp;
-// SMI_POL_HEAD=0: its own launch, 1: at any batch; A/B knob); one log_var
+// row pass runs as that chain's prologue (head_kernels.hip, pol_rows.hpp); one log_var
 // partial per chain workgroup (<= the 4096 of s.lvpart).  Measured: 128
 // segments 2.947 -> 2.929 ms per learn; 1024 segments 6.98 -> 7.05 ms (the
 // 32-row workgroups' serial prologue costs more than the launch it saves)
 static bool pol_head_grad(const smi_ppo_rnn_args& a, const RnnDims& d, const RnnScratch& s,
                           const Head& actor) {
-  static const int knob = [] { const char* e = getenv("SMI_POL_HEAD"); return e && e[0] ? atoi(e) : -1; }();
-  if (knob == 0) return false;
-  return a.mode != 0 && d.H > 0 && d.A == 8 && d.H <= 320 && (knob == 1 || d.NE < 16384) &&
+  return a.mode != 0 && d.H > 0 && d.A == 8 && d.H <= 320 && d.NE < 16384 &&
          head_fused(actor, head_in(d, s, s.Xz), d.Hld) && head_bwd_blocks(d.NE) <= 4096;
 }
 
-// adapt mode, 8 actions, 300 x 200-class heads on the fused path: the policy
-// statistics row pass as the head forward's epilogue (one launch fewer per
-// policy epoch); one PS_N partial per head workgroup (<= 4096 of them).  Off
-// unless SMI_POL_STATS_HEAD=1 (A/B knob): measured 2.933 vs 2.928 ms at 128
-// segments, 6.986 vs 6.999 ms at C3 — the workgroups' serial row epilogue
-// (+6 / +10 us per forward) costs what the launch it removes did
-static bool pol_head_stats(const smi_ppo_rnn_args& a, const RnnDims& d, const RnnScratch& s,
-                           const Head& actor) {
-  static const bool on = [] { const char* e = getenv("SMI_POL_STATS_HEAD"); return e && e[0] == '1'; }();
-  return on && a.mode != 0 && d.A == 8 && head_fwd_ps_ok(d.h1, d.h2, d.A) &&
-         head_fused(actor, head_in(d, s, s.Xz), d.Hld) && head_bwd_blocks(d.NE) <= 4096;
-}
-// the partials the policy statistics pass wrote (its grid, or the head's)
-static int pol_stats_nb(const smi_ppo_rnn_args& a, const RnnDims& d, const RnnScratch& s,
-                        const Head& actor) {
-  if (a.mode == 0) return pol_stats_blocks<true>(d.A, d.NE);
-  return pol_head_stats(a, d, s, actor) ? head_bwd_blocks(d.NE) : pol_stats_blocks<false>(d.A, d.NE);
+// the partials the policy statistics pass wrote (its grid)
+static int pol_stats_nb(const smi_ppo_rnn_args& a, const RnnDims& d) {
+  return a.mode == 0 ? pol_stats_blocks<true>(d.A, d.NE) : pol_stats_blocks<false>(d.A, d.NE);
 }
 
 // adapt mode, one rank, a policy epoch that trains: the decision of POLICY_FWD
 // (early stop, KL coefficient, statistics) is taken by the gradient pass of
 // POLICY_BWD itself (policy_rows_grad_kernel, dec_part)
-static bool fused_decide(const smi_ppo_rnn_args& a, const RnnDims& d, const RnnScratch& s,
-                         const Head& actor, int e) {
+static bool fused_decide(const smi_ppo_rnn_args& a, const RnnDims& d, int e) {
   // every gradient workgroup re-reduces the statistics pass's partials: only
   // while they are few (at 65536 segments, ~3000 partials per workgroup over
   // ~4000 workgroups took the gradient pass from 47 to 103 us)
   return a.mode != 0 && a.B_global == a.B && e < a.epoch_policy && fault() == 0 &&
-         pol_stats_nb(a, d, s, actor) <= 512;
+         pol_stats_nb(a, d) <= 512;
 }
 
 int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
@@ -1797,7 +1697,7 @@ int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
         RC(lstm_forward(d, a.lstm, s.Xz, d.S1, a.h0, a.c0, s, true, st, nullptr, d.E));
       }
       RC(head_fwd(critic, head_in(d, s, s.Xz), d.Hld, d.NG, s.HA1, s.HA2, s.OUT, st, nullptr,
-                  nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, false));
+                  nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, false));
       hipLaunchKernelGGL(tmajor_to_bmajor_kernel, dim3(grid_of(d.NG)), dim3(kWG), 0, st, s.OUT,
                          d.S1, d.B, s.values, s.ci, s.cf);
       RC(check_launch("tmajor_to_bmajor_kernel"));
@@ -1830,7 +1730,7 @@ int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
       }
       const Head ref{a.ref_actor, d.LA, d.Hin, d.h1, d.h2, d.A, 1};
       return head_fwd(ref, head_in(d, sp, X), d.Hld, d.NE, sp.HA1, sp.HA2, s.refmu, st,
-                      nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, nullptr, false);
+                      nullptr, nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, false);
     }
     case SMI_RNN_PH_POLICY_FWD: {
       if (e == 0) {
@@ -1846,23 +1746,19 @@ int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
       if (d.H > 0 && e > 0) RC(lstm_forward(d, a.lstm, s.Xz, d.E, a.h0, a.c0, s, true, st, stop));
       PolRowArgs p = pol_rows(a, d, s);
       p.invN = (float)(1.0 / (double)NEg);
-      const bool hs = pol_head_stats(a, d, s, actor);
       // (the KL check after the last update, e == epoch_policy, has no backward:
       // neither the activations nor the weight transposes are kept)
       const bool bwd_next = e < a.epoch_policy;
       RC(head_fwd(actor, head_in(d, s, s.Xz), d.Hld, d.NE, s.HA1, s.HA2, s.OUT, st, stop,
-                  bwd_next ? s.wT : nullptr, nullptr, nullptr, 0.f, nullptr, hs ? &p : nullptr,
-                  nullptr, bwd_next));
-      const int nb = pol_stats_nb(a, d, s, actor);
-      if (!hs) {
-        const int kt = ktime_begin(st);
-        if (a.mode == 0) launch_pol_stats<true>(d.A, nb, p, st);     // + the clip gradient
-        else launch_pol_stats<false>(d.A, nb, p, st);
-        // per row: mu, refmu, actions (3A) + adv, ret, bl, rbd (4) floats read
-        ktime_end(kt, KT_POLICY_STATS, 4.0 * (double)d.NE * (3 * d.A + 4), st);
-        RC(check_launch("policy_rows_stats_kernel"));
-      }
-      if (fused_decide(a, d, s, actor, e)) return SMI_OK;     // decided by POLICY_BWD's gradient pass
+                  bwd_next ? s.wT : nullptr, nullptr, nullptr, 0.f, nullptr, nullptr, bwd_next));
+      const int nb = pol_stats_nb(a, d);
+      const int kt = ktime_begin(st);
+      if (a.mode == 0) launch_pol_stats<true>(d.A, nb, p, st);     // + the clip gradient
+      else launch_pol_stats<false>(d.A, nb, p, st);
+      // per row: mu, refmu, actions (3A) + adv, ret, bl, rbd (4) floats read
+      ktime_end(kt, KT_POLICY_STATS, 4.0 * (double)d.NE * (3 * d.A + 4), st);
+      RC(check_launch("policy_rows_stats_kernel"));
+      if (fused_decide(a, d, e)) return SMI_OK;     // decided by POLICY_BWD's gradient pass
       if (a.B_global == a.B) {         // one rank: nothing to exchange before the decision
         DecideArgs da{a.pstat, e, a.epoch_policy, a.mode,
                       a.kl_target, a.kl_cutoff_coeff, NEg, a.hyper, a.actor + d.LA.flv, d.A,
@@ -1887,9 +1783,9 @@ int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
       PolRowArgs p = pol_rows(a, d, s);
       // clip: the log_var partials came from POLICY_FWD's fused pass, over its grid
       const int nb = a.mode == 0 ? pol_stats_blocks<true>(d.A, d.NE) : rnn_nblk(d.NE, kRowNT);
-      if (fused_decide(a, d, s, actor, e)) {
+      if (fused_decide(a, d, e)) {
         p.dec_part = s.part;
-        p.dec_nb = pol_stats_nb(a, d, s, actor);
+        p.dec_nb = pol_stats_nb(a, d);
         p.dec = DecideArgs{a.pstat, e, a.epoch_policy, a.mode,
                            a.kl_target, a.kl_cutoff_coeff, NEg, a.hyper, a.actor + d.LA.flv, d.A,
                            c_entropy_of(d.A), s.ci, s.cf, a.stats};
@@ -1967,11 +1863,11 @@ int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st) {
       const bool last = e == a.epoch_baseline - 1;
       const float vscale = (float)(2.0 / (double)NEg);
       bool vdone = false;
-      const bool vstats = last && use_value_stats_head() &&
+      const bool vstats = last &&
                           5 * (int64_t)head_bwd_blocks(d.NE) <= part_doubles(d);
       RC(head_fwd(critic, head_in(d, s, s.Xz), d.Hld, d.NE, s.HA1, s.HA2, s.OUT, st, nullptr,
                   s.wT, last && !vstats ? nullptr : s.ret_tm, last && !vstats ? nullptr : s.dOUT,
-                  vscale, &vdone, nullptr, vstats ? s.part : nullptr));
+                  vscale, &vdone, vstats ? s.part : nullptr));
       int nb = rnn_nblk((d.NE + 3) / 4, kRowNT);           // 4 rows per thread
       if (vdone && vstats) nb = head_bwd_blocks(d.NE);     // the head forward's partials
       if (!vdone) {

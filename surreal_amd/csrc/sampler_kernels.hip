@@ -257,14 +257,9 @@ int launch_gather_rows(const float* table, int64_t cols, const int64_t* idx, int
 // 333,333 x 63,504 B, is 21 GB per side).  Items are dealt to a capped 1-D
 // grid.  The float side rows follow in the same launch through gather_body.
 //
-// SMI_RG_NT (developer A/B, build.py variants rgnt1-3): nontemporal loads (bit
-// 0) and / or stores (bit 1).  The product is plain loads and stores (B = 512
-// of 9 x 84 x 84, one MI355X: plain 25.8-26.0 us, loads 26.3, stores 28.5, both
-// 27.7): the frames are read by the conv forward right after
-// this launch.
-#ifndef SMI_RG_NT
-#define SMI_RG_NT 0
-#endif
+// Plain loads and stores (B = 512 of 9 x 84 x 84, one MI355X: plain 25.8-26.0
+// us, nontemporal loads 26.3, stores 28.5, both 27.7): the
+// frames are read by the conv forward right after this launch.
 constexpr int kRgU = 4;
 constexpr int kRgChunk = kWG * kRgU;   // 16-byte vectors (VEC) or bytes x 16 per work item
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
@@ -322,16 +317,12 @@ replay_gather_kernel(const float* __restrict__ table, int64_t cols,
 #pragma unroll
       for (int u = 0; u < kRgU; ++u) {
         const int e = min(v0 + u * kWG, nvec - 1);
-        if constexpr ((SMI_RG_NT & 1) != 0) v[u] = __builtin_nontemporal_load(s4 + e);
-        else v[u] = s4[e];
+        v[u] = s4[e];
       }
 #pragma unroll
       for (int u = 0; u < kRgU; ++u) {
         const int e = v0 + u * kWG;
-        if (e < nvec) {
-          if constexpr ((SMI_RG_NT & 2) != 0) __builtin_nontemporal_store(v[u], d4 + e);
-          else d4[e] = v[u];
-        }
+        if (e < nvec) d4[e] = v[u];
       }
     } else {
       const int64_t b0 = chunk * kRgChunk * 16;

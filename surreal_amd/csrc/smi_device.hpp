@@ -85,13 +85,7 @@ __device__ __forceinline__ float block_sum_f(float v, double* scratch) {
 }
 
 // --------------------------------------------------------------- dense layers
-// SMI_DENSE_NOINLINE (developer variant) emits each dense helper once instead of
-// inlining it at every call site: smaller code, at the price of call overhead.
-#ifdef SMI_DENSE_NOINLINE
-#define SMI_DENSE __device__ __attribute__((noinline))
-#else
 #define SMI_DENSE __device__
-#endif
 // Forward: Y[r][n] = act(b[n] + sum_k X[r][k] * W[n][k]),  r in [0,64), n in [0,N)
 //   X: LDS [64][ldx], columns [K, round4(K)) must be zero (finite).
 //   W: [N][ldw] row-major (k contiguous) in LDS or global; b: [N].

@@ -23,7 +23,6 @@ with use_layernorm):
   critic: Wo[c1][D] bo [go bo'] Wc[c2][c1+A] bc [gc bc'] Wq[1][c2] bq
 """
 import math
-import os
 
 import numpy as np
 import torch
@@ -33,9 +32,6 @@ from . import _lib as L
 from .session import LearnerHooks
 from .config import Config, ConfigError
 from .model import CNNStemNetwork, _FlatViews, _LinearView
-
-# group each backward's weight-gradient GEMMs into one launch (SMI_DDPG_DW_GROUP=0: A/B off)
-_DW_GROUP = os.environ.get('SMI_DDPG_DW_GROUP', '1') != '0'
 
 RELU, TANH, NONE = 1, 2, 0
 
@@ -604,7 +600,7 @@ class DDPGLearner(LearnerHooks):
         cnn = (model, pixels, perception store, gradient) continues through the
         model's perception (pixel inputs).  Always returns d loss / d action
         (B, A) when g is None."""
-        if g is None or not _DW_GROUP:
+        if g is None:
             return self._critic_backward_body(net, crit, obs, B, dq, pre, g, st, cnn)
         L.call('smi_dw_group_begin')
         try:
@@ -656,8 +652,6 @@ class DDPGLearner(LearnerHooks):
     def _actor_backward(self, net, act, obs, B, dA, g, st):
         """Backward through ActorNetworkX into g; its three weight-gradient
         GEMMs as one grouped launch (smi_dw_group_*)."""
-        if not _DW_GROUP:
-            return self._actor_backward_body(net, act, obs, B, dA, g, st)
         L.call('smi_dw_group_begin')
         try:
             self._actor_backward_body(net, act, obs, B, dA, g, st)

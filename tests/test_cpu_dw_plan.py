@@ -17,7 +17,7 @@ NS = (16, 79, 91, 101, 128, 143, 201, 301)
 KS = (513, 1100, 21504)
 SLOTS = 768                      # 256 CUs x 3 resident workgroups (the C3 launch)
 CAP = 1 << 26                    # floats of workspace
-RED_BLOCK = 256                  # elements per reducer block (64 x SMI_RED_U, default 4)
+RED_BLOCK = 256                  # elements per reducer block (64 x 4)
 F = ('gi', 'm0', 'n0', 'M', 'N', 'mt', 'nt', 'kchunk', 'S', 'wg0', 'rb0', 'part_off')
 
 

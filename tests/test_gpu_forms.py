@@ -196,7 +196,7 @@ def test_lstm_forms(big, S, D, H, pad, f_fwd, f_fwdx, f_bwd):
 
 
 def _fwd_v_lds(S, kx, blk):
-    """lstm_fwd_v_lds (lstm_kernels.hip) at one segment per workgroup: bytes of
+    """lstm_fwd_v_lds (lstm_cell.hpp) at one segment per workgroup: bytes of
     the staged x sequence + the x parts."""
     return (((S * kx + 3) & ~3) + S * blk) * 4
 

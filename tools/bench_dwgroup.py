@@ -81,71 +81,6 @@ def main():
     torch.cuda.synchronize()
     t = sorted(s.elapsed_time(e) for s, e in ev)
     ms = t[len(t) // 2]
-    if (os.environ.get('SMI_LIB_VARIANT') or '').startswith('dwtrace'):
-        # one more phase, then the per-workgroup clock trace of its dW launch
-        import ctypes
-        import numpy as np
-        phase()
-        torch.cuda.synchronize()
-        buf = np.zeros((8192, 6), dtype=np.uint64)
-        n = L.lib().smi_diag_dw_trace(ctypes.c_void_p(buf.ctypes.data), 8192)
-        tr = buf[:n]
-        tr = tr[tr[:, 1] > 0]
-        t0 = tr[:, 0].min()
-        st_, en = (tr[:, 0] - t0) / 100.0, (tr[:, 1] - t0) / 100.0      # us (100 MHz)
-        dur = en - st_
-        gi = ((tr[:, 3] >> 8) & 0xFF).astype(int)
-        rows = ((tr[:, 3] >> 16) & 0xFFFF).astype(int)
-        # the entry's tile class (dw_cls): MT x NT sub-tiles, 16-byte A / B loads
-        mt = ((tr[:, 3] >> 32) & 7).astype(int)
-        nt = ((tr[:, 3] >> 35) & 15).astype(int)
-        vec = (2 * ((tr[:, 3] >> 39) & 1) + ((tr[:, 3] >> 40) & 1)).astype(int)
-        narrow = (mt * nt < 16).astype(int)
-        xcc = (tr[:, 3] & 0xF).astype(int)
-        cu = ((tr[:, 2] >> 8) & 0xF).astype(int) + 16 * ((tr[:, 2] >> 13) & 0x7).astype(int)
-        grid = np.arange(0.0, float(en.max()) + 1.0, 1.0)
-        conc = [int(((st_ <= x) & (en > x)).sum()) for x in grid]
-        clk = (tr[:, 5] - tr[:, 4]).astype(np.float64) / np.maximum(dur, 1e-3) / 1e3   # GHz
-        # residency: workgroups per CU at 20 us, and durations by that count
-        key = xcc * 64 + cu
-        at = (st_ <= 20.0) & (en > 20.0)
-        per_cu = np.bincount(key[at], minlength=512)
-        cnt = per_cu[key]
-        # work per workgroup in full-tile rows (a class priced 0.2 + 0.8 MT NT / 16 of a full tile),
-        # and us per 1000 of them
-        work = rows * np.where(narrow == 1, 0.2 + 0.8 * mt * nt / 16.0, 1.0)
-        # per tile class: workgroups, slab rows, median us and us per 1000 rows (the
-        # measured cost of a class is its us_per_krow over the 4x4 class's)
-        per_class = {}
-        for m_, n_ in sorted(set(zip(mt.tolist(), nt.tolist()))):
-            sel = (mt == m_) & (nt == n_)
-            per_class[f'{m_}x{n_}'] = {
-                'wgs': int(sel.sum()), 'rows_med': int(np.median(rows[sel])),
-                'dur_med_us': round(float(np.median(dur[sel])), 1),
-                'us_per_krow': round(float(np.median(1e3 * dur[sel] / np.maximum(rows[sel], 1))), 2)}
-        full = per_class.get('4x4', {}).get('us_per_krow')
-        if full:
-            for v in per_class.values():
-                v['cost_vs_4x4'] = round(v['us_per_krow'] / full, 3)
-        out_extra = {
-            'wgs_per_cu_at_20us_hist': {int(k): int(v) for k, v in enumerate(np.bincount(per_cu[per_cu > 0]))},
-            'dur_med_by_cu_count': {int(k): round(float(np.median(dur[at & (cnt == k)])), 1)
-                                    for k in np.unique(cnt[at])},
-            'slab_rows_by_group': {int(k): sorted(set(int(r) for r in rows[gi == k]))[:4] for k in np.unique(gi)},
-            'us_per_krow_p10_50_90': [round(float(np.percentile(1e3 * dur / np.maximum(work, 1), q)), 2)
-                                      for q in (10, 50, 90)],
-            'vec_by_group': {int(k): int(np.median(vec[gi == k])) for k in np.unique(gi)},
-            'narrow_wgs': int(narrow.sum()), 'per_class': per_class}
-        out = {**out_extra, 'clock_ghz_p10_50_90': [round(float(np.percentile(clk, q)), 3) for q in (10, 50, 90)],
-               'trace_wgs': int(len(tr)), 'span_us': round(float(en.max()), 1),
-               'dur_us_p10_50_90_max': [round(float(np.percentile(dur, q)), 1) for q in (10, 50, 90, 100)],
-               'start_us_p50_90_max': [round(float(np.percentile(st_, q)), 1) for q in (50, 90, 100)],
-               'per_group_dur_med': {int(k): round(float(np.median(dur[gi == k])), 1) for k in np.unique(gi)},
-               'per_group_wgs': {int(k): int((gi == k).sum()) for k in np.unique(gi)},
-               'per_xcc_wgs': {int(k): int((xcc == k).sum()) for k in np.unique(xcc)},
-               'max_wgs_per_xcc_cu': int(np.bincount(xcc * 64 + cu).max()),
-               'concurrency_every_5us': conc[::5]}
-        print(json.dumps(out), flush=True)
     print(json.dumps({'bench': 'dw_group', 'rows': R, 'ms': round(ms, 4), 'gflop': round(fl / 1e9, 3),
                       'tflops': round(fl / ms / 1e9, 2), 'frac_f32_mfma': round(fl / ms / 1e9 / 157.3, 3)}),
           flush=True)

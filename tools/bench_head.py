@@ -1,9 +1,8 @@
 """Timing of the fused head passes (smi_head_forward / smi_head_backward_input)
 at the learner's shapes: LSTM 100 -> 300 -> 200 -> 8 (policy, tanh) over
 21504 rows (C3 policy epochs), -> 1 over 26624 rows (the GAE critic pass) and
-2688 rows (one rank of N = 8).  The kernel choice comes from the environment
-(SMI_HEAD_T, SMI_HEAD_FQ: read once per process), so A/B arms run as separate
-processes.  Prints one JSON line per (pass, shape): median us and TF/s.
+2688 rows (one rank of N = 8).  Prints one JSON line per (pass, shape): median
+us and TF/s, tagged with --tag.
 Usage: python tools/bench_head.py [--iters 50] [--tag NAME]"""
 import argparse
 import json
@@ -37,8 +36,7 @@ def timed(fn, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=50)
-    ap.add_argument('--tag', default=os.environ.get('SMI_HEAD_T', '1') + '/' +
-                    os.environ.get('SMI_HEAD_FQ', 'auto'))
+    ap.add_argument('--tag', default='')
     args = ap.parse_args()
     dev = torch.device('cuda', 0)
     L.ensure_workspace(dev)

@@ -3,8 +3,7 @@
 replayed hipGraph of 20 back-to-back launches (the learner's launch mode), for
 smi_lstm_forward (xproj input), smi_lstm_forward_x (fused input projection)
 and smi_lstm_backward at each step count, so the per-step cost and the fixed
-(prologue) cost separate.  A/B knobs are environment variables
-(SMI_LSTM_VALU, SMI_LSTM_Q, SMI_LSTM_XM).
+(prologue) cost separate.  The form is the dispatch's choice for the shape.
 Usage: python tools/bench_lstm.py [--segments 128] [--steps 1,13,25] [--reps 10]"""
 import argparse
 import json
@@ -75,7 +74,6 @@ def main():
     gates = torch.empty(SM, B, 4 * H, device=dev)
     dh = torch.randn(SM, B, H, device=dev, generator=g)
     dgates = torch.empty(SM, B, 4 * H, device=dev)
-    knobs = {k: v for k, v in os.environ.items() if k.startswith('SMI_LSTM')}
     for S in (int(s) for s in args.steps.split(',')):
         def st():
             return torch.cuda.current_stream(dev).cuda_stream
@@ -95,7 +93,7 @@ def main():
             for w in (whh, wih, bhh, bih):
                 w.mul_(1.0)
 
-        out = {'bench': 'lstm', 'segments': B, 'steps': S, 'hidden': H, 'din': D, 'knobs': knobs,
+        out = {'bench': 'lstm', 'segments': B, 'steps': S, 'hidden': H, 'din': D,
                'dirty': args.dirty}
         base = graph_us(dirty, dev, reps=args.reps) if args.dirty else 0.0
         for name, fn in (('fwd', fwd), ('fwd_x', fwdx), ('bwd', bwd)):

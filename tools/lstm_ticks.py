@@ -29,7 +29,7 @@ def main():
     learner = PPOLearner(lc, env_config(D, A), seed=1, device='cuda')
     batch = synthetic.to_device(synthetic.ppo_batch(B, T, D, A, seed=0, rnn_hidden=100), 'cuda')
     lib = L.lib()
-    # the MFMA forms' and the VALU recurrence's ticks (two objects: build.py UNITS)
+    # the MFMA forms' and the VALU recurrence's ticks (lstm_mfma.hip, lstm_valu.hip)
     fns = [lib.smi_lstm_phase_ticks, lib.smi_lstm_v_phase_ticks]
     for f in fns:
         f.argtypes = [ctypes.c_void_p]
