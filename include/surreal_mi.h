@@ -671,6 +671,12 @@ int smi_diag_dw_plan(const int* gemms, int ng, int waves, int slots, int64_t cap
 /* critic loss nn.MSELoss()(Q, y) (ddpg.py:306): loss = mean((Q-y)^2), dQ = 2(Q-y)/n */
 int smi_mse_grad(const float* q, int64_t q_stride, const float* y, int64_t n, float* dq,
                  float* loss, void* stream);
+/* The prioritized replay's critic loss mean(w (Q-y)^2): dQ = (2(Q-y)/n) * w (in
+ * this order, so w = 1 gives smi_mse_grad's bits), loss, and td_out[i] = Q-y
+ * (the TD error the priorities are made from).  w == NULL: unweighted;
+ * td_out == NULL: not written; both NULL: smi_mse_grad's own kernel. */
+int smi_mse_grad_weighted(const float* q, int64_t q_stride, const float* y, const float* w,
+                          int64_t n, float* dq, float* loss, float* td_out, void* stream);
 /* actor loss -Q(s, mu(s)).mean() (ddpg.py:325-329): loss, dQ = -1/n */
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream);
@@ -767,6 +773,52 @@ int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
                       const uint8_t* frames_next, int64_t frame_bytes, const int64_t* idx,
                       int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
                       void* stream);
+
+/* ------------------------------------------------- prioritized replay */
+/* Proportional prioritized replay (replay/prioritized_replay.py +
+ * replay/segment_tree.py, read as the openai/baselines code they were adapted
+ * from; the decisions are listed in csrc/per_kernels.hip and INTEGRATION.md).
+ * One device buffer of smi_per_tree_doubles(capacity) = 4 * capacity doubles
+ * holds both fp64 trees: node i is the pair {sum, min} at [2i], [2i+1], its
+ * children are 2i and 2i+1, the leaf of slot s is node capacity + s; node 0 is
+ * unused and [0] holds max_priority (1.0 after init).  A parent is always
+ * left + right (min(left, right)), so every value is bit-identical to the
+ * Python tree's.  capacity: a power of two in [1, 2^30] (the smallest one >=
+ * memory_size).  Indices are trusted (0 <= idx < capacity), as in
+ * smi_gather_rows.  n == 0 / batch == 0 return SMI_OK without a launch; NULL
+ * pointers, negative counts, a capacity that is no power of two, len outside
+ * [2, capacity], eps <= 0, alpha <= 0 and beta < 0 are SMI_E_ARG.
+ *   smi_per_init       empty trees (sum 0.0, min +inf), max_priority 1.0
+ *   smi_per_set        leaf[i] at slot idx[i] in both trees and every ancestor;
+ *                      where a slot repeats the last occurrence wins
+ *   smi_per_insert     leaf max_priority ** alpha at the ring slots of n rows
+ *                      written from first_slot on (mod memory_size; n >
+ *                      memory_size: the surviving slots only)
+ *   smi_per_update_td  leaf (|td[i * td_stride]| + eps) ** alpha (fp64) at slot
+ *                      idx[i], last occurrence wins; max_priority raised to the
+ *                      largest |td| + eps, in the same launch
+ *   smi_per_sample     batch draws idx = find_prefixsum_idx(random.random() *
+ *                      sum(slots 0 .. len-2)) with CPython's random.random() on
+ *                      the MT19937 state of smi_mt_seed (two words per draw),
+ *                      clamped to len - 1, and their importance-sampling
+ *                      weights (leaf / sum * len) ** -beta / max_w as float32
+ *                      (beta == 0: exactly 1)
+ * The *_host forms do the same on host buffers. */
+int64_t smi_per_tree_doubles(int64_t capacity);
+int smi_per_init(double* tree, int64_t capacity, void* stream);
+int smi_per_set(double* tree, int64_t capacity, const int64_t* idx, const double* leaf, int64_t n,
+                void* stream);
+int smi_per_insert(double* tree, int64_t capacity, int64_t first_slot, int64_t n,
+                   int64_t memory_size, double alpha, void* stream);
+int smi_per_update_td(double* tree, int64_t capacity, const int64_t* idx, const float* td,
+                      int64_t td_stride, int64_t n, double eps, double alpha, void* stream);
+int smi_per_sample(const double* tree, int64_t capacity, int64_t len, uint32_t* dev_state625,
+                   int64_t batch, double beta, int64_t* idx_out, float* w_out, void* stream);
+int smi_per_init_host(double* tree, int64_t capacity);
+int smi_per_set_host(double* tree, int64_t capacity, const int64_t* idx, const double* leaf,
+                     int64_t n);
+int smi_per_sample_host(const double* tree, int64_t capacity, int64_t len, uint32_t* host_state625,
+                        int64_t batch, double beta, int64_t* idx_out, float* w_out);
 
 #ifdef __cplusplus
 }

@@ -167,6 +167,7 @@ _SIGS = {
     'smi_linear_backward_weight': (c_int, [P, c_i64, c_int, c_int, P, c_i64, c_int, P, c_i64, P,
                                            c_int, P]),
     'smi_mse_grad': (c_int, [P, c_i64, P, c_i64, P, P, P]),
+    'smi_mse_grad_weighted': (c_int, [P, c_i64, P, P, c_i64, P, P, P, P]),
     'smi_neg_mean_grad': (c_int, [P, c_i64, c_i64, P, P, P]),
     'smi_tanh_backward': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, P, c_i64, P]),
     'smi_copy_cols': (c_int, [P, c_i64, c_i64, c_int, P, c_i64, P]),
@@ -186,6 +187,15 @@ _SIGS = {
     'smi_mt_randint': (c_int, [P, c_i64, c_i64, P, P]),
     'smi_gather_rows': (c_int, [P, c_i64, P, c_i64, P, P]),
     'smi_replay_gather': (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, P]),
+    'smi_per_tree_doubles': (c_i64, [c_i64]),
+    'smi_per_init': (c_int, [P, c_i64, P]),
+    'smi_per_set': (c_int, [P, c_i64, P, P, c_i64, P]),
+    'smi_per_insert': (c_int, [P, c_i64, c_i64, c_i64, c_i64, c_f64, P]),
+    'smi_per_update_td': (c_int, [P, c_i64, P, P, c_i64, c_i64, c_f64, c_f64, P]),
+    'smi_per_sample': (c_int, [P, c_i64, c_i64, P, c_i64, c_f64, P, P, P]),
+    'smi_per_init_host': (c_int, [P, c_i64]),
+    'smi_per_set_host': (c_int, [P, c_i64, P, P, c_i64]),
+    'smi_per_sample_host': (c_int, [P, c_i64, c_i64, P, c_i64, c_f64, P, P]),
     'smi_lstm_param_count': (c_i64, [c_int, c_int]),
     'smi_kernel_timing': (c_int, [c_int]),
     'smi_kernel_timing_report': (c_int, [c_int, P]),

@@ -115,6 +115,8 @@ int launch_zfilter_tmajor(const float*, const float*, int, int, int, int, int, c
 int launch_adam_clip(float*, const float*, float*, float*, int64_t, int*, const float*, float,
                      float, float, float, float, float, const int*, float*, hipStream_t);
 int launch_mse_grad(const float*, int64_t, const float*, int64_t, float*, float*, hipStream_t);
+int launch_mse_grad_weighted(const float*, int64_t, const float*, const float*, int64_t, float*,
+                             float*, float*, hipStream_t);
 int launch_neg_mean_grad(const float*, int64_t, int64_t, float*, float*, hipStream_t);
 int launch_tanh_backward(const float*, int64_t, const float*, int64_t, int64_t, int, float*,
                          int64_t, hipStream_t);
@@ -154,6 +156,16 @@ int launch_replay_gather(const float*, int64_t, const uint8_t*, const uint8_t*, 
                          const int64_t*, int64_t, float*, uint8_t*, uint8_t*, hipStream_t);
 int launch_zfilter_accumulate(const float*, const float*, int, float, float*, float*, float*,
                               hipStream_t);
+int per_init_host(double*, int64_t);
+int per_set_host(double*, int64_t, const int64_t*, const double*, int64_t);
+int per_sample_host(const double*, int64_t, int64_t, uint32_t*, int64_t, double, int64_t*, float*);
+int launch_per_init(double*, int64_t, hipStream_t);
+int launch_per_set(double*, int64_t, const int64_t*, const double*, int64_t, hipStream_t);
+int launch_per_insert(double*, int64_t, int64_t, int64_t, int64_t, double, hipStream_t);
+int launch_per_update_td(double*, int64_t, const int64_t*, const float*, int64_t, int64_t, double,
+                         double, hipStream_t);
+int launch_per_sample(const double*, int64_t, int64_t, uint32_t*, int64_t, double, int64_t*, float*,
+                      hipStream_t);
 
 }  // namespace smi
 
@@ -510,6 +522,12 @@ int smi_mse_grad(const float* q, int64_t q_stride, const float* y, int64_t n, fl
   return launch_mse_grad(q, q_stride, y, n, dq, loss, SMI_STREAM(stream));
 }
 
+int smi_mse_grad_weighted(const float* q, int64_t q_stride, const float* y, const float* w,
+                          int64_t n, float* dq, float* loss, float* td_out, void* stream) {
+  REQUIRE(q && y && dq && n > 0, "mse_grad_weighted: bad args");
+  return launch_mse_grad_weighted(q, q_stride, y, w, n, dq, loss, td_out, SMI_STREAM(stream));
+}
+
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream) {
   REQUIRE(q && dq && n > 0, "neg_mean_grad: bad args");
@@ -641,6 +659,89 @@ int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
   if (batch == 0) return SMI_OK;
   return launch_replay_gather(table, cols, frames, frames_next, frame_bytes, idx, batch, rows_out,
                               pix_out, pix_next_out, SMI_STREAM(stream));
+}
+
+/* -------------------------------------------------- prioritized replay */
+#define PER_CAP(name, capacity) \
+  REQUIRE((capacity) >= 1 && (capacity) <= ((int64_t)1 << 30) && ((capacity) & ((capacity) - 1)) == 0, \
+          name ": capacity must be a power of two in [1, 2^30]")
+
+int64_t smi_per_tree_doubles(int64_t capacity) { return capacity > 0 ? 4 * capacity : 0; }
+
+int smi_per_init(double* tree, int64_t capacity, void* stream) {
+  REQUIRE(tree, "per_init: null tree");
+  PER_CAP("per_init", capacity);
+  return launch_per_init(tree, capacity, SMI_STREAM(stream));
+}
+
+int smi_per_init_host(double* tree, int64_t capacity) {
+  REQUIRE(tree, "per_init_host: null tree");
+  PER_CAP("per_init_host", capacity);
+  return per_init_host(tree, capacity);
+}
+
+int smi_per_set(double* tree, int64_t capacity, const int64_t* idx, const double* leaf, int64_t n,
+                void* stream) {
+  REQUIRE(tree && idx && leaf, "per_set: null tree, idx or leaf");
+  PER_CAP("per_set", capacity);
+  REQUIRE(n >= 0, "per_set: n < 0");
+  if (n == 0) return SMI_OK;
+  return launch_per_set(tree, capacity, idx, leaf, n, SMI_STREAM(stream));
+}
+
+int smi_per_set_host(double* tree, int64_t capacity, const int64_t* idx, const double* leaf,
+                     int64_t n) {
+  REQUIRE(tree && idx && leaf, "per_set_host: null tree, idx or leaf");
+  PER_CAP("per_set_host", capacity);
+  REQUIRE(n >= 0, "per_set_host: n < 0");
+  if (n == 0) return SMI_OK;
+  return per_set_host(tree, capacity, idx, leaf, n);
+}
+
+int smi_per_insert(double* tree, int64_t capacity, int64_t first_slot, int64_t n,
+                   int64_t memory_size, double alpha, void* stream) {
+  REQUIRE(tree, "per_insert: null tree");
+  PER_CAP("per_insert", capacity);
+  REQUIRE(n >= 0, "per_insert: n < 0");
+  REQUIRE(memory_size >= 1 && memory_size <= capacity && first_slot >= 0 && first_slot < memory_size,
+          "per_insert: memory_size outside [1, capacity] or first_slot outside [0, memory_size)");
+  REQUIRE(alpha > 0.0, "per_insert: alpha must be > 0");
+  if (n == 0) return SMI_OK;
+  return launch_per_insert(tree, capacity, first_slot, n, memory_size, alpha, SMI_STREAM(stream));
+}
+
+int smi_per_update_td(double* tree, int64_t capacity, const int64_t* idx, const float* td,
+                      int64_t td_stride, int64_t n, double eps, double alpha, void* stream) {
+  REQUIRE(tree && idx && td, "per_update_td: null tree, idx or td");
+  PER_CAP("per_update_td", capacity);
+  REQUIRE(n >= 0, "per_update_td: n < 0");
+  REQUIRE(eps > 0.0, "per_update_td: eps must be > 0");
+  REQUIRE(alpha > 0.0, "per_update_td: alpha must be > 0");
+  if (n == 0) return SMI_OK;
+  return launch_per_update_td(tree, capacity, idx, td, td_stride, n, eps, alpha,
+                              SMI_STREAM(stream));
+}
+
+#define PER_SAMPLE_ARGS(name, state) \
+  REQUIRE(tree && (state) && idx_out && w_out, name ": null tree, state or output"); \
+  PER_CAP(name, capacity); \
+  REQUIRE(batch >= 0, name ": batch < 0"); \
+  REQUIRE(len >= 2 && len <= capacity, name ": len must be in [2, capacity]"); \
+  REQUIRE(beta >= 0.0, name ": beta must be >= 0")
+
+int smi_per_sample(const double* tree, int64_t capacity, int64_t len, uint32_t* dev_state625,
+                   int64_t batch, double beta, int64_t* idx_out, float* w_out, void* stream) {
+  PER_SAMPLE_ARGS("per_sample", dev_state625);
+  if (batch == 0) return SMI_OK;
+  return launch_per_sample(tree, capacity, len, dev_state625, batch, beta, idx_out, w_out,
+                           SMI_STREAM(stream));
+}
+
+int smi_per_sample_host(const double* tree, int64_t capacity, int64_t len, uint32_t* host_state625,
+                        int64_t batch, double beta, int64_t* idx_out, float* w_out) {
+  PER_SAMPLE_ARGS("per_sample_host", host_state625);
+  if (batch == 0) return SMI_OK;
+  return per_sample_host(tree, capacity, len, host_state625, batch, beta, idx_out, w_out);
 }
 
 

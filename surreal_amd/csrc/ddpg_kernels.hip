@@ -3,6 +3,9 @@
 // the dense layers run on linear_kernels.hip.
 //
 //   mse_grad        critic loss nn.MSELoss()(Q, y): loss, dQ = 2 (Q - y) / n
+//   mse_grad_weighted  the prioritized replay's critic loss mean(w (Q - y)^2):
+//                   dQ = (2 (Q - y) / n) * w (this order: w = 1 gives mse_grad's
+//                   bits), and the TD error Q - y for the priorities
 //   neg_mean_grad   actor loss -Q(s, mu(s)).mean(): loss, dQ = -1 / n
 //   tanh_backward   d/dz tanh(z) = 1 - tanh(z)^2 (actor output layer)
 //   copy_cols       write the action block of the critic's concat input
@@ -28,6 +31,31 @@ mse_grad_kernel(const float* __restrict__ q, int64_t qs, const float* __restrict
     const float d = q[i * qs] - y[i];
     dq[i] = inv * (2.f * d);
     a += (double)(d * d);
+  }
+  a = block_sum_d(a, scr);
+  if (threadIdx.x == 0 && loss) loss[0] = (float)(a / (double)n);
+}
+
+__global__ void __launch_bounds__(kWG)
+mse_grad_weighted_kernel(const float* __restrict__ q, int64_t qs, const float* __restrict__ y,
+                         const float* __restrict__ w, int64_t n, float* __restrict__ dq,
+                         float* loss, float* __restrict__ td) {
+  __shared__ double scr[kNW];
+  const float inv = 1.f / (float)n;
+  double a = 0.0;
+  for (int64_t i = threadIdx.x; i < n; i += kWG) {
+    const float d = q[i * qs] - y[i];
+    const float g = inv * (2.f * d);
+    const float d2 = d * d;
+    if (w) {
+      const float wi = w[i];
+      dq[i] = g * wi;
+      a += (double)(wi * d2);
+    } else {
+      dq[i] = g;
+      a += (double)d2;
+    }
+    if (td) td[i] = d;
   }
   a = block_sum_d(a, scr);
   if (threadIdx.x == 0 && loss) loss[0] = (float)(a / (double)n);
@@ -255,6 +283,13 @@ int launch_mse_grad(const float* q, int64_t qs, const float* y, int64_t n, float
                     hipStream_t st) {
   hipLaunchKernelGGL(mse_grad_kernel, dim3(1), dim3(kWG), 0, st, q, qs, y, n, dq, loss);
   return check_launch("mse_grad_kernel");
+}
+int launch_mse_grad_weighted(const float* q, int64_t qs, const float* y, const float* w, int64_t n,
+                             float* dq, float* loss, float* td, hipStream_t st) {
+  if (!w && !td) return launch_mse_grad(q, qs, y, n, dq, loss, st);
+  hipLaunchKernelGGL(mse_grad_weighted_kernel, dim3(1), dim3(kWG), 0, st, q, qs, y, w, n, dq, loss,
+                     td);
+  return check_launch("mse_grad_weighted_kernel");
 }
 int launch_neg_mean_grad(const float* q, int64_t qs, int64_t n, float* dq, float* loss,
                          hipStream_t st) {

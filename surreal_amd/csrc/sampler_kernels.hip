@@ -17,23 +17,9 @@
 // sequence CPython produces, and exactly as many words are consumed.
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
+#include "mt19937.hpp"
 
 namespace smi {
-
-constexpr int kMtN = 624, kMtM = 397;
-constexpr uint32_t kMatA = 0x9908b0dfU, kUpper = 0x80000000U, kLower = 0x7fffffffU;
-
-__host__ __device__ inline uint32_t mt_temper(uint32_t y) {
-  y ^= (y >> 11);
-  y ^= (y << 7) & 0x9d2c5680U;
-  y ^= (y << 15) & 0xefc60000U;
-  y ^= (y >> 18);
-  return y;
-}
-__host__ __device__ inline uint32_t mt_mix(uint32_t hi, uint32_t lo, uint32_t far) {
-  const uint32_t y = (hi & kUpper) | (lo & kLower);
-  return far ^ (y >> 1) ^ ((y & 1U) ? kMatA : 0U);
-}
 
 // ------------------------------------------------------------------ host
 static void mt_init_genrand(uint32_t* mt, uint32_t s) {
@@ -65,7 +51,7 @@ void mt_seed_host(uint64_t seed, uint32_t* st) {
   st[kMtN] = kMtN;  // position: next call twists
 }
 
-static uint32_t mt_next_host(uint32_t* st) {
+uint32_t mt_next_host(uint32_t* st) {
   uint32_t* mt = st;
   if (st[kMtN] >= (uint32_t)kMtN) {
     int kk = 0;
@@ -94,8 +80,6 @@ int mt_randint_host(uint32_t* st, int64_t n, int64_t batch, int64_t* out) {
 }
 
 // ---------------------------------------------------------------- device
-constexpr int kMtWG = 1024;
-
 __global__ void __launch_bounds__(kMtWG)
 mt_randint_kernel(uint32_t* __restrict__ st, int64_t n, int k, int64_t batch,
                   int64_t* __restrict__ out) {
@@ -109,26 +93,8 @@ mt_randint_kernel(uint32_t* __restrict__ st, int64_t n, int k, int64_t batch,
   int64_t filled = 0;
   while (filled < batch) {
     if (s_pos >= kMtN) {
-      // phase 1: [0, 227) from old words
-      uint32_t nv = 0;
-      if (tid < kMtN - kMtM) nv = mt_mix(mt[tid], mt[tid + 1], mt[tid + kMtM]);
-      __syncthreads();
-      if (tid < kMtN - kMtM) mt[tid] = nv;
-      __syncthreads();
-      // phase 2: [227, 454) and phase 3: [454, 623) read words 227 back
-      for (int base = kMtN - kMtM; base < kMtN - 1; base += kMtN - kMtM) {
-        const int kk = base + tid;
-        const int end = (base + (kMtN - kMtM) < kMtN - 1) ? base + (kMtN - kMtM) : kMtN - 1;
-        nv = 0;
-        if (kk < end) nv = mt_mix(mt[kk], mt[kk + 1], mt[kk + (kMtM - kMtN)]);
-        __syncthreads();
-        if (kk < end) mt[kk] = nv;
-        __syncthreads();
-      }
-      if (tid == 0) {
-        mt[kMtN - 1] = mt_mix(mt[kMtN - 1], mt[0], mt[kMtM - 1]);
-        s_pos = 0;
-      }
+      mt_twist_wg(mt, tid);
+      if (tid == 0) s_pos = 0;
       __syncthreads();
     }
     const int pos = s_pos;

@@ -320,7 +320,10 @@ class _Net(object):
 
 class DDPGLearner(LearnerHooks):
     """ddpg.py:12-440 on MI355X (low-dim or pixel observations; optional
-    layernorm, TD3 options)."""
+    layernorm, TD3 options).  A batch with a 'weights' entry (float32 [B, 1],
+    replay.PrioritizedReplay.sample_batch) weights both critics' loss; after
+    every learn() `td_error` is a device view [B] of the first critic's Q - y
+    before its Adam step (PrioritizedReplay.update_priorities_from_td)."""
 
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  device=None, seed=0, use_graph=False, dp=None, checkpoint_full_state=False,
@@ -492,12 +495,23 @@ class DDPGLearner(LearnerHooks):
             out[k] = torch.as_tensor(v, dtype=torch.float32).to(self.device, non_blocking=True)
         for k in ('actions', 'rewards', 'dones'):
             out[k] = torch.as_tensor(batch[k], dtype=torch.float32).to(self.device, non_blocking=True)
+        if batch.get('weights') is not None:         # prioritized replay: importance-sampling weights
+            out['weights'] = torch.as_tensor(batch['weights'], dtype=torch.float32).to(
+                self.device, non_blocking=True)
         return Config(out)
 
     # --------------------------------------------------------- _optimize
     def _optimize(self, obs, actions, rewards, obs_next, done,           # ddpg.py:244-352
-                  target_update=True):
+                  target_update=True, weights=None):
+        """weights (float32 [B] or [B, 1], contiguous; a prioritized replay's
+        importance-sampling weights): both critics' loss becomes mean(w (Q -
+        y)^2); the actor loss stays unweighted.  The first critic's Q - y
+        before its Adam step is left in self.td_error either way."""
         B = actions.shape[0]
+        if weights is not None and (weights.numel() != B or not weights.is_contiguous()
+                                    or weights.dtype != torch.float32):
+            raise ValueError(f'weights: expected contiguous float32 [{B}] or [{B}, 1], got '
+                             f'{weights.dtype} {tuple(weights.shape)}')
         st = L.stream(self.device)
         net = _Net(self.model, self._bufs)
         tnet = _Net(self.model_target, self._bufs)
@@ -548,7 +562,9 @@ class DDPGLearner(LearnerHooks):
         crit = self.model.critic
         q = net.critic_fwd(crit, obs, actions, B, store='c')
         dq = net.buf('dq', (B, 1))
-        L.call('smi_mse_grad', _p(q), 1, _p(y), B, _p(dq), _p(self.stats_buf[1:2]), st)
+        self.td_error = net.buf('td', (B,))
+        L.call('smi_mse_grad_weighted', _p(q), 1, _p(y), _p(weights), B, _p(dq),
+               _p(self.stats_buf[1:2]), _p(self.td_error), st)
         g = self.opt['critic']['g']
         cnn = (self.model, pix, 'cp', self.opt['critic_cnn']['g']) if self.is_pixel_input else None
         self._critic_backward(net, crit, obs, B, dq, 'c', g, st, need_obs_grad=True, cnn=cnn)
@@ -560,7 +576,8 @@ class DDPGLearner(LearnerHooks):
             q_2 = net.critic_fwd(crit2, obs2, actions, B, store='q2c')
             dq_2 = net.buf('dq_2', (B, 1))
             # the reference reports this critic's loss as 'critic_loss'
-            L.call('smi_mse_grad', _p(q_2), 1, _p(y), B, _p(dq_2), _p(self.stats_buf[1:2]), st)
+            L.call('smi_mse_grad_weighted', _p(q_2), 1, _p(y), _p(weights), B, _p(dq_2),
+                   _p(self.stats_buf[1:2]), None, st)
             cnn2 = (self.model2, pix, 'q2p', self.opt['critic2_cnn']['g']) if self.is_pixel_input \
                 else None
             self._critic_backward(net, crit2, obs2, B, dq_2, 'q2c', self.opt['critic2']['g'], st,
@@ -713,29 +730,38 @@ class DDPGLearner(LearnerHooks):
             obs = obs['low_dim']['flat_inputs'] if isinstance(obs, dict) else obs
             obs_next = obs_next['low_dim']['flat_inputs'] if isinstance(obs_next, dict) else obs_next
         ins = (obs, batch['actions'], batch['rewards'], obs_next, batch['dones'])
+        weights = batch.get('weights')
         if self.use_graph and not self.is_pixel_input:
-            self._optimize_graphed(*ins)
+            self._optimize_graphed(*ins, weights=weights)
         else:
-            self._optimize(*ins)
+            self._optimize(*ins, weights=weights)
         self._report_metrics(self.current_iteration)                     # ddpg.py:371
         self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
 
-    def _optimize_graphed(self, obs, actions, rewards, obs_next, done):
+    def _optimize_graphed(self, obs, actions, rewards, obs_next, done, weights=None):
         """One _optimize as a hipGraph replay (the step is ~40 small launches at
         batch 512, so host launch overhead, not the GPU, bounds it).  The first
         call runs eagerly (it is that call's update, and it sizes every scratch
         buffer), then captures the same launch sequence over static input
         buffers; later calls copy their inputs in (skipped when the caller
         already wrote them: graph_inputs()) and replay.  The target update stays
-        on the host, where its interval counter lives (ddpg.py:403-428)."""
+        on the host, where its interval counter lives (ddpg.py:403-428).
+        Importance-sampling weights are one more static input; a graph captured
+        without them is not reused with them (nor the other way round): the
+        step is captured again."""
         ins = (obs, actions, rewards, obs_next, done)
+        if weights is not None:
+            ins = ins + (weights,)
+        if self._graph is not None and len(self._gin) != len(ins):
+            self._graph = None
         if self._graph is None:
-            self._optimize(*ins)
+            self._optimize(*ins[:5], weights=weights)
             self._gin = [torch.zeros(tuple(t.shape), dtype=torch.float32, device=self.device)
                          for t in ins]
             g = torch.cuda.CUDAGraph()
             with L.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._optimize(*self._gin, target_update=False)
+                self._optimize(*self._gin[:5], target_update=False,
+                               weights=self._gin[5] if weights is not None else None)
             self._graph = g
             return
         for s, t in zip(self._gin, ins):
@@ -748,7 +774,7 @@ class DDPGLearner(LearnerHooks):
         """Static (obs, actions, rewards, obs_next, dones) buffers of the captured
         step (None before the first learn() in graph mode)."""
         return None if self._gin is None else dict(zip(
-            ('obs', 'actions', 'rewards', 'obs_next', 'dones'), self._gin))
+            ('obs', 'actions', 'rewards', 'obs_next', 'dones', 'weights'), self._gin))
 
     def _host_scalars(self):
         return {}

@@ -8,8 +8,12 @@ done) in HBM and the index draw done by the CPython-exact MT19937 HIP kernel
 `random.seed(seed)`.  With camera observations (a 'pixel' entry in the obs
 spec) the ring also holds the uint8 frames of both observations on the device
 and `sample_batch()` gathers rows and frames in one launch (smi_replay_gather)
-into the batch form DDPGLearner.learn() takes.  FIFOReplay mirrors fifo_replay.py:6-49 (host deque; the
-PPO path consumes batches in insertion order).
+into the batch form DDPGLearner.learn() takes.  PrioritizedReplay adds the
+proportional draw of prioritized_replay.py / segment_tree.py on the same ring:
+fp64 sum and min trees in HBM, the draw and its importance-sampling weights in
+one kernel (smi_per_sample), priorities from the learner's TD errors without a
+host round trip (smi_per_update_td).  FIFOReplay mirrors fifo_replay.py:6-49
+(host deque; the PPO path consumes batches in insertion order).
 """
 import ctypes
 from collections import deque
@@ -265,6 +269,143 @@ class UniformReplay(object):
         return {'obs': rows[:, :D], 'actions': rows[:, D:D + A],
                 'rewards': rows[:, D + A:D + A + 1], 'obs_next': rows[:, D + A + 1:2 * D + A + 1],
                 'dones': rows[:, 2 * D + A + 1:2 * D + A + 2]}
+
+
+class PrioritizedReplay(UniformReplay):
+    """Proportional prioritized replay (prioritized_replay.py, segment_tree.py)
+    on the device ring.  The reference class cannot be constructed (its super()
+    names another class, it reads self._storage, sample returns only the
+    experiences), so its text is read as the openai/baselines code it was
+    adapted from; the decisions are listed in csrc/per_kernels.hip and
+    INTEGRATION.md.  In short: fp64 trees over capacity = the smallest power
+    of two >= memory_size; a written slot gets max_priority ** alpha; a draw is
+    find_prefixsum_idx(random.random() * sum(slots 0 .. len-2)) on the
+    CPython-exact stream (slot len-1 is never drawn, as in baselines); weights
+    (p_i * len) ** -beta / max_w; a repeated index keeps its last priority.
+
+    alpha is read from learner_config.replay.alpha, as the reference does.
+    Data parallelism is out of scope: replicated trees would need an
+    all-gather of the TD errors, so world > 1 raises ValueError."""
+
+    def __init__(self, learner_config, env_config, session_config=None, index=0, seed=0,
+                 device=None):
+        super().__init__(learner_config, env_config, session_config, index, seed, device)
+        self.alpha = float(learner_config['replay']['alpha'])
+        if not self.alpha > 0:
+            raise ValueError(f'replay.alpha must be > 0, got {self.alpha}')
+        self.capacity = 1
+        while self.capacity < self.memory_size:
+            self.capacity *= 2
+        self.tree = torch.empty(int(L.lib().smi_per_tree_doubles(self.capacity)),
+                                dtype=torch.float64, device=self.device)
+        L.call('smi_per_init', L.ptr(self.tree), self.capacity, L.stream(self.device))
+        self.weights = None
+        self._beta = None
+
+    @property
+    def max_priority(self):
+        """host copy of the running maximum priority (synchronises)"""
+        return float(self.tree[0].item())
+
+    def insert_rows(self, rows, pix=None, pix_next=None):
+        """UniformReplay.insert_rows; the written slots get max_priority ** alpha"""
+        first = self._next_idx
+        n = int(torch.as_tensor(rows).shape[0])
+        super().insert_rows(rows, pix, pix_next)
+        L.call('smi_per_insert', L.ptr(self.tree), self.capacity, first, n, self.memory_size,
+               self.alpha, L.stream(self.device))
+
+    def sample_indices(self, batch_size, beta=0):
+        """batch_size proportional draws; their weights are kept in self.weights"""
+        if self._beta is not None:                 # sample() / sample_batch() in progress
+            beta, self._beta = self._beta, None
+        if self._idx is None or self._idx.numel() != batch_size:
+            self._idx = torch.empty(batch_size, dtype=torch.int64, device=self.device)
+            self.weights = torch.empty(batch_size, dtype=torch.float32, device=self.device)
+        L.call('smi_per_sample', L.ptr(self.tree), self.capacity, len(self), L.ptr(self.rng.dev),
+               int(batch_size), float(beta), L.ptr(self._idx), L.ptr(self.weights),
+               L.stream(self.device))
+        return self._idx
+
+    @staticmethod
+    def _one_rank(world):
+        if world != 1:
+            raise ValueError('a prioritized replay is not data parallel (world must be 1): '
+                             'replicated trees need an all-gather of the TD errors')
+
+    def sample(self, batch_size, out=None, rank=0, world=1, beta=0):
+        """(indices, rows, weights [batch] float32) on the device"""
+        self._one_rank(world)
+        self._beta = beta
+        try:
+            idx, rows = super().sample(batch_size, out=out)
+        finally:
+            self._beta = None
+        return idx, rows, self.weights
+
+    def sample_batch(self, batch_size, rank=0, world=1, beta=0):
+        """UniformReplay.sample_batch over the prioritized draw; the weights go
+        under batch['weights'] as float32 [n, 1], where DDPGLearner.learn()
+        reads them.  Pixel mode gathers through smi_replay_gather unchanged."""
+        self._one_rank(world)
+        if not self.is_pixel:
+            if self._out is None or self._out[0].shape[0] != batch_size:
+                self._out = (torch.empty(batch_size, self.width, dtype=torch.float32,
+                                         device=self.device),)
+            idx, rows, _ = self.sample(batch_size, out=self._out[0], beta=beta)
+            batch = self.split(rows)
+        else:
+            self._beta = beta
+            try:
+                idx, batch = super().sample_batch(batch_size)
+            finally:
+                self._beta = None
+        batch['weights'] = self.weights.view(-1, 1)
+        return idx, batch
+
+    def _indices(self, indices):
+        if isinstance(indices, torch.Tensor):
+            return indices.to(device=self.device, dtype=torch.int64).contiguous().view(-1)
+        return torch.as_tensor(np.asarray(indices, dtype=np.int64).reshape(-1), device=self.device)
+
+    def update_priorities(self, indices, priorities):
+        """tree[idx] = priority ** alpha in the sequential loop's meaning (a
+        repeated index keeps its last priority), max_priority raised to the
+        largest one.  Host floats are raised to alpha on the host in fp64;
+        device tensors stay on the device."""
+        idx = self._indices(indices)
+        if not idx.numel() and not len(priorities):
+            return
+        if isinstance(priorities, torch.Tensor) and priorities.is_cuda:
+            p = priorities.to(torch.float64).contiguous().view(-1)
+            leaf = p.pow(self.alpha)
+            top = p.max().view(1)
+        else:
+            p = np.asarray(priorities, dtype=np.float64).reshape(-1)
+            if not np.all(p > 0):
+                raise ValueError('priorities must be > 0')
+            leaf = torch.as_tensor(np.array([float(v) ** self.alpha for v in p], dtype=np.float64),
+                                   device=self.device)
+            top = torch.as_tensor(np.array([p.max()]), device=self.device)
+        if idx.numel() != leaf.numel():
+            raise ValueError(f'{idx.numel()} indices, {leaf.numel()} priorities')
+        L.call('smi_per_set', L.ptr(self.tree), self.capacity, L.ptr(idx), L.ptr(leaf), idx.numel(),
+               L.stream(self.device))
+        torch.maximum(self.tree[0:1], top, out=self.tree[0:1])
+
+    def update_priorities_from_td(self, indices, td, eps=1e-6):
+        """priority = |td| + eps from a float32 device tensor of TD errors
+        (DDPGLearner.td_error), one launch, no synchronisation"""
+        idx = self._indices(indices)
+        if not (isinstance(td, torch.Tensor) and td.is_cuda and td.dtype == torch.float32):
+            raise ValueError('td must be a float32 device tensor')
+        if td.dim() == 2 and td.shape[1] == 1:
+            td = td[:, 0]
+        if td.dim() != 1 or td.shape[0] != idx.numel():
+            raise ValueError(f'{idx.numel()} indices, td of shape {tuple(td.shape)}')
+        L.call('smi_per_update_td', L.ptr(self.tree), self.capacity, L.ptr(idx), L.ptr(td),
+               td.stride(0) if td.numel() > 1 else 1, idx.numel(), float(eps), self.alpha,
+               L.stream(self.device))
 
 
 class FIFOReplay(object):
