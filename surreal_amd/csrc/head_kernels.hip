@@ -33,7 +33,7 @@
 // the value): a VALU pass in the order of the streaming small-K kernel.
 //
 // Rows are the learner's [step][segment] rows; the weight gradients of the
-// three layers stay in the phase's grouped dW launch (linear_kernels.hip).
+// three layers stay in the phase's grouped dW launch (linear_dw.hip).
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "pol_rows.hpp"

@@ -1,5 +1,5 @@
 // lstm_cell.hpp — LSTM cell arithmetic shared by the sequence kernels
-// (lstm_mfma.hip, lstm_valu.hip) and the BPTT + weight-gradient launch (linear_kernels.hip):
+// (lstm_mfma.hip, lstm_valu.hip) and the BPTT + weight-gradient launch (linear_dw.hip):
 // the activations, the kernel argument blocks, the lane-quad exchanges and the
 // one-segment-per-workgroup BPTT body (lstm_bwd_q_body).
 #pragma once

@@ -787,7 +787,7 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
 
 // BR of the BPTT's one-segment-per-workgroup K-split form (lstm_bwd_q_kernel)
 // when launch_lstm_bwd would run it for (B, H), else 0: the form that the
-// BPTT + weight-gradient launch (linear_kernels.hip) embeds
+// BPTT + weight-gradient launch (linear_dw.hip) embeds
 int lstm_bwd_q_form(int B, int H, const float* w_hh) {
   if (!lstm_valu(B, H) || !lstm_bwd_q_ok(H, w_hh)) return 0;
   return H <= 64 ? 16 : H <= 100 ? 25 : 32;

@@ -519,7 +519,7 @@ lstm_fwd_q_kernel(LstmFwdArgs a0, LstmFwdArgs a1) {
 
 // BR: rows of W_hh per lane of a 16-lane row (16 BR >= 4H); the body is
 // lstm_bwd_q_body (lstm_cell.hpp), shared with the BPTT + weight-gradient
-// launch of linear_kernels.hip
+// launch of linear_dw.hip
 template <int BR>
 __global__ void __launch_bounds__(kVT)
 lstm_bwd_q_kernel(LstmBwdArgs a) {

@@ -10,6 +10,7 @@
 // launches on every call and every rank, and never waits for the device.
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
+#include "dw_plan.hpp"
 #include "pol_rows.hpp"
 #include "lstm_cell.hpp"
 

@@ -63,12 +63,11 @@ struct DwEpilogue {
   const int* skip;
 };
 int dw_group_epilogue(const DwEpilogue& x);
-// an M x N weight gradient (bias column included in N) joins an open group
-bool dw_group_takes(int M, int N);
+// (whether an M x N weight gradient joins an open group: dw_group_takes, dw_plan.hpp)
 // BR of the one-segment-per-workgroup BPTT form for (B, H), 0 when another form runs
 int lstm_bwd_q_form(int B, int H, const float* w_hh);
 // the LSTM BPTT (lstm_bwd_q form) and the weight gradients queued so far in the
-// open dW group in one launch (linear_kernels.hip); SMI_E_NOFIT: run
+// open dW group in one launch (linear_dw.hip); SMI_E_NOFIT: run
 // launch_lstm_bwd instead (nothing launched)
 int launch_lstm_bwd_dw(const float* dh, const float* gates, const float* cbuf, const float* w_hh,
                        int S, int B, int H, float* dgates, hipStream_t st, const int* skip);
