@@ -15,7 +15,8 @@ ROOT = os.path.dirname(HERE)
 BUILD = os.path.join(ROOT, 'build', 'obj')
 LIB = os.path.join(HERE, 'libsurreal_mi.so')
 HEADERS = ['smi_device.hpp', 'smi_internal.hpp', 'lstm_cell.hpp', 'pol_rows.hpp', 'mt19937.hpp',
-           'gemm_args.hpp', 'dw_plan.hpp']
+           'gemm_args.hpp', 'dw_plan.hpp', 'smi_shapes.hpp', 'smi_launch.hpp', 'rnn_layout.hpp',
+           'rnn_kernels.hpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-object-version=5',
@@ -30,7 +31,8 @@ UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('sampler_kernels.hip', []), ('per_kernels.hip', []),
          ('linear_kernels.hip', []), ('linear_dw.hip', []), ('ddpg_kernels.hip', []),
          ('lstm_mfma.hip', []), ('lstm_valu.hip', ['-fno-slp-vectorize']), ('cnn_kernels.hip', []),
-         ('head_kernels.hip', []), ('ppo_rnn.hip', []), ('calib_kernels.hip', []), ('capi.hip', [])]
+         ('head_kernels.hip', []), ('ppo_rnn_kernels.hip', []), ('ppo_rnn.hip', []),
+         ('calib_kernels.hip', []), ('capi.hip', [])]
 
 
 def torch_lib_dir():

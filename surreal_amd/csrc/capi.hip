@@ -6,6 +6,7 @@
 #include <atomic>
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
+#include "rnn_layout.hpp"
 
 namespace smi {
 
@@ -90,82 +91,6 @@ float* workspace_f32(int64_t nfloats) {
   if (!c->ws || nfloats + t_ws_reserved > c->bytes / 4) return nullptr;
   return static_cast<float*>(c->ws) + t_ws_reserved;
 }
-
-// declared in the other translation units
-int launch_zfilter_apply(const float*, float*, int64_t, int, const float*, const float*,
-                         const float*, float, hipStream_t);
-int launch_colstats(const float*, int64_t, int, int64_t, int, float*, float*, float*,
-                    hipStream_t);
-int launch_reward_filter(float*, int64_t, float, int, float*, float*, float*, float, double*,
-                         hipStream_t);
-int launch_reward_filter_commit(const double*, float*, float*, float*, hipStream_t);
-int launch_layernorm_fwd(const float*, int64_t, int64_t, int, const float*, const float*, float,
-                         float*, int64_t, float*, float*, hipStream_t);
-int launch_layernorm_bwd(const float*, int64_t, const float*, int64_t, const float*, const float*,
-                         const float*, int64_t, int, int, float*, int64_t, float*, float*,
-                         hipStream_t);
-int launch_diag_gauss(const float*, const float*, const float*, int64_t, int, float*, float*,
-                      float*, float*, hipStream_t);
-int launch_mlp_forward(const float*, int, int, int, int, int, int, const float*, int64_t,
-                       int64_t, int, const float*, const float*, const float*, float, float*,
-                       hipStream_t);
-int launch_moments(const float*, int64_t, const double*, int, double*, hipStream_t);
-int launch_zfilter_tmajor(const float*, const float*, int, int, int, int, int, const float*,
-                          const float*, const float*, float, float*, int, int, hipStream_t);
-int launch_adam_clip(float*, const float*, float*, float*, int64_t, int*, const float*, float,
-                     float, float, float, float, float, const int*, float*, hipStream_t);
-int launch_mse_grad(const float*, int64_t, const float*, int64_t, float*, float*, hipStream_t);
-int launch_mse_grad_weighted(const float*, int64_t, const float*, const float*, int64_t, float*,
-                             float*, float*, hipStream_t);
-int launch_neg_mean_grad(const float*, int64_t, int64_t, float*, float*, hipStream_t);
-int launch_tanh_backward(const float*, int64_t, const float*, int64_t, int64_t, int, float*,
-                         int64_t, hipStream_t);
-int launch_copy_cols(const float*, int64_t, int64_t, int, float*, int64_t, hipStream_t);
-int launch_linear_fwd_cat(const float*, int64_t, int, int, const float*, int64_t, const float*, int,
-                          int, float*, int64_t, const float*, int64_t, int, hipStream_t);
-int launch_soft_update(float*, const float*, int64_t, float, hipStream_t);
-int launch_copy_bytes16(const void*, void*, int64_t, hipStream_t);
-int launch_copy_gather(void*, const void* const*, const int64_t*, const int64_t*, int, hipStream_t);
-bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
-                   const float* W1, const float* W2, const float* W3);
-struct PolRowArgs;
-int launch_mlp3_stacked(const float* P, int64_t pstride, const int64_t* o6, int in, int h1, int h2,
-                        int out, int act_out, const float* x, int64_t ldx, int n, float* y,
-                        int64_t ldy, hipStream_t st);
-int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, const float* W1,
-                          const float* b1, int h1, const float* W2, const float* b2, int h2,
-                          const float* W3, const float* b3, int out, int tanh_out, float* HA1,
-                          float* HA2, float* Y, int64_t ldy, float* W1T, float* W2T,
-                          hipStream_t st, const int* skip, const float* vret = nullptr,
-                          float* vgrad = nullptr, float vscale = 0.f, double* vpart = nullptr);
-int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W3,
-                          const float* W2T, const float* W1T, int h1, int h2, int dx0, int dxn,
-                          const float* HA1, const float* HA2, float* dH2, float* dH1, float* dX,
-                          int64_t lddx, const float* mask, int64_t ldm, hipStream_t st,
-                          const int* skip, const PolRowArgs* pg = nullptr);
-int head_bwd_blocks(int64_t rows);
-int launch_ddpg_stats(const float*, int64_t, int, const float*, int64_t, const float*,
-                      const float*, int64_t, int64_t, float*, hipStream_t);
-int launch_ddpg_target(const float*, const float*, const float*, const float*, int64_t, float,
-                       float*, hipStream_t);
-void mt_seed_host(uint64_t, uint32_t*);
-int mt_randint_host(uint32_t*, int64_t, int64_t, int64_t*);
-int launch_mt_randint(uint32_t*, int64_t, int64_t, int64_t*, hipStream_t);
-int launch_gather_rows(const float*, int64_t, const int64_t*, int64_t, float*, hipStream_t);
-int launch_replay_gather(const float*, int64_t, const uint8_t*, const uint8_t*, int64_t,
-                         const int64_t*, int64_t, float*, uint8_t*, uint8_t*, hipStream_t);
-int launch_zfilter_accumulate(const float*, const float*, int, float, float*, float*, float*,
-                              hipStream_t);
-int per_init_host(double*, int64_t);
-int per_set_host(double*, int64_t, const int64_t*, const double*, int64_t);
-int per_sample_host(const double*, int64_t, int64_t, uint32_t*, int64_t, double, int64_t*, float*);
-int launch_per_init(double*, int64_t, hipStream_t);
-int launch_per_set(double*, int64_t, const int64_t*, const double*, int64_t, hipStream_t);
-int launch_per_insert(double*, int64_t, int64_t, int64_t, int64_t, double, hipStream_t);
-int launch_per_update_td(double*, int64_t, const int64_t*, const float*, int64_t, int64_t, double,
-                         double, hipStream_t);
-int launch_per_sample(const double*, int64_t, int64_t, uint32_t*, int64_t, double, int64_t*, float*,
-                      hipStream_t);
 
 }  // namespace smi
 
@@ -762,15 +687,9 @@ int64_t smi_cnn_param_count(int C, int H, int W, int F) { return cnn_geom(C, H, 
 int64_t smi_ppo_rnn_xbuf_floats(int obs_dim, int rnn_hidden, int h1, int h2, int act_dim,
                                 int critic_h1, int critic_h2, int pix_c, int pix_h, int pix_w,
                                 int cnn_feat, int rnn_layer) {
-  const int F = cnn_feat > 0 ? cnn_feat : 0;
-  const int hin = rnn_hidden > 0 ? rnn_hidden : obs_dim + F;     // 0: MLP policy on the stem
-  const int nl = rnn_layer > 1 ? rnn_layer : 1;
-  const int64_t ns = (rnn_hidden > 0 ? smi_lstm_param_count(obs_dim + F, rnn_hidden) +
-                                           (nl - 1) * smi_lstm_param_count(rnn_hidden, rnn_hidden)
-                                     : 0) +
-                     (F > 0 ? smi_cnn_param_count(pix_c, pix_h, pix_w, F) : 0);
-  return mlp_layout(hin, h1, h2, act_dim, 1).fcount +
-         mlp_layout(hin, critic_h1, critic_h2, 1, 0).fcount + 2 * ns;
+  const RnnDims d = rnn_dims(1, 1, 1, obs_dim, rnn_hidden, h1, h2, act_dim, critic_h1, critic_h2,
+                             pix_c, pix_h, pix_w, cnn_feat, rnn_layer);
+  return d.nA_head + d.nC_head + 2 * d.nS;
 }
 
 int64_t smi_cnn_scratch_bytes(int64_t rows, int C, int H, int W, int F) {

@@ -28,9 +28,6 @@
 
 namespace smi {
 
-int launch_slab_reduce(const float* part, int S, int64_t n, float* out, hipStream_t st,
-                       const int* skip);
-
 __device__ __forceinline__ float u8f(unsigned u, int byte) {
   return (float)((u >> (8 * byte)) & 0xffu);
 }
@@ -427,7 +424,6 @@ static size_t cnn_bwd_lds(const CnnGeom& g) {
          4 * (size_t)(g.P1 + g.P2);
 }
 
-int cnn_bwd_grid(int64_t rows) { return (int)(rows < kCnnPartials ? rows : kCnnPartials); }
 
 int cnn_forward(const float* prm, const PixRows& pr, int C, int H, int W, int F, int64_t rows,
                 float* A1, float* A2, float* feat, int64_t ldf, hipStream_t st, const int* skip) {

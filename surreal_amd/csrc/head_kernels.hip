@@ -40,7 +40,7 @@
 
 namespace smi {
 
-constexpr int HC_R = 16;                 // rows per workgroup
+// (HC_R, rows per workgroup: smi_shapes.hpp)
 constexpr int HC_MAXK = 512;             // widest layer input / output handled here
 constexpr int HC_SR = 32 * 33 + 32;     // last-layer partials (1024) / a transpose tile (1056)
 
@@ -750,16 +750,7 @@ bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
          out >= 1 && out <= 16 && al16(X) && al16(W1) && al16(W2) && al16(W3);
 }
 
-// row tiles per workgroup: 2 (32 rows: the weight chunks feed twice the MFMAs)
-// once the batch leaves at least ~2 workgroups per CU of them, else 1
-static int hc_rt(int64_t rows) { return rows >= 16384 ? 2 : 1; }
-
-// workgroups of a fused head launch over rows (the policy prologue writes one
-// log_var partial per workgroup)
-int head_bwd_blocks(int64_t rows) {
-  const int R = HC_R * hc_rt(rows);
-  return (int)((rows + R - 1) / R);
-}
+// (hc_rt, head_bwd_blocks: smi_shapes.hpp)
 
 int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, const float* W1,
                           const float* b1, int h1, const float* W2, const float* b2, int h2,

@@ -967,8 +967,6 @@ int launch_linear_fwd(const float* X, int64_t ldx, int M, int K, const float* W,
 
 // launch_linear_fwd plus Y[:, N : N + xcols] = S[:, :xcols] (one launch on the
 // short-batch kernel, else the forward and a column copy)
-int launch_copy_cols(const float* src, int64_t lds, int64_t rows, int cols, float* dst,
-                     int64_t ldd, hipStream_t st);
 int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,
                           int64_t lds, int xcols, hipStream_t st) {

@@ -633,8 +633,6 @@ int launch_zfilter_apply(const float* x, float* out, int64_t rows, int dim, cons
 // scratch for colstats partials: caller-provided workspace is avoided by
 // bounding the partial count; the partial buffer lives in a static device
 // allocation made once at library load (see capi.cpp: smi_workspace()).
-float* workspace_f32(int64_t nfloats);
-
 int launch_colstats(const float* x, int64_t rows, int dim, int64_t stride, int mode,
                     float* osum, float* osq, float* cnt, hipStream_t st) {
   if (rows * (int64_t)dim <= (int64_t)1 << 16) {

@@ -20,16 +20,10 @@ enum {
   PS_RET,          // sum returns                                ppo.py:570
   PS_N = 8
 };
-// device control block (int / float scratch)
-enum { CI_STOP = 0, CI_RUNS, CI_NG, CI_NP, CI_COUNT = 8 };
-enum { CF_KLCOEF = 0, CF_SURRW, CF_COUNT = 8 };
-
-// fields of a packed row: A actions, 2A behaviour parameters, the advantage,
-// then the row's behaviour-policy terms, fixed for the whole learn() (the
-// behaviour parameters and the reference policy do not change across epochs):
-// the clamped behaviour likelihood and the row's KL(ref || behaviour) term,
-// computed once by row_pack_kernel instead of in every epoch's row passes
-__host__ __device__ inline int row_w(int A) { return 3 * A + 3; }
+// (the device control block CI_* / CF_* and the packed row's width row_w:
+// smi_shapes.hpp) fields of a packed row after the A actions and 2A behaviour
+// parameters: the advantage, the clamped behaviour likelihood, the row's
+// KL(ref || behaviour) term
 __host__ __device__ inline int rin_adv(int A) { return 3 * A; }
 __host__ __device__ inline int rin_bl(int A) { return 3 * A + 1; }
 __host__ __device__ inline int rin_rbd(int A) { return 3 * A + 2; }
@@ -485,7 +479,6 @@ template <int AT>
 __device__ __forceinline__ void pol_grad_compute(const PolRowArgs& a, const PolGradCols<AT>& c,
                                                  const AdvNorm& nadv, const PolGradRow<AT>& x,
                                                  float wsurr, float wkl, float* dz, float* glv) {
-  constexpr int AM = AT > 0 ? AT : 32;
   const int A = c.A;
   const float* m = x.m;
   const float* rm = x.rm;

@@ -17,6 +17,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "smi_shapes.hpp"
 
 namespace smi {
 
@@ -29,15 +30,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 enum { ACT_NONE = 0, ACT_RELU = 1, ACT_TANH = 2 };
 
-// LDS leading dimension for a K-wide row: >= roundup(K,4) and == 2 (mod 32), so
-// the A-operand column reads of a 32-lane half (16 rows at k, 16 rows at k+1)
-// land on 32 distinct banks.
-__host__ __device__ inline int pad_ld(int k) {
-  const int k4 = (k + 3) & ~3;
-  const int r = (k4 - 2) & 31;
-  return k4 + (32 - r);
-}
-__host__ __device__ inline int round4(int k) { return (k + 3) & ~3; }
+// (pad_ld, round4: smi_shapes.hpp)
 // Leading dim of narrow (<= ~16 column) output/gradient tiles: odd stride, a few
 // 2-way conflicts at most, and 3-7x less LDS than pad_ld for 1..8 columns.
 __host__ __device__ inline int pad_small(int k) { return round4(k) + 1; }
@@ -228,40 +221,7 @@ SMI_DENSE void dense_bwd_dw(const float* __restrict__ G, int ldg,
 }
 
 // ------------------------------------------------------------ MLP layouts
-// Flat (global, torch) layout and padded (LDS) layout of a 3-layer MLP
-// in -> h1 -> h2 -> out [+ log_var(out)].
-struct MlpLayout {
-  int in, h1, h2, out, lv;
-  // flat offsets
-  int fW1, fb1, fW2, fb2, fW3, fb3, flv, fcount;
-  // padded LDS offsets and leading dims
-  int ld1, ld2, ld3;
-  int pW1, pb1, pW2, pb2, pW3, pb3, plv, pcount;
-};
-
-__host__ __device__ inline MlpLayout mlp_layout(int in, int h1, int h2, int out, int lv) {
-  MlpLayout L;
-  L.in = in; L.h1 = h1; L.h2 = h2; L.out = out; L.lv = lv;
-  L.fW1 = 0;
-  L.fb1 = L.fW1 + h1 * in;
-  L.fW2 = L.fb1 + h1;
-  L.fb2 = L.fW2 + h2 * h1;
-  L.fW3 = L.fb2 + h2;
-  L.fb3 = L.fW3 + out * h2;
-  L.flv = L.fb3 + out;
-  L.fcount = L.flv + (lv ? out : 0);
-  L.ld1 = pad_ld(in); L.ld2 = pad_ld(h1); L.ld3 = pad_ld(h2);
-  L.pW1 = 0;
-  L.pb1 = L.pW1 + h1 * L.ld1;
-  L.pW2 = round4(L.pb1 + h1);
-  L.pb2 = L.pW2 + h2 * L.ld2;
-  L.pW3 = round4(L.pb2 + h2);
-  L.pb3 = L.pW3 + out * L.ld3;
-  L.plv = round4(L.pb3 + out);
-  L.pcount = round4(L.plv + (lv ? out : 0));
-  return L;
-}
-
+// (MlpLayout, mlp_layout: smi_shapes.hpp)
 // flat index -> padded index
 __device__ inline int mlp_flat_to_pad(const MlpLayout& L, int i) {
   if (i < L.fb1) { const int n = i / L.in; return L.pW1 + n * L.ld1 + (i - n * L.in); }

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/surreal_mi.h"
+#include "smi_shapes.hpp"
 
 namespace smi {
 
@@ -90,32 +91,9 @@ constexpr int fault() { return SMI_FAULT_NONE; }
 
 #define RC_CHECK(x) do { const int rc_ = (x); if (rc_) return rc_; } while (0)
 
-// ---- pixel stem (CNNStemNetwork, builders.py:8-33) -------------------------
-// Flat parameter layout (torch Conv2d / Linear shapes, in module order):
-// [conv1.weight (16,C,8,8) | conv1.bias (16) | conv2.weight (32,16,4,4) |
-//  conv2.bias (32) | fc.weight (F, 32*H2*W2) | fc.bias (F)]
-struct CnnGeom {
-  int C, H, W, H1, W1, P1, H2, W2, P2, K1, flat, F;
-  int64_t img;                                  // bytes per uint8 image
-  int64_t oW1, ob1, oW2, ob2, oWf, obf, total;  // offsets (floats)
-  int64_t nconv;                                // conv parameters = oWf
-};
-__host__ __device__ inline CnnGeom cnn_geom(int C, int H, int W, int F) {
-  CnnGeom g;
-  g.C = C; g.H = H; g.W = W; g.F = F;
-  g.H1 = (H - 8) / 4 + 1; g.W1 = (W - 8) / 4 + 1; g.P1 = g.H1 * g.W1;
-  g.H2 = (g.H1 - 4) / 2 + 1; g.W2 = (g.W1 - 4) / 2 + 1; g.P2 = g.H2 * g.W2;
-  g.K1 = 64 * C; g.flat = 32 * g.P2;
-  g.img = (int64_t)C * H * W;
-  g.oW1 = 0; g.ob1 = 16 * (int64_t)g.K1; g.oW2 = g.ob1 + 16; g.ob2 = g.oW2 + 32 * 256;
-  g.oWf = g.ob2 + 32; g.obf = g.oWf + (int64_t)F * g.flat; g.total = g.obf + F;
-  g.nconv = g.oWf;
-  return g;
-}
+// ---- pixel stem (CnnGeom, cnn_geom, cnn_bwd_grid: smi_shapes.hpp) ------------
 // image of activation row n = t*B + b: t < T -> pix[b][t], else pix_next[b]
 struct PixRows { const unsigned char* pix; const unsigned char* pix_next; int64_t B, T, img_bytes; };
-constexpr int kCnnPartials = 512;               // max workgroups (partial slabs) of the backward
-int cnn_bwd_grid(int64_t rows);
 int cnn_forward(const float* prm, const PixRows& pr, int C, int H, int W, int F, int64_t rows,
                 float* A1, float* A2, float* feat, int64_t ldf, hipStream_t st, const int* skip);
 // dz: gradient at the Linear pre-activation (ReLU mask applied), rows x F
@@ -184,3 +162,5 @@ int launch_lstm_bwd(const float* dh, const float* gates, const float* cbuf, cons
                     int S, int B, int H, float* dgates, hipStream_t st, const int* skip);
 
 }  // namespace smi
+
+#include "smi_launch.hpp"
