@@ -774,6 +774,41 @@ int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
                       int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
                       void* stream);
 
+/* Frame-shared pixel replay.  Every frame (fbytes uint8) is kept once in
+ * `store`; fid[slot][side][k] (int32, [slots][2][stack]) names the store slot
+ * of stack position k of obs (side 0) and obs_next (side 1) of a transition.
+ *
+ * smi_replay_gather_shared, one launch, the outputs of smi_replay_gather:
+ *   pix_out[i]      = store[fid[idx[i]][0][0]] | ... | store[fid[idx[i]][0][stack-1]]
+ *   pix_next_out[i] = the same from side 1      (stack * fbytes uint8 each)
+ *   rows_out[i]     = table[idx[i]]             (cols floats; skipped when cols == 0)
+ * Source offsets are 64-bit (stores beyond 4 GiB).  Frames move as 16-byte
+ * vectors when fbytes % 16 == 0 and store, pix_out and pix_next_out are
+ * 16-byte aligned, as bytes otherwise.  The indices AND the fid entries are
+ * trusted (0 <= idx[i] < ring slots, 0 <= fid < store slots).  batch == 0
+ * returns SMI_OK without a launch; NULL store, fid, idx or pixel outputs, stack
+ * outside [1, 4], fbytes outside [1, 2^31 / stack), batch < 0, cols < 0, or
+ * cols > 0 with a NULL table / rows_out are SMI_E_ARG.
+ *
+ * smi_replay_insert_shared, one launch, all sources in device memory:
+ *   store[fslots[j]] = frames[j]                       j < m (fslots distinct)
+ *   table[s(e)] = rows[e], fid[s(e)] = ids[e]          s(e) = (first_slot + e) %
+ *       memory_size for the last min(n, memory_size) of e < n (the wrap rule of
+ *       smi_per_insert); ids is int32 [n][2][stack]
+ * n == 0 and m == 0 returns SMI_OK without a launch.  NULL store or fid, stack
+ * and fbytes as above, n < 0, m < 0, cols < 0, memory_size < 1, first_slot
+ * outside [0, memory_size), n > 0 with NULL ids (or, cols > 0, NULL table /
+ * rows), m > 0 with NULL frames / fslots are SMI_E_ARG.  fslots are trusted. */
+int smi_replay_gather_shared(const float* table, int64_t cols, const uint8_t* store,
+                             const int32_t* fid, int stack, int64_t fbytes, const int64_t* idx,
+                             int64_t batch, float* rows_out, uint8_t* pix_out,
+                             uint8_t* pix_next_out, void* stream);
+int smi_replay_insert_shared(float* table, int64_t cols, int32_t* fid, int stack, uint8_t* store,
+                             int64_t fbytes, int64_t memory_size, int64_t first_slot,
+                             const float* rows, const int32_t* ids, int64_t n,
+                             const uint8_t* frames, const int32_t* fslots, int64_t m,
+                             void* stream);
+
 /* ------------------------------------------------- prioritized replay */
 /* Proportional prioritized replay (replay/prioritized_replay.py +
  * replay/segment_tree.py, read as the openai/baselines code they were adapted

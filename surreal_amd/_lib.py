@@ -187,6 +187,9 @@ _SIGS = {
     'smi_mt_randint': (c_int, [P, c_i64, c_i64, P, P]),
     'smi_gather_rows': (c_int, [P, c_i64, P, c_i64, P, P]),
     'smi_replay_gather': (c_int, [P, c_i64, P, P, c_i64, P, c_i64, P, P, P, P]),
+    'smi_replay_gather_shared': (c_int, [P, c_i64, P, P, c_int, c_i64, P, c_i64, P, P, P, P]),
+    'smi_replay_insert_shared': (c_int, [P, c_i64, P, c_int, P, c_i64, c_i64, c_i64, P, P, c_i64,
+                                         P, P, c_i64, P]),
     'smi_per_tree_doubles': (c_i64, [c_i64]),
     'smi_per_init': (c_int, [P, c_i64, P]),
     'smi_per_set': (c_int, [P, c_i64, P, P, c_i64, P]),

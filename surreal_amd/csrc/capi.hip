@@ -586,6 +586,43 @@ int smi_replay_gather(const float* table, int64_t cols, const uint8_t* frames,
                               pix_out, pix_next_out, SMI_STREAM(stream));
 }
 
+#define SHARED_FRAME_ARGS(name) \
+  REQUIRE(stack >= 1 && stack <= 4, name ": stack outside [1, 4]"); \
+  REQUIRE(fbytes >= 1 && fbytes < ((int64_t)1 << 31) / stack, name ": fbytes outside [1, 2^31 / stack)")
+
+int smi_replay_gather_shared(const float* table, int64_t cols, const uint8_t* store,
+                             const int32_t* fid, int stack, int64_t fbytes, const int64_t* idx,
+                             int64_t batch, float* rows_out, uint8_t* pix_out,
+                             uint8_t* pix_next_out, void* stream) {
+  REQUIRE(store && fid && pix_out && pix_next_out && idx,
+          "replay_gather_shared: null store, ids, output or index pointer");
+  SHARED_FRAME_ARGS("replay_gather_shared");
+  REQUIRE(batch >= 0 && cols >= 0, "replay_gather_shared: batch < 0 or cols < 0");
+  REQUIRE(cols == 0 || (table && rows_out),
+          "replay_gather_shared: cols > 0 needs table and rows_out");
+  if (batch == 0) return SMI_OK;
+  return launch_replay_gather_shared(table, cols, store, fid, stack, fbytes, idx, batch, rows_out,
+                                     pix_out, pix_next_out, SMI_STREAM(stream));
+}
+
+int smi_replay_insert_shared(float* table, int64_t cols, int32_t* fid, int stack, uint8_t* store,
+                             int64_t fbytes, int64_t memory_size, int64_t first_slot,
+                             const float* rows, const int32_t* ids, int64_t n,
+                             const uint8_t* frames, const int32_t* fslots, int64_t m,
+                             void* stream) {
+  REQUIRE(store && fid, "replay_insert_shared: null store or ids ring");
+  SHARED_FRAME_ARGS("replay_insert_shared");
+  REQUIRE(n >= 0 && m >= 0 && cols >= 0, "replay_insert_shared: n < 0, m < 0 or cols < 0");
+  REQUIRE(memory_size >= 1 && first_slot >= 0 && first_slot < memory_size,
+          "replay_insert_shared: memory_size < 1 or first_slot outside [0, memory_size)");
+  REQUIRE(n == 0 || (ids && (cols == 0 || (table && rows))),
+          "replay_insert_shared: n > 0 needs ids and, with cols > 0, table and rows");
+  REQUIRE(m == 0 || (frames && fslots), "replay_insert_shared: m > 0 needs frames and fslots");
+  if (n == 0 && m == 0) return SMI_OK;
+  return launch_replay_insert_shared(table, cols, fid, stack, store, fbytes, memory_size, first_slot,
+                                     rows, ids, n, frames, fslots, m, SMI_STREAM(stream));
+}
+
 /* -------------------------------------------------- prioritized replay */
 #define PER_CAP(name, capacity) \
   REQUIRE((capacity) >= 1 && (capacity) <= ((int64_t)1 << 30) && ((capacity) & ((capacity) - 1)) == 0, \

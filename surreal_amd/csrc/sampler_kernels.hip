@@ -1,6 +1,7 @@
 // sampler_kernels.hip — CPython-exact uniform replay index sampling and the
 // replay row gather (UniformReplay.sample, surreal/replay/uniform_replay.py:43-47),
-// and the pixel replay's fused frame + row gather (UniformReplay.sample_batch).
+// and the pixel replay's fused frame + row gather (UniformReplay.sample_batch),
+// with the gather and the insert scatter of its frame-shared store.
 //
 // The reference draws [random.randint(0, n-1) for _ in range(B)] from the
 // Python stdlib generator: MT19937 (Matsumoto & Nishimura 1998) seeded by
@@ -318,6 +319,197 @@ int launch_replay_gather(const float* table, int64_t cols, const uint8_t* frames
                        frames, frames_next, frame_bytes, idx, batch, rows_out, pix_out,
                        pix_next_out, cpf);
   return check_launch("replay_gather_kernel");
+}
+
+// ------------------------------------- replay gather (frame-shared store)
+// The frame-shared pixel replay keeps every (C/S, H, W) frame once in `store`
+// and names the S frames of each observation in fid[slot][side][k].  The
+// sample is the same output as replay_gather_kernel: pix_out[i] = the S frames
+// fid[idx[i]][0][:] one after the other, pix_next_out[i] from side 1.
+//
+// A work item is (sample, side, chunk) of the DESTINATION side (S * fbytes
+// bytes), chunked as above, so the chunks stay full where a 21,168-byte frame
+// alone would leave every second one 29 % full.  idx[i], the S ids of the side
+// (one dependent load of 4 S bytes) and the S source offsets are workgroup-
+// uniform; a lane picks its source frame from its destination vector index
+// (compares against multiples of the vectors per frame, no divide) and frame
+// boundaries fall on vector boundaries because fbytes % 16 == 0.  Every lane
+// issues its kRgU loads before its first store; tail lanes re-read the side's
+// last vector and skip the store.  Source offsets are 64-bit (the reference
+// store, 416,666 x 21,168 B, is 8.8 GB).
+constexpr int kRgMaxStack = 4;
+
+// STACK = S is a template parameter: the S ids of a side are one block of
+// scalar loads and a lane's source frame is picked by S - 1 selects, no branch.
+template <bool VEC, int STACK>
+__global__ void __launch_bounds__(kWG)
+replay_gather_shared_kernel(const float* __restrict__ table, int64_t cols,
+                            const uint8_t* __restrict__ store, const int32_t* __restrict__ fid,
+                            int64_t fbytes, const int64_t* __restrict__ idx, int64_t batch,
+                            float* __restrict__ rows_out, uint8_t* __restrict__ pix_out,
+                            uint8_t* __restrict__ pix_next_out, int64_t cps) {
+  const int64_t items = batch * 2 * cps;
+  const int64_t side_bytes = STACK * fbytes;            // < 2^31 (checked by the entry point)
+  for (int64_t it = blockIdx.x; it < items; it += gridDim.x) {
+    const int64_t s = it / cps, chunk = it - s * cps;
+    const int64_t i = s >> 1;
+    const bool nxt = (s & 1) != 0;
+    const int32_t* ids = fid + (idx[i] * 2 + (nxt ? 1 : 0)) * STACK;
+    int64_t off[STACK];                                  // byte offset of frame k in the store
+#pragma unroll
+    for (int k = 0; k < STACK; ++k) off[k] = (int64_t)ids[k] * fbytes;
+    uint8_t* dst = (nxt ? pix_next_out : pix_out) + i * side_bytes;
+    if constexpr (VEC) {
+      u32x4* d4 = reinterpret_cast<u32x4*>(dst);
+      const int nvf = (int)(fbytes >> 4);          // vectors per frame
+      const int nvec = STACK * nvf;                // vectors per side
+      const int v0 = (int)chunk * kRgChunk + (int)threadIdx.x;
+      u32x4 v[kRgU];
+#pragma unroll
+      for (int u = 0; u < kRgU; ++u) {
+        // Tail lanes load the side's last vector (in bounds, unconditional) and
+        // skip the store.
+        const int e = min(v0 + u * kWG, nvec - 1);
+        int64_t o = off[0];
+        int r = e;
+#pragma unroll
+        for (int k = 1; k < STACK; ++k) {
+          const bool past = e >= k * nvf;
+          o = past ? off[k] : o;
+          r = past ? e - k * nvf : r;
+        }
+        v[u] = *reinterpret_cast<const u32x4*>(store + o + ((int64_t)r << 4));
+      }
+#pragma unroll
+      for (int u = 0; u < kRgU; ++u) {
+        const int e = v0 + u * kWG;
+        if (e < nvec) d4[e] = v[u];
+      }
+    } else {
+      const int64_t b0 = chunk * kRgChunk * 16;
+      const int64_t b1 = b0 + kRgChunk * 16 < side_bytes ? b0 + kRgChunk * 16 : side_bytes;
+      for (int64_t b = b0 + threadIdx.x; b < b1; b += kWG) {
+        int64_t o = off[0], r = b;
+#pragma unroll
+        for (int k = 1; k < STACK; ++k) {
+          const bool past = b >= k * fbytes;
+          o = past ? off[k] : o;
+          r = past ? b - k * fbytes : r;
+        }
+        dst[b] = store[o + r];
+      }
+    }
+  }
+  if (cols > 0) gather_rows_side(table, cols, idx, batch, rows_out);
+}
+
+template <bool VEC>
+static void launch_rgs(int stack, int g, hipStream_t s, const float* table, int64_t cols,
+                       const uint8_t* store, const int32_t* fid, int64_t fbytes, const int64_t* idx,
+                       int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
+                       int64_t cps) {
+#define SMI_RGS(S) \
+  hipLaunchKernelGGL((replay_gather_shared_kernel<VEC, S>), dim3(g), dim3(kWG), 0, s, table, cols, \
+                     store, fid, fbytes, idx, batch, rows_out, pix_out, pix_next_out, cps)
+  switch (stack) {
+    case 1: SMI_RGS(1); break;
+    case 2: SMI_RGS(2); break;
+    case 3: SMI_RGS(3); break;
+    default: SMI_RGS(4); break;
+  }
+#undef SMI_RGS
+}
+
+int launch_replay_gather_shared(const float* table, int64_t cols, const uint8_t* store,
+                                const int32_t* fid, int stack, int64_t fbytes, const int64_t* idx,
+                                int64_t batch, float* rows_out, uint8_t* pix_out,
+                                uint8_t* pix_next_out, hipStream_t s) {
+  if (batch <= 0) return SMI_OK;
+  if (stack < 1 || stack > kRgMaxStack)
+    return set_error(SMI_E_ARG, "replay_gather_shared: stack outside [1, 4]");
+  const uintptr_t al = reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(pix_out) |
+                       reinterpret_cast<uintptr_t>(pix_next_out);
+  const bool vec = (fbytes & 15) == 0 && (al & 15) == 0;
+  const int64_t side_bytes = (int64_t)stack * fbytes;
+  const int64_t cps = (side_bytes + kRgChunk * 16 - 1) / (kRgChunk * 16);
+  int64_t g = batch * 2 * cps;
+  if (g > 4096) g = 4096;
+  if (vec)
+    launch_rgs<true>(stack, (int)g, s, table, cols, store, fid, fbytes, idx, batch, rows_out, pix_out,
+                     pix_next_out, cps);
+  else
+    launch_rgs<false>(stack, (int)g, s, table, cols, store, fid, fbytes, idx, batch, rows_out,
+                      pix_out, pix_next_out, cps);
+  return check_launch("replay_gather_shared_kernel");
+}
+
+// ------------------------------------- replay insert (frame-shared store)
+// One launch per insert call, reading one staged block: the m new frames go
+// to store[fslots[j]] (16-byte vectors when fbytes % 16 == 0 and both frame
+// pointers are aligned, bytes otherwise; no two fslots are equal, the host
+// allocator hands a slot out once per call), and the last cnt = min(n,
+// memory_size) of the n rows and of their [2][S] frame ids go to the ring
+// slots (first_slot + e) % memory_size, e = n - cnt .. n - 1 (the wrap rule of
+// launch_per_insert).  Flat grid-stride loops: the insert is bound by the
+// host-to-device copy in front of it, not by this kernel.
+template <bool VEC>
+__global__ void __launch_bounds__(kWG)
+replay_insert_shared_kernel(float* __restrict__ table, int64_t cols, int32_t* __restrict__ fid,
+                            int64_t ids_per_row, uint8_t* __restrict__ store, int64_t fbytes,
+                            int64_t memory_size, int64_t first_slot,
+                            const float* __restrict__ rows, const int32_t* __restrict__ ids,
+                            int64_t n, int64_t cnt, const uint8_t* __restrict__ frames,
+                            const int32_t* __restrict__ fslots, int64_t m) {
+  const int64_t stride = (int64_t)gridDim.x * kWG;
+  const int64_t t0 = (int64_t)blockIdx.x * kWG + threadIdx.x;
+  if constexpr (VEC) {
+    const int64_t nvf = fbytes >> 4;
+    const u32x4* f4 = reinterpret_cast<const u32x4*>(frames);
+    for (int64_t e = t0; e < m * nvf; e += stride) {
+      const int64_t j = e / nvf, r = e - j * nvf;
+      reinterpret_cast<u32x4*>(store + (int64_t)fslots[j] * fbytes)[r] = f4[e];
+    }
+  } else {
+    for (int64_t e = t0; e < m * fbytes; e += stride) {
+      const int64_t j = e / fbytes, r = e - j * fbytes;
+      store[(int64_t)fslots[j] * fbytes + r] = frames[e];
+    }
+  }
+  const int64_t skip = n - cnt;
+  for (int64_t e = t0; e < cnt * cols; e += stride) {
+    const int64_t r = skip + e / cols, c = e % cols;
+    table[((first_slot + r) % memory_size) * cols + c] = rows[r * cols + c];
+  }
+  for (int64_t e = t0; e < cnt * ids_per_row; e += stride) {
+    const int64_t r = skip + e / ids_per_row, c = e % ids_per_row;
+    fid[((first_slot + r) % memory_size) * ids_per_row + c] = ids[r * ids_per_row + c];
+  }
+}
+
+int launch_replay_insert_shared(float* table, int64_t cols, int32_t* fid, int stack, uint8_t* store,
+                                int64_t fbytes, int64_t memory_size, int64_t first_slot,
+                                const float* rows, const int32_t* ids, int64_t n,
+                                const uint8_t* frames, const int32_t* fslots, int64_t m,
+                                hipStream_t s) {
+  if (n <= 0 && m <= 0) return SMI_OK;
+  const int64_t cnt = n < memory_size ? n : memory_size;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(store) | reinterpret_cast<uintptr_t>(frames);
+  const bool vec = (fbytes & 15) == 0 && (al & 15) == 0;
+  int64_t work = vec ? m * (fbytes >> 4) : m * fbytes;
+  if (cnt * cols > work) work = cnt * cols;
+  if (cnt * 2 * stack > work) work = cnt * 2 * stack;
+  int64_t g = (work + kWG - 1) / kWG;
+  if (g > 4096) g = 4096;
+  if (g < 1) g = 1;
+  if (vec)
+    hipLaunchKernelGGL(replay_insert_shared_kernel<true>, dim3((int)g), dim3(kWG), 0, s, table, cols,
+                       fid, (int64_t)2 * stack, store, fbytes, memory_size, first_slot, rows, ids, n,
+                       cnt, frames, fslots, m);
+  else
+    hipLaunchKernelGGL(replay_insert_shared_kernel<false>, dim3((int)g), dim3(kWG), 0, s, table, cols,
+                       fid, (int64_t)2 * stack, store, fbytes, memory_size, first_slot, rows, ids, n,
+                       cnt, frames, fslots, m);
+  return check_launch("replay_insert_shared_kernel");
 }
 
 }  // namespace smi

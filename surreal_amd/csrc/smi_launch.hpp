@@ -97,6 +97,15 @@ int launch_replay_gather(const float* table, int64_t cols, const uint8_t* frames
                          const uint8_t* frames_next, int64_t frame_bytes, const int64_t* idx,
                          int64_t batch, float* rows_out, uint8_t* pix_out, uint8_t* pix_next_out,
                          hipStream_t s);
+int launch_replay_gather_shared(const float* table, int64_t cols, const uint8_t* store,
+                                const int32_t* fid, int stack, int64_t fbytes, const int64_t* idx,
+                                int64_t batch, float* rows_out, uint8_t* pix_out,
+                                uint8_t* pix_next_out, hipStream_t s);
+int launch_replay_insert_shared(float* table, int64_t cols, int32_t* fid, int stack, uint8_t* store,
+                                int64_t fbytes, int64_t memory_size, int64_t first_slot,
+                                const float* rows, const int32_t* ids, int64_t n,
+                                const uint8_t* frames, const int32_t* fslots, int64_t m,
+                                hipStream_t s);
 // ---- per_kernels.hip
 int per_init_host(double* tree, int64_t cap);
 int per_set_host(double* tree, int64_t cap, const int64_t* idx, const double* leaf, int64_t n);

@@ -22,6 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from .frame_store import FrameAllocator, frame_sharing, split_camera
 
 
 class CPythonRandom(object):
@@ -106,9 +107,24 @@ class UniformReplay(object):
     before and after each transition; D is the low-dim width and may be 0
     (W = A + 2).  The three rings always advance together.  The frame rings
     take 2 * memory_size * C*H*W bytes: 42 GB at the reference defaults
-    (memory_size 333,333, 9 x 84 x 84).  Every transition stores both of its
-    frames; sharing a frame between consecutive transitions (the reference
-    sender's hash dedup) is out of scope."""
+    (memory_size 333,333, 9 x 84 x 84), because every transition stores both
+    of its observations whole.
+
+    Frame-shared pixel mode (learner_config.replay.share_frames = True) keeps
+    every camera frame once, as the reference sender's per-frame hashing does
+    (distributed/exp_sender.py:45-59).  With S = env_config.frame_stacks an
+    observation is S frames of (C/S, H, W); `frame_store`, uint8 (frame_slots,
+    C/S, H, W), holds each distinct frame once and `frame_ids`, int32
+    (memory_size, 2, S), names the store slots of obs and obs_next of every
+    transition; `frames` and `frames_next` do not exist.  frame_slots is
+    learner_config.replay.frame_slots, by default memory_size + memory_size //
+    4: 8.8 GB at the reference defaults.  The host side (frame_store.py:
+    digests, reference counts, free list) decides which frames of an insert
+    are new; those, the rows and the ids go up in one pinned buffer, one copy
+    and one launch (smi_replay_insert_shared), and sample_batch() gathers
+    through the ids (smi_replay_gather_shared) into the same batch.  Sampling
+    draws transition slots, which have not moved, so it is unchanged.  A full
+    store raises RuntimeError and leaves the replay as it was."""
 
     def __init__(self, learner_config, env_config, session_config=None, index=0, seed=0,
                  device=None):
@@ -130,6 +146,11 @@ class UniformReplay(object):
                                  device=self.device)
         if self.is_pixel:
             self.frame_bytes = int(np.prod(self.camera_shape))
+        self.share_frames = False
+        shared = frame_sharing(learner_config, env_config)
+        if shared is not None:
+            self._init_shared(*shared)
+        elif self.is_pixel:
             self.frames = torch.zeros((self.memory_size,) + self.camera_shape, dtype=torch.uint8,
                                       device=self.device)
             self.frames_next = torch.zeros_like(self.frames)
@@ -138,6 +159,26 @@ class UniformReplay(object):
         self.rng = CPythonRandom(seed, self.device)
         self._idx = None
         self._out = None
+
+    def _init_shared(self, stack, frame_shape, frame_slots):
+        self.share_frames = True
+        self.frame_stacks, self.frame_shape = stack, frame_shape
+        self.fbytes = int(np.prod(frame_shape))
+        self._alloc = FrameAllocator(self.memory_size, frame_slots, stack)
+        self.frame_store = torch.zeros((frame_slots,) + frame_shape, dtype=torch.uint8,
+                                       device=self.device)
+        self.frame_ids = torch.zeros(self.memory_size, 2, stack, dtype=torch.int32,
+                                     device=self.device)
+        self._stage = None                 # (pinned host bytes, device bytes, copy-done event)
+
+    @property
+    def frame_slots(self):
+        return self._alloc.frame_slots
+
+    @property
+    def frames_in_use(self):
+        """store slots that hold a frame some live transition names"""
+        return self._alloc.frames_in_use
 
     def __len__(self):
         return self._len
@@ -151,6 +192,8 @@ class UniformReplay(object):
         self.insert_rows(row)
 
     def pack(self, exps):
+        if self.share_frames:
+            return self._pack_shared(exps)
         if self.is_pixel:
             return pack_pixel_exps(exps, self.obs_dim, self.act_dim, self.camera_shape)
         D, A = self.obs_dim, self.act_dim
@@ -165,9 +208,98 @@ class UniformReplay(object):
             out[i, 2 * D + A + 1] = float(e['done'])
         return out
 
+    def _pack_shared(self, exps):
+        """pack() of the frame-shared mode: (rows, frames of obs, frames of
+        obs_next), the frames as one list of S uint8 arrays per experience.
+        camera0 may be a list of S frames or one (C, H, W) array; an object
+        that several experiences share comes back as the same arrays, so
+        insert_rows digests it once."""
+        D, A, S = self.obs_dim, self.act_dim, self.frame_stacks
+        rows = np.zeros((len(exps), self.width), dtype=np.float32)
+        pix, pix_next, cache = [], [], {}
+        for i, e in enumerate(exps):
+            o0, o1 = e['obs']
+            if D:
+                rows[i, :D] = _low_dim(o0)
+                rows[i, D + A + 1:2 * D + A + 1] = _low_dim(o1)
+            rows[i, D:D + A] = e['action']
+            rows[i, D + A] = e['reward']
+            rows[i, 2 * D + A + 1] = float(e['done'])
+            pix.append(split_camera(o0['pixel']['camera0'], S, self.frame_shape, cache))
+            pix_next.append(split_camera(o1['pixel']['camera0'], S, self.frame_shape, cache))
+        return rows, pix, pix_next
+
+    def _side_frames(self, name, pix, n):
+        """one side of insert_rows -> n lists of S contiguous uint8 frames"""
+        S = self.frame_stacks
+        if isinstance(pix, (list, tuple)) and (not len(pix) or isinstance(pix[0], (list, tuple))):
+            if len(pix) != n:
+                raise ValueError(f'{name} holds {len(pix)} observations for {n} rows')
+            return [split_camera(f, S, self.frame_shape) for f in pix]
+        t = torch.as_tensor(pix)
+        if t.dtype != torch.uint8 or tuple(t.shape) != (n,) + self.camera_shape:
+            raise ValueError(f'{name} must be uint8 {(n,) + self.camera_shape}, got '
+                             f'{t.dtype} {tuple(t.shape)}')
+        a = np.ascontiguousarray(t.cpu().numpy()).reshape((n, S) + self.frame_shape)
+        return [[a[i, k] for k in range(S)] for i in range(n)]
+
+    def _insert_shared(self, rows, pix, pix_next):
+        rows = np.ascontiguousarray(torch.as_tensor(rows, dtype=torch.float32).cpu().numpy())
+        n = rows.shape[0]
+        if pix is None or pix_next is None:
+            raise ValueError('a pixel replay inserts rows together with pix and pix_next')
+        if tuple(rows.shape) != (n, self.width):
+            raise ValueError(f'rows must be ({n}, {self.width}), got {tuple(rows.shape)}')
+        skip = max(0, n - self.memory_size)
+        sides = list(zip(self._side_frames('pix', pix, n)[skip:],
+                         self._side_frames('pix_next', pix_next, n)[skip:]))
+        # raises RuntimeError, with nothing changed, when the store is full
+        first, ids, fslots, new = self._alloc.insert(sides, skipped=skip)
+        cnt, m, fb = n - skip, len(new), self.fbytes
+        # one pinned block [new frames | rows | ids | fslots], the float and
+        # int parts from a 16-byte boundary on
+        o_rows = (m * fb + 15) // 16 * 16
+        o_ids = o_rows + cnt * self.width * 4
+        o_slots = o_ids + ids.size * 4
+        total = o_slots + m * 4
+        if total:
+            if self._stage is None or self._stage[0].numel() < total:
+                cap = max(total, 2 * self._stage[0].numel() if self._stage else 0)
+                if self._stage is not None and self._stage[2] is not None:
+                    self._stage[2].synchronize()
+                self._stage = (torch.empty(cap, dtype=torch.uint8).pin_memory(),
+                               torch.empty(cap, dtype=torch.uint8, device=self.device), None)
+            host, dev, done = self._stage
+            if done is not None:
+                done.synchronize()         # the previous copy has read the pinned block
+            h = host.numpy()
+            for j, f in enumerate(new):
+                h[j * fb:(j + 1) * fb] = f.reshape(-1)
+            h[o_rows:o_ids].view(np.float32)[:] = rows[skip:].reshape(-1)
+            h[o_ids:o_slots].view(np.int32)[:] = ids.reshape(-1)
+            h[o_slots:total].view(np.int32)[:] = fslots
+            dev[:total].copy_(host[:total], non_blocking=True)
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.device))
+            self._stage = (host, dev, done)
+            base = dev.data_ptr()
+
+            def at(off, count):
+                return ctypes.c_void_p(base + off) if count else None
+            L.call('smi_replay_insert_shared', L.ptr(self.table), self.width,
+                   L.ptr(self.frame_ids), self.frame_stacks, L.ptr(self.frame_store), fb,
+                   self.memory_size, first, at(o_rows, cnt), at(o_ids, cnt), cnt, at(0, m),
+                   at(o_slots, m), m, L.stream(self.device))
+        self._len = min(self.memory_size, self._len + n)
+        self._next_idx = int((self._next_idx + n) % self.memory_size)
+
     def insert_rows(self, rows, pix=None, pix_next=None):
         """Bulk ring insert of packed rows (same slot sequence as repeated insert);
-        pixel mode: with their uint8 (n, C, H, W) frames."""
+        pixel mode: with their uint8 (n, C, H, W) frames.  Frame-shared mode
+        also takes what its pack() returns (per experience a list of S frames)
+        and stores only the frames the store does not hold yet."""
+        if self.share_frames:
+            return self._insert_shared(rows, pix, pix_next)
         rows = torch.as_tensor(rows, dtype=torch.float32)
         n = rows.shape[0]
         if self.is_pixel:
@@ -232,7 +364,8 @@ class UniformReplay(object):
         """Returns (indices, batch): the draw of sample() (same CPython-exact
         stream, same rank slicing) gathered into the batch DDPGLearner.learn()
         takes.  Low-dim: split(rows), one smi_gather_rows.  Pixel: one
-        smi_replay_gather moves this rank's rows and both frames of each;
+        smi_replay_gather (frame-shared: smi_replay_gather_shared, through the
+        frame ids) moves this rank's rows and both frames of each;
         batch = {'obs': {'pixel': {'camera0': u8 [n, C, H, W]}, 'low_dim':
         {'flat_inputs': [n, D]}}, 'obs_next': likewise, 'actions', 'rewards',
         'dones'} ('low_dim' omitted when D == 0).  The output buffers are
@@ -253,9 +386,14 @@ class UniformReplay(object):
         rows, pix, pix_next = self._out
         idx = self.sample_indices(batch_size)
         mine = idx[rank * n:(rank + 1) * n]
-        L.call('smi_replay_gather', L.ptr(self.table), self.width, L.ptr(self.frames),
-               L.ptr(self.frames_next), self.frame_bytes, L.ptr(mine), n, L.ptr(rows), L.ptr(pix),
-               L.ptr(pix_next), L.stream(self.device))
+        if self.share_frames:
+            L.call('smi_replay_gather_shared', L.ptr(self.table), self.width,
+                   L.ptr(self.frame_store), L.ptr(self.frame_ids), self.frame_stacks, self.fbytes,
+                   L.ptr(mine), n, L.ptr(rows), L.ptr(pix), L.ptr(pix_next), L.stream(self.device))
+        else:
+            L.call('smi_replay_gather', L.ptr(self.table), self.width, L.ptr(self.frames),
+                   L.ptr(self.frames_next), self.frame_bytes, L.ptr(mine), n, L.ptr(rows),
+                   L.ptr(pix), L.ptr(pix_next), L.stream(self.device))
         flat = self.split(rows)
         obs, obs_next = {'pixel': {'camera0': pix}}, {'pixel': {'camera0': pix_next}}
         if self.obs_dim:

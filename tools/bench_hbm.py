@@ -20,6 +20,16 @@ the algorithmic bytes are the §8(d) per-unit figures:
   replay_gather (9x84x84 u8, W=42)  8 idx + 2 sides x 2 x 63504 B + 2 x 4 W B per sample (B = 512,
                                     8,192-slot rings); replay_gather_baseline3 is the same
                                     gather as two torch.index_select + one smi_gather_rows
+  replay_gather_shared              the same sample from the frame-shared store (3x84x84 frames,
+                                    S = 3, ids of a rolling stream: the two sides of a transition
+                                    share two frames): 8 idx + 2 x S x 4 id B + 2 sides x 2 x
+                                    63504 B + 2 x 4 W B per sample; replay_gather_shared_distinct
+                                    gives every transition 2 S frames of its own (a store as
+                                    large as the two rings, no frame read twice)
+  replay_insert                     host wall time of one insert call of 64 rolling-stream
+                                    transitions of 9x84x84 ending in a synchronise, frame-shared
+                                    against unshared, with the bytes each uploads and the host
+                                    time of the digests
   moments                           4 B per element
 
 peak = 8000 GB/s (MI355X HBM3E spec, MI355X_MICROARCH.md).  Prints one JSON line
@@ -208,6 +218,96 @@ def main():
                    calib_stream_GBs=round(calib, 1),
                    frac_of_calib_stream=round(nbytes / (med * 1e-3) / 1e9 / calib, 4))
         del fr, fn_, tab, sets, rows, po, pn
+
+    if want('replay_gather_shared'):
+        # the protocol of replay_gather on the frame-shared store
+        slots, batch, W, S = 8192, 512, 42, 3
+        fbytes = 3 * 84 * 84
+        tab = torch.randn(slots, W, device=dev, generator=g)
+        sets = torch.randperm(slots, device=dev, generator=g).view(slots // batch, batch)
+        rows = torch.empty(batch, W, device=dev)
+        po = torch.empty(batch, S * fbytes, dtype=torch.uint8, device=dev)
+        pn = torch.empty(batch, S * fbytes, dtype=torch.uint8, device=dev)
+        nbytes = batch * (8 + 2 * S * 4 + 2 * 2 * S * fbytes + 8 * W)
+        t = torch.arange(slots, dtype=torch.int32).view(slots, 1, 1)
+        k = torch.arange(S, dtype=torch.int32).view(1, 1, S)
+        side = torch.arange(2, dtype=torch.int32).view(1, 2, 1)
+        layouts = (('replay_gather_shared', t + side + k, slots + S),           # frames t .. t + S
+                   ('replay_gather_shared_distinct', t * (2 * S) + side * S + k, slots * 2 * S))
+        for name, fid, fslots in layouts:
+            store = torch.randint(0, 256, (fslots, fbytes), device=dev, generator=g,
+                                  dtype=torch.uint8)
+            fid = fid.contiguous().to(dev)
+            turn = [0]
+
+            def shared():
+                turn[0] = (turn[0] + 1) % sets.shape[0]
+                idx = sets[turn[0]]
+                L.call('smi_replay_gather_shared', P(tab), W, P(store), P(fid), S, fbytes, P(idx),
+                       batch, P(rows), P(po), P(pn), st)
+            ts = timed(shared, max(args.iters, 20), spread=True)
+            med = ts[len(ts) // 2]
+            report(name, nbytes, med, slots=slots, batch=batch, frame_bytes=S * fbytes, stack=S,
+                   cols=W, store_slots=fslots, store_bytes=fslots * fbytes, repeats=len(ts),
+                   min_ms=round(ts[0], 4), p25_ms=round(ts[len(ts) // 4], 4),
+                   p75_ms=round(ts[(3 * len(ts)) // 4], 4), max_ms=round(ts[-1], 4))
+            del store, fid
+        del tab, sets, rows, po, pn
+
+    if want('replay_insert'):
+        import copy
+        import time
+        import numpy as np
+        from surreal_amd.config import DDPG_DEFAULT_LEARNER_CONFIG, pixel_env_config
+        from surreal_amd.frame_store import frame_digest
+        from surreal_amd.replay import UniformReplay
+        D, A, S, n, calls = 17, 6, 3, 64, 23
+        rs = np.random.RandomState(0)
+        fr = [rs.randint(0, 256, (3, 84, 84)).astype(np.uint8) for _ in range(n * calls + S + 1)]
+        exps = []
+        for i in range(n * calls):
+            low = rs.randn(2, D).astype(np.float32)
+            exps.append({'obs': [{'low_dim': {'flat_inputs': low[j]},
+                                  'pixel': {'camera0': fr[i + j:i + j + S]}} for j in range(2)],
+                         'action': rs.randn(A).astype(np.float32), 'reward': 0.5, 'done': False})
+        ec = pixel_env_config(D, A, (9, 84, 84))
+        ec['frame_stacks'] = S
+        for name, share in (('replay_insert_shared', True), ('replay_insert_unshared', False)):
+            lc = copy.deepcopy(DDPG_DEFAULT_LEARNER_CONFIG)
+            lc.replay.memory_size = 4096
+            lc.replay.share_frames = share
+            rep = UniformReplay(lc, ec, seed=0, device=dev)
+            ts, packs = [], []
+            for c in range(calls):
+                chunk = exps[c * n:(c + 1) * n]
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                packed = rep.pack(chunk)
+                t1 = time.perf_counter()
+                rep.insert_rows(*packed)
+                torch.cuda.synchronize()
+                t2 = time.perf_counter()
+                if c >= 3:
+                    ts.append((t2 - t1) * 1e3)
+                    packs.append((t1 - t0) * 1e3)
+            ts.sort()
+            packs.sort()
+            t0 = time.perf_counter()
+            for f in fr[:n + 1]:
+                frame_digest(f)
+            dig = (time.perf_counter() - t0) * 1e3
+            fb = 3 * 84 * 84
+            up = n * rep.width * 4 + ((n + 1) * fb + n * 2 * S * 4 + (n + 1) * 4 if share
+                                      else 2 * n * S * fb)
+            print(json.dumps({'kernel': name, 'transitions': n, 'repeats': len(ts),
+                              'insert_rows_median_ms': round(ts[len(ts) // 2], 4),
+                              'insert_rows_min_ms': round(ts[0], 4),
+                              'insert_rows_max_ms': round(ts[-1], 4),
+                              'pack_median_ms': round(packs[len(packs) // 2], 4),
+                              'uploaded_bytes': int(up),
+                              'digest_ms_of_65_frames': round(dig, 4) if share else None}),
+                  flush=True)
+            del rep
 
     if want('moments'):
         n = 1 << 27
