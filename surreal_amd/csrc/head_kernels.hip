@@ -40,9 +40,8 @@
 
 namespace smi {
 
-// (HC_R, rows per workgroup: smi_shapes.hpp)
+// (HC_R, rows per workgroup, and the LDS carve, head_plan: smi_shapes.hpp)
 constexpr int HC_MAXK = 512;             // widest layer input / output handled here
-constexpr int HC_SR = 32 * 33 + 32;     // last-layer partials (1024) / a transpose tile (1056)
 
 struct HeadFwdArgs {
   const float* X; int64_t ldx; int K0;   // input rows [rows][ldx], K0 features
@@ -55,6 +54,10 @@ struct HeadFwdArgs {
   float* W1T; float* W2T;                // optional: [K0][h1], [h1][h2] for the backward
   int64_t rows; const int* skip;
   int ld0, ld1, ld2;                     // LDS leading dims (floats)
+  // the carve (head_plan): the HA1 tile and the partials / transpose tile in
+  // floats from the start of LDS (X and HA2 at 0); shared: o1 == 0, every tile
+  // takes its turn in the one region
+  int o1, oR, shared;
   // optional value-loss epilogue (out == 1, ppo.py:311-331): vgrad[r] =
   // vscale * (Y[r] - vret[r]), the MSE gradient the learner's value_rows pass
   // would compute from Y (same fp32 ops), written by the forward itself
@@ -111,11 +114,6 @@ __device__ unsigned long long g_head_ticks[2][10];
 #define HEAD_TICK(k, id) (void)0
 #define HEAD_END(k) (void)0
 #endif
-
-// LDS leading dim of a K-wide activation tile: K rounded up to the 16-k chunk,
-// + 4 (an odd multiple of 4 floats: the 16 rows of a chunk read land on 16
-// distinct 16-byte bank groups)
-__host__ __device__ inline int hc_ld(int k) { return ((k + 15) & ~15) + 4; }
 
 // A barrier for LDS hand-offs between the waves only: the fences are limited
 // to the LDS address space, so global loads in flight (the next layer's weight
@@ -383,9 +381,14 @@ __device__ __forceinline__ void hc_transpose_tile(const float* __restrict__ W, i
   }
 }
 
-// LDS floats of the forward's last-layer partials / transpose tile
-__host__ __device__ constexpr int hc_sr(int RT) { return RT * 1024 > HC_SR ? RT * 1024 : HC_SR; }
-
+// Two row tiles, both layers of at most 5 tiles per wave: at most 168 registers
+// (<5, 4, 2>: 128 VGPR + 40 AGPR), the three-waves-per-SIMD step, so the shared
+// carve's LDS is what lets a third workgroup onto the CU.  The bound is NOT
+// stated as __launch_bounds__(kWG, 3): any minimum above one makes the compiler
+// keep the accumulators in VGPRs (124 registers, no AGPRs), and that form of
+// <5, 4, 2> took 79 us against 62 us at two workgroups per CU and 68 us at
+// three; a change that pushes a form past 168 registers
+// shows in -Rpass-analysis=kernel-resource-usage as occupancy 2
 template <int NT1, int NT2, int RT>
 __global__ void __launch_bounds__(kWG)
 head_fwd_kernel(HeadFwdArgs a) {
@@ -394,11 +397,16 @@ head_fwd_kernel(HeadFwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float hsm[];
   // X and HA2 share one region (X is dead once layer 1's k loop is done: the
   // barrier after its epilogue orders that before layer 2 writes HA2): 37.5 KB
-  // at C3 widths and RT = 1, four workgroups per CU
+  // at C3 widths and RT = 1, four workgroups per CU.  Shared carve (RT = 2,
+  // a.shared): HA1 takes its turn in that region too (o1 == 0), each tile in
+  // its own leading dim, so a layer's epilogue waits at a barrier until every
+  // wave's k loop has read the tile it overwrites.  Every tile is written
+  // whole, all R rows up to its last 16-chunk (padding zeroed), and read no
+  // further: what a wider predecessor leaves beyond it is never read.
   float* s0 = hsm;                                // [R][ld0]  X
   float* s2 = hsm;                                // [R][ld2]  HA2
-  float* s1 = hsm + R * (a.ld0 > a.ld2 ? a.ld0 : a.ld2);   // [R][ld1]  HA1
-  float* sR = s1 + R * a.ld1;                     // [4][RT][64][4] partials of the last layer;
+  float* s1 = hsm + a.o1;                         // [R][ld1]  HA1
+  float* sR = hsm + a.oR;                         // [4][RT][64][4] partials of the last layer;
                                                   // [32][33] transpose tile
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
@@ -450,6 +458,9 @@ head_fwd_kernel(HeadFwdArgs a) {
       HEAD_TICK(0, 1);                            // layer 1 k loop
       S2.init(a.W2, a.h1, a.h1, a.h2, wave, 4, 0, 1);     // layer 2's stream, in flight
       hc_epi_load<NT2, 0, RT>(wave, a.h2, a.b2, nullptr, r0, a.rows, e2);
+      if constexpr (RT == 2) {
+        if (a.shared) hc_sync();                  // X read by every wave before HA1 lands on it
+      }
       hc_store<NT1, 0, RT>(acc, e1, wave, a.h1, s1, a.ld1);
     }
     hc_sync();
@@ -462,6 +473,9 @@ head_fwd_kernel(HeadFwdArgs a) {
       hc_run<NT2, RT>(S2, s1, a.ld1, acc);
       HEAD_TICK(0, 4);                            // layer 2 k loop
       S3.init(a.W3, a.h2, a.h2, a.out, 0, 1, wave, 4);    // layer 3's stream
+      if constexpr (RT == 2) {
+        if (a.shared) hc_sync();                  // HA1 read (k loop and copy-out) before HA2 lands on it
+      }
       hc_store<NT2, 0, RT>(acc, e2, wave, a.h2, s2, a.ld2);
     }
     hc_sync();
@@ -543,6 +557,7 @@ head_fwd_kernel(HeadFwdArgs a) {
 
 // PG: the policy loss gradient of the workgroup's rows as the prologue (the
 // action width is the template's 8: out == 8)
+static_assert(sizeof(PolGradShared) <= HC_PG_LDS, "head_plan counts the prologue's static LDS");
 template <int NTA, int NTB, int RT, bool PG>
 __global__ void __launch_bounds__(kWG, RT == 1 ? 3 : 2)
 head_bwd_kernel(HeadBwdArgs a) {
@@ -734,11 +749,6 @@ extern "C" int smi_head_phase_ticks(unsigned long long* out /* [2][10] */) {
 #endif
 
 // ------------------------------------------------------------------ host side
-static int hc_nt(int n) {                        // tiles per wave, rounded to an instantiation
-  const int t = (((n + 15) >> 4) + 3) >> 2;
-  return t <= 2 ? 2 : t <= 4 ? t : t <= 5 ? 5 : 8;     // 2, 3, 4, 5, 8
-}
-
 static bool al16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 // shapes the fused chains take (the caller falls back to the layer GEMMs
@@ -750,7 +760,7 @@ bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
          out >= 1 && out <= 16 && al16(X) && al16(W1) && al16(W2) && al16(W3);
 }
 
-// (hc_rt, head_bwd_blocks: smi_shapes.hpp)
+// (hc_rt, head_bwd_blocks, hc_nt, head_plan: smi_shapes.hpp)
 
 int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, const float* W1,
                           const float* b1, int h1, const float* W2, const float* b2, int h2,
@@ -761,14 +771,15 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
   if (rows <= 0) return SMI_OK;
   if (vgrad && (out != 1 || !vret)) return set_error(SMI_E_ARG, "head_forward: value epilogue needs out == 1");
   if (vpart && !vgrad) return set_error(SMI_E_ARG, "head_forward: value statistics need the value epilogue");
+  const HeadPlan hp = head_plan(rows, in, h1, h2, 0);
   HeadFwdArgs a{X, ldx, in, W1, b1, W2, b2, W3, b3, h1, h2, out, tanh_out, HA1, HA2, Y, ldy,
-                W1T, W2T, rows, skip, hc_ld(in), hc_ld(h1), hc_ld(h2), vret, vgrad, vscale};
+                W1T, W2T, rows, skip, hp.ld0, hp.ld1, hp.ld2, hp.fwd_o1, hp.fwd_oR, hp.fwd_shared,
+                vret, vgrad, vscale};
   a.vpart = vpart;
-  const int rt = hc_rt(rows);
-  const int R = HC_R * rt;
-  const size_t lds = (size_t)(R * ((a.ld0 > a.ld2 ? a.ld0 : a.ld2) + a.ld1) + hc_sr(rt)) * 4;
-  const dim3 grid((unsigned)((rows + R - 1) / R));
-  const int n1 = hc_nt(h1), n2 = hc_nt(h2);
+  const int rt = hp.rt;
+  const size_t lds = (size_t)hp.fwd_lds;
+  const dim3 grid((unsigned)hp.grid);
+  const int m1 = hp.fwd_n1, n2 = hp.fwd_n2;
   const int kslot = ktime_begin(st);
   const char* form = "head_fwd_kernel";          // the instantiation launched (smi_last_launch)
 #define SMI_HF(A, B)                                                                    \
@@ -783,8 +794,7 @@ int launch_head_fwd_fused(const float* X, int64_t ldx, int64_t rows, int in, con
       form = "head_fwd_kernel<" #A "," #B ",rt1>";                                      \
     }                                                                                   \
   } while (0)
-  // layer-1 slots {2, 5, 8} x layer-2 slots {2, 3, 4, 5, 8} (C3 / C5: 300 x 200 -> 5, 4)
-  const int m1 = n1 <= 2 ? 2 : n1 <= 5 ? 5 : 8;
+  // layer-1 slots {2, 5, 8} x layer-2 slots {2, 3, 4, 5, 8} (head_plan)
 #define SMI_HF2(A)                                        \
   do {                                                    \
     switch (n2) {                                         \
@@ -812,16 +822,14 @@ int launch_head_bwd_fused(const float* dZ, int out, int64_t rows, const float* W
                           const int* skip, const PolRowArgs* pg) {
   if (rows <= 0) return SMI_OK;
   if (pg && out != 8) return set_error(SMI_E_ARG, "head_backward: the policy prologue needs out == 8");
+  const HeadPlan hp = head_plan(rows, 0, h1, h2, dxn);   // (the input width shapes the forward only)
   HeadBwdArgs a{dZ, out, W3, W2T, W1T, h1, h2, dx0, dxn, HA1, HA2, dH2, dH1, dX, lddx, mask, ldm,
-                rows, skip, hc_ld(h2), hc_ld(h1)};
+                rows, skip, hp.ld2, hp.ld1};
   if (pg) a.pg = *pg;
-  const int rt = hc_rt(rows);
-  const int R = HC_R * rt;
-  const size_t lds = (size_t)(R * (a.ld2 + a.ld1) + R * 16) * 4;
-  const dim3 grid((unsigned)((rows + R - 1) / R));
-  int na = hc_nt(h1), nb = hc_nt(dxn > 0 ? dxn : 1);
-  na = na <= 2 ? 2 : na <= 5 ? 5 : 8;
-  nb = nb <= 2 ? 2 : 5;
+  const int rt = hp.rt;
+  const size_t lds = (size_t)hp.bwd_lds;
+  const dim3 grid((unsigned)hp.grid);
+  const int na = hp.bwd_na, nb = hp.bwd_nb;
   const int kslot = ktime_begin(st);
   const char* form = "head_bwd_kernel";
 #define SMI_HB2(A, B, P)                                                               \

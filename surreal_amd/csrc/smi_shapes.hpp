@@ -95,6 +95,78 @@ inline int head_bwd_blocks(int64_t rows) {
   const int R = HC_R * hc_rt(rows);
   return (int)((rows + R - 1) / R);
 }
+// LDS leading dim of a K-wide activation tile: K rounded up to the 16-k chunk,
+// + 4 (an odd multiple of 4 floats: the 16 rows of a chunk read land on 16
+// distinct 16-byte bank groups)
+SMI_HD inline int hc_ld(int k) { return ((k + 15) & ~15) + 4; }
+constexpr int HC_SR = 32 * 33 + 32;     // last-layer partials (1024) / a transpose tile (1056)
+// LDS floats of the forward's last-layer partials / transpose tile
+SMI_HD constexpr int hc_sr(int RT) { return RT * 1024 > HC_SR ? RT * 1024 : HC_SR; }
+// 16-column tiles per wave of an n-wide layer, rounded to an instantiation
+inline int hc_nt(int n) {
+  const int t = (((n + 15) >> 4) + 3) >> 2;
+  return t <= 2 ? 2 : t <= 4 ? t : t <= 5 ? 5 : 8;     // 2, 3, 4, 5, 8
+}
+constexpr int kCuLdsBytes = 160 * 1024;  // LDS of one CU
+constexpr int kCuWgSlots = 8;            // 8 waves per SIMD: 8 four-wave workgroups per CU
+constexpr int HC_PG_LDS = 1024;          // bound of the policy prologue's static LDS (PolGradShared)
+
+// The launch shape of the two fused chains over `rows` rows of an
+// in -> h1 -> h2 head (dX over dxn input columns): the one place that decides
+// the row tiles per workgroup, the kernel forms, the LDS carve and the grid.
+// Offsets are in floats from the start of the dynamic LDS.
+//   forward:  X [R][ld0] and HA2 [R][ld2] at 0, HA1 [R][ld1] at fwd_o1, the
+//             partials / transpose tile at fwd_oR;
+//   backward: dH2 [R][ld2], dH1 [R][ld1], dZ [R][16], one behind the other.
+// Forward, separate carve: HA1 has LDS of its own beside the X / HA2 region.
+// Shared carve (two row tiles only): X, HA1 and HA2 take their turns in ONE
+// region of the widest tile's size (fwd_o1 == 0), at the price of a barrier
+// between a layer's k loop and its epilogue.  It is chosen only where the
+// smaller carve lets more workgroups onto a CU: at the C3 widths 100 -> 300 ->
+// 200 and 32 rows, 74,752 -> 47,616 B, two -> three per CU, so the 672
+// workgroups of 21,504 rows are one resident round of the 256 CUs (62 -> 59
+// us per launch).  The backward keeps dH2 and dH1 apart: sharing them, with
+// the register cuts three per CU need, measured no faster (DESIGN.md section
+// 9).  *_wgs is what the LDS carve allows (the backward's with the policy
+// prologue's static LDS); registers may hold a form below it (the forward's
+// 8-tile forms and the two-row-tile backward: two per CU).
+struct HeadPlan {
+  int rt, grid;                          // row tiles per workgroup, workgroups
+  int ld0, ld1, ld2;                     // LDS leading dims of the in / h1 / h2 wide tiles
+  int fwd_n1, fwd_n2, bwd_na, bwd_nb;    // tiles per wave of the instantiation launched
+  int fwd_shared;                        // forward: the shared carve
+  int fwd_o1, fwd_oR;
+  int fwd_lds, bwd_lds;                  // dynamic LDS bytes
+  int fwd_wgs, bwd_wgs;                  // workgroups per CU
+};
+inline int hc_wgs(int lds_bytes) {
+  const int n = kCuLdsBytes / lds_bytes;
+  return n < kCuWgSlots ? n : kCuWgSlots;
+}
+inline HeadPlan head_plan(int64_t rows, int in, int h1, int h2, int dxn) {
+  HeadPlan p;
+  p.rt = hc_rt(rows);
+  p.grid = head_bwd_blocks(rows);
+  p.ld0 = hc_ld(in); p.ld1 = hc_ld(h1); p.ld2 = hc_ld(h2);
+  const int n1 = hc_nt(h1), nb = hc_nt(dxn > 0 ? dxn : 1);
+  // forward: layer-1 slots {2, 5, 8} x layer-2 slots {2, 3, 4, 5, 8} (C3 / C5:
+  // 300 x 200 -> 5, 4); backward: {2, 5, 8} x {2, 5}
+  p.fwd_n1 = p.bwd_na = n1 <= 2 ? 2 : n1 <= 5 ? 5 : 8;
+  p.fwd_n2 = hc_nt(h2);
+  p.bwd_nb = nb <= 2 ? 2 : 5;
+  const int R = HC_R * p.rt;
+  const int w02 = p.ld0 > p.ld2 ? p.ld0 : p.ld2;
+  const int w012 = w02 > p.ld1 ? w02 : p.ld1;
+  const int fsep = (R * (w02 + p.ld1) + hc_sr(p.rt)) * 4, fsh = (R * w012 + hc_sr(p.rt)) * 4;
+  p.fwd_shared = p.rt == 2 && hc_wgs(fsh) > hc_wgs(fsep);
+  p.fwd_o1 = p.fwd_shared ? 0 : R * w02;
+  p.fwd_oR = p.fwd_shared ? R * w012 : R * (w02 + p.ld1);
+  p.fwd_lds = p.fwd_shared ? fsh : fsep;
+  p.bwd_lds = (R * (p.ld2 + p.ld1) + R * 16) * 4;
+  p.fwd_wgs = hc_wgs(p.fwd_lds);
+  p.bwd_wgs = hc_wgs(p.bwd_lds + HC_PG_LDS);
+  return p;
+}
 
 // ---- policy rows (pol_rows.hpp) ---------------------------------------------
 // device control block (int / float scratch)
