@@ -626,7 +626,9 @@ int smi_adam_clip(float* params, const float* grad, float* m, float* v, int64_t 
  *   backward_weight:  dw[o][i] (+)= sum_r dy[r][o] x[r][i];  db[o] (+)= sum_r dy[r][o]
  * w is [out][ldw] row-major (torch nn.Linear when ldw == in); a column block of a
  * wider weight (the action block of CriticNetworkX's concat layer) is addressed
- * by offsetting w and keeping ldw.  Deterministic (no atomics). */
+ * by offsetting w and keeping ldw.  Every leading dimension must be at least
+ * the width it strides (ldm only with a mask): rows may not overlap.
+ * Deterministic (no atomics). */
 int smi_linear_forward(const float* x, int64_t ldx, int rows, int in_dim, const float* w,
                        int64_t ldw, const float* b, int out_dim, int act, float* y, int64_t ldy,
                        void* stream);
@@ -692,7 +694,8 @@ int smi_copy_cols(const float* src, int64_t lds, int64_t rows, int cols, float* 
  * the square root, affine), n <= 1024.  forward: y = (x - mean) rstd gamma +
  * beta per row, mean / rstd [rows] saved for the backward.  backward: dx from
  * dy (relu_input != 0: zero where x <= 0, the ReLU before the norm), and
- * dgamma = sum_rows dy xhat, dbeta = sum_rows dy (overwritten; fixed order). */
+ * dgamma = sum_rows dy xhat, dbeta = sum_rows dy (overwritten; fixed order).
+ * Every leading dimension must be >= n. */
 int smi_layernorm_forward(const float* x, int64_t ldx, int64_t rows, int n, const float* gamma,
                           const float* beta, float eps, float* y, int64_t ldy, float* mean,
                           float* rstd, void* stream);

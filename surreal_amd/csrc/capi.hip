@@ -424,6 +424,8 @@ int smi_linear_backward_input(const float* dy, int64_t ldg, int rows, int out_di
                               float* dx, int64_t lddx, void* stream) {
   REQUIRE(dy && w && dx && rows >= 0 && in_dim > 0 && out_dim > 0 && ldw >= in_dim,
           "linear_backward_input: bad args");
+  REQUIRE(ldg >= out_dim && lddx >= in_dim && (!relu_mask || ldm >= in_dim),
+          "linear_backward_input: leading dims too small");
   return launch_linear_bwd_dx(dy, ldg, rows, out_dim, w, ldw, in_dim, relu_mask, ldm, dx, lddx,
                               SMI_STREAM(stream));
 }
@@ -437,6 +439,7 @@ int smi_linear_backward_weight(const float* dy, int64_t ldg, int rows, int out_d
                                int accumulate, void* stream) {
   REQUIRE(dy && x && dw && rows >= 0 && in_dim > 0 && out_dim > 0 && lddw >= in_dim,
           "linear_backward_weight: bad args");
+  REQUIRE(ldg >= out_dim && ldx >= in_dim, "linear_backward_weight: leading dims too small");
   return launch_linear_bwd_dw(dy, ldg, rows, out_dim, x, ldx, in_dim, dw, lddw, db, accumulate,
                               SMI_STREAM(stream));
 }
@@ -470,6 +473,7 @@ int smi_layernorm_forward(const float* x, int64_t ldx, int64_t rows, int n, cons
                           const float* beta, float eps, float* y, int64_t ldy, float* mean,
                           float* rstd, void* stream) {
   REQUIRE(x && gamma && beta && y && mean && rstd && rows >= 0, "layernorm_forward: bad args");
+  REQUIRE(ldx >= n && ldy >= n, "layernorm_forward: leading dims too small");
   return launch_layernorm_fwd(x, ldx, rows, n, gamma, beta, eps, y, ldy, mean, rstd,
                               SMI_STREAM(stream));
 }
@@ -480,6 +484,7 @@ int smi_layernorm_backward(const float* dy, int64_t ldg, const float* x, int64_t
                            float* dbeta, void* stream) {
   REQUIRE(dy && x && mean && rstd && gamma && dx && dgamma && dbeta && rows >= 0,
           "layernorm_backward: bad args");
+  REQUIRE(ldg >= n && ldx >= n && lddx >= n, "layernorm_backward: leading dims too small");
   return launch_layernorm_bwd(dy, ldg, x, ldx, mean, rstd, gamma, rows, n, relu_input, dx, lddx,
                               dgamma, dbeta, SMI_STREAM(stream));
 }
@@ -510,8 +515,10 @@ int smi_copy_to_host(void* host_dst, const void* src, int64_t nbytes, void* stre
           "copy_to_host: 16-byte aligned pointers and a multiple of 16 bytes required");
   if (nbytes == 0) return SMI_OK;
   void* dev = nullptr;
-  if (hipHostGetDevicePointer(&dev, host_dst, 0) != hipSuccess || !dev)
+  if (hipHostGetDevicePointer(&dev, host_dst, 0) != hipSuccess || !dev) {
+    (void)hipGetLastError();     // the refusal is reported here, not by the next launch's check
     return set_error(SMI_E_ARG, "copy_to_host: destination is not pinned (mapped) host memory");
+  }
   return launch_copy_bytes16(src, dev, nbytes / 16, SMI_STREAM(stream));
 }
 
