@@ -735,6 +735,38 @@ int smi_ddpg_stats(const float* actions, int64_t lda, int act_dim, const float* 
                    int64_t rs, const float* y, const float* q, int64_t qs, int64_t n,
                    float* stats4, void* stream);
 
+/* ------------------------------------------------------------ DQN pieces */
+/* DQNLearner._optimize between the network outputs and the backward
+ * (surreal/learner/dqn.py:50-71) in one launch.  adv / adv_next / adv_target
+ * [B][ld >= A]: action scores of the online net at s, of the online net at s'
+ * (read only with double_q) and of the target net at s'; val / val_next /
+ * val_target: the state-value columns (read only with dueling), each with a
+ * stride; actions: a float32 column of integral values in [0, A) (out of range:
+ * clamped into it); rewards, dones: columns; w: [B] importance weights or NULL
+ * (= ones, same bits).  Per row, fp32:
+ *   dueling: q_j = (a_j - mean_j a_j) + v (mean summed left to right); else q_j = a_j
+ *   j* = first index of max_j q_online(s')_j (double_q) | q_target(s')_j
+ *   y = r + gamma * ((1 - d) * q_target(s')[j*]);  td = q(s)[a] - y
+ *   l = 0.5 td^2 if |td| < 1 else |td| - 0.5;  g = (w * clamp(td, -1, 1)) / B
+ * Outputs: dadv [B][ldd >= A] = g * ([j == a] - 1/A) (dueling) | g * [j == a],
+ * every entry of the A columns written; dval [B] = g (dueling only); td_out
+ * [B]; y_out [B] (may be NULL); stats[2] = { mean(w l), mean |td| } (fixed-order
+ * fp64 sums).  SMI_E_ARG: NULL required pointer, B < 1, A < 1, a leading
+ * dimension below A, dueling without val / val_target / dval (/ val_next). */
+int smi_dqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+               const float* adv_target, int64_t ldt, const float* val, int64_t val_stride,
+               const float* val_next, int64_t val_next_stride, const float* val_target,
+               int64_t val_target_stride, const float* actions, int64_t action_stride,
+               const float* rewards, int64_t reward_stride, const float* dones,
+               int64_t done_stride, const float* w, int64_t B, int A, float gamma, int dueling,
+               int double_q, float* dadv, int64_t ldd, float* dval, float* td_out, float* y_out,
+               float* stats, void* stream);
+/* out[i] = first index of the maximum of row i's q_j (the combination and the
+ * scan of smi_dqn_td) over adv [rows][lda >= A] (+ val with dueling):
+ * QAgent.act's q_values.max(1)[1] (surreal/agent/q_agent.py:45-46). */
+int smi_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t val_stride,
+                   int64_t rows, int A, int dueling, int32_t* out, void* stream);
+
 /* ------------------------------------------------------ DDPG n-step target */
 /* Replaces the target of DDPGLearner._optimize (surreal/learner/ddpg.py:279-283):
  *   y = r + gamma_n * q_next * (1 - done); with twin critics y = min(y, y2). */

@@ -330,3 +330,82 @@ class DDPGAgentBatch(object):
         if self.agent_mode != 'eval_deterministic':
             a += self._noise()
         return a.clip(-1, 1)
+
+
+class QAgentBatch(object):
+    """N epsilon-greedy DQN actors (q_agent.py:12-87; agent_mode 'training' |
+    'eval_stochastic' | 'eval_deterministic').  act() first makes every agent's
+    decision on the host, agents in order, with exactly the draws
+    q_agent.py:35-48 makes from Python's global `random`: eps from the linear
+    schedule (1.0 -> exploration.final_eps over exploration.steps) at the
+    agent's own step count T[i] in training mode, learner_config.eval.eps
+    otherwise; `random.random() > eps` (not drawn in eval_deterministic mode)
+    picks the greedy action, else `random.randrange(A)` is the action.  One
+    forward over the N rows and one smi_dqn_greedy (first index of the
+    maximum, as torch's max(1)[1] on the CPU) then serve the greedy agents,
+    and one D2H copy returns the N actions."""
+
+    def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
+        from .config import ConfigError
+        from .dqn import FFQfunc, dqn_specs
+        lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
+        ec = env_config if isinstance(env_config, Config) else Config(env_config)
+        D, A, hidden, dueling = dqn_specs(lc, ec)
+        ex = lc.algo.exploration
+        if str(ex.schedule).lower() != 'linear':
+            raise ConfigError('QAgentBatch runs the linear exploration schedule only, got '
+                              '{!r}'.format(ex.schedule))
+        L.require_gpu()
+        self.schedule_steps, self.final_eps = int(ex.steps), float(ex.final_eps)
+        self.learner_config = lc
+        self.n = int(n_agents)
+        self.agent_mode = agent_mode
+        self.action_dim, self.obs_dim = A, D
+        self.device = torch.device(device) if device is not None else torch.device('cuda')
+        self._ctx = L.Context(self.device)      # own workspace (re-entrancy)
+        self.q_func = FFQfunc(D, A, hidden, dueling, self.device, torch.Generator().manual_seed(0))
+        self.T = np.zeros(self.n, dtype=np.int64)           # q_agent.py:33, per agent
+        self._bufs = {}
+        self._greedy = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+
+    def load_module_dict(self, module_dict):
+        self.q_func.load_state_dict(module_dict['q_func'].state_dict())
+
+    def load_numpy(self, numpy_dict):
+        self.q_func.load_state_dict(_np_state_to_torch(numpy_dict['q_func']))
+
+    def eps(self, i):
+        """q_agent.py:37-40 for agent i at its current step count"""
+        if self.agent_mode != 'training':
+            return self.learner_config.eval.eps
+        fraction = min(float(self.T[i]) / self.schedule_steps, 1.0)     # LinearSchedule.value
+        return 1.0 + fraction * (self.final_eps - 1.0)
+
+    def act(self, obs):
+        """obs: (N, D) low-dim observations or {'low_dim': {key: (N, D)}};
+        returns the N actions (int64 numpy)."""
+        import random
+        from .dqn import _QNet
+        self._ctx.make_current()
+        if isinstance(obs, dict):
+            obs = obs['low_dim'][list(obs['low_dim'])[0]]
+        x = np.ascontiguousarray(obs, dtype=np.float32)
+        if x.ndim != 2 or x.shape != (self.n, self.obs_dim):
+            raise ValueError(f'expected observations ({self.n}, {self.obs_dim}), got {x.shape}')
+        A = self.action_dim
+        actions = np.zeros(self.n, dtype=np.int64)
+        greedy = np.zeros(self.n, dtype=bool)
+        for i in range(self.n):                                         # q_agent.py:35-48
+            eps = self.eps(i)
+            self.T[i] += 1
+            if self.agent_mode == 'eval_deterministic' or random.random() > eps:
+                greedy[i] = True
+            else:
+                actions[i] = random.randrange(A)
+        if greedy.any():
+            xd = torch.from_numpy(x).to(self.device)
+            adv, val = _QNet(self.q_func, self._bufs).fwd(xd, self.n, 'act')
+            L.call('smi_dqn_greedy', L.ptr(adv), A, L.ptr(val), 1, self.n, A,
+                   int(self.q_func.dueling), L.ptr(self._greedy), L.stream(self.device))
+            actions[greedy] = self._greedy.cpu().numpy()[greedy]        # one D2H
+        return actions

@@ -30,6 +30,7 @@ CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-obje
 UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('sampler_kernels.hip', []), ('per_kernels.hip', []),
          ('linear_kernels.hip', []), ('linear_dw.hip', []), ('ddpg_kernels.hip', []),
+         ('dqn_kernels.hip', []),
          ('lstm_mfma.hip', []), ('lstm_valu.hip', ['-fno-slp-vectorize']), ('cnn_kernels.hip', []),
          ('head_kernels.hip', []), ('ppo_rnn_kernels.hip', []), ('ppo_rnn.hip', []),
          ('calib_kernels.hip', []), ('capi.hip', [])]

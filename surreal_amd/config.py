@@ -173,6 +173,42 @@ DDPG_DEFAULT_LEARNER_CONFIG = Config({
 })
 DDPG_DEFAULT_LEARNER_CONFIG.extend(BASE_LEARNER_CONFIG)
 
+# surreal/learner/dqn.py:94-121 with its '_list_' / '_int_' / '_bool_'
+# placeholders filled, the agent's eval.eps (surreal/agent/q_agent.py:55-65) and a
+# replay block shaped like DDPG's (replay.alpha: PrioritizedReplay reads it)
+DQN_DEFAULT_LEARNER_CONFIG = Config({
+    'model': {
+        'convs': [],
+        'fc_hidden_sizes': [128, 128],
+        'dueling': True,
+    },
+    'algo': {
+        'lr': 1e-3,
+        'optimizer': 'Adam',
+        'grad_norm_clipping': 10,
+        'gamma': .99,
+        'target_network_update_freq': 500,
+        'double_q': True,
+        'exploration': {
+            'schedule': 'linear',
+            'steps': 10000,
+            'final_eps': 0.01,
+        },
+        'prioritized': {
+            'enabled': False,
+            'alpha': 0.6,
+            'beta0': 0.4,
+            'beta_anneal_iters': None,
+            'eps': 1e-6,
+        },
+    },
+    'eval': {'eps': 0.05},
+    'replay': {'batch_size': 512, 'memory_size': int(1000000 / 3),
+               'sampling_start_size': 3000, 'replay_shards': 3, 'alpha': 0.6},
+    'parameter_publish': {'min_publish_interval': 3},
+})
+DQN_DEFAULT_LEARNER_CONFIG.extend(BASE_LEARNER_CONFIG)
+
 # learner-side session keys (surreal/session/default_configs.py)
 BASE_SESSION_CONFIG = Config({
     'folder': '/tmp/surreal_amd',
@@ -194,6 +230,18 @@ def pixel_env_config(obs_dim, act_dim, camera=(3, 84, 84)):
         'frame_stack_concatenate_on_env': True,
         'obs_spec': spec,
         'action_spec': {'dim': (act_dim,), 'type': 'continuous'},
+    })
+
+
+def discrete_env_config(obs_dim, n_actions):
+    """env_config of a flat low-dim env with n_actions discrete actions
+    (surreal/env/make_env.py:16-38: action_spec.dim = (n,), type 'discrete')."""
+    return Config({
+        'pixel_input': False,
+        'frame_stacks': 1,
+        'frame_stack_concatenate_on_env': True,
+        'obs_spec': {'low_dim': {'flat_inputs': (obs_dim,)}},
+        'action_spec': {'dim': (n_actions,), 'type': 'discrete'},
     })
 
 

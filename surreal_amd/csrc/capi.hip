@@ -456,6 +456,40 @@ int smi_mse_grad_weighted(const float* q, int64_t q_stride, const float* y, cons
   return launch_mse_grad_weighted(q, q_stride, y, w, n, dq, loss, td_out, SMI_STREAM(stream));
 }
 
+int smi_dqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+               const float* adv_target, int64_t ldt, const float* val, int64_t val_stride,
+               const float* val_next, int64_t val_next_stride, const float* val_target,
+               int64_t val_target_stride, const float* actions, int64_t action_stride,
+               const float* rewards, int64_t reward_stride, const float* dones,
+               int64_t done_stride, const float* w, int64_t B, int A, float gamma, int dueling,
+               int double_q, float* dadv, int64_t ldd, float* dval, float* td_out, float* y_out,
+               float* stats, void* stream) {
+  REQUIRE(adv && adv_target && actions && rewards && dones && dadv && td_out && stats,
+          "dqn_td: null pointer");
+  REQUIRE(!double_q || adv_next, "dqn_td: double_q without the online scores at s' (null pointer)");
+  REQUIRE(B >= 1, "dqn_td: B < 1");
+  REQUIRE(A >= 1, "dqn_td: A < 1");
+  REQUIRE(lda >= A && ldt >= A && ldd >= A && (!double_q || ldn >= A),
+          "dqn_td: leading dims too small");
+  REQUIRE(!dueling || (val && val_target && dval && (!double_q || val_next)),
+          "dqn_td: dueling needs val, val_target, dval (and val_next with double_q)");
+  return launch_dqn_td(adv, lda, adv_next, ldn, adv_target, ldt, val, val_stride, val_next,
+                       val_next_stride, val_target, val_target_stride, actions, action_stride,
+                       rewards, reward_stride, dones, done_stride, w, B, A, gamma, dueling,
+                       double_q, dadv, ldd, dval, td_out, y_out, stats, SMI_STREAM(stream));
+}
+
+int smi_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t val_stride,
+                   int64_t rows, int A, int dueling, int32_t* out, void* stream) {
+  REQUIRE(adv && out, "dqn_greedy: null pointer");
+  REQUIRE(rows >= 0, "dqn_greedy: rows < 0");
+  REQUIRE(A >= 1, "dqn_greedy: A < 1");
+  REQUIRE(lda >= A, "dqn_greedy: leading dims too small");
+  REQUIRE(!dueling || val, "dqn_greedy: dueling needs val");
+  if (rows == 0) return SMI_OK;
+  return launch_dqn_greedy(adv, lda, val, val_stride, rows, A, dueling, out, SMI_STREAM(stream));
+}
+
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream) {
   REQUIRE(q && dq && n > 0, "neg_mean_grad: bad args");

@@ -62,6 +62,16 @@ int launch_layernorm_bwd(const float* dy, int64_t ldg, const float* x, int64_t l
 int launch_mlp3_stacked(const float* P, int64_t pstride, const int64_t* o6, int in, int h1, int h2,
                         int out, int act_out, const float* x, int64_t ldx, int n, float* y,
                         int64_t ldy, hipStream_t st);
+// ---- dqn_kernels.hip
+int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn,
+                  const float* adv_t, int64_t ldt, const float* val, int64_t vs,
+                  const float* val_n, int64_t vns, const float* val_t, int64_t vts,
+                  const float* actions, int64_t as, const float* rewards, int64_t rs,
+                  const float* dones, int64_t ds, const float* w, int64_t B, int A, float gamma,
+                  int dueling, int double_q, float* dadv, int64_t ldd, float* dval, float* td_out,
+                  float* y_out, float* stats, hipStream_t st);
+int launch_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t vs, int64_t rows,
+                      int A, int dueling, int32_t* out, hipStream_t st);
 // ---- linear_kernels.hip
 int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,

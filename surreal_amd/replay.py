@@ -100,6 +100,8 @@ class UniformReplay(object):
 
     Rows are fixed-width float32 records laid out [obs(D) | action(A) |
     reward(1) | obs_next(D) | done(1)] in one (memory_size, W) device tensor.
+    For an action spec of type 'discrete' A is 1: the column holds the action
+    index (pack() takes a Python or numpy integer), as DQNLearner reads it.
 
     Pixel mode (a 'pixel' entry in env_config['obs_spec']; only camera0 is
     read, as DDPGModel does): two more device rings, `frames` and
@@ -139,7 +141,10 @@ class UniformReplay(object):
             self.obs_dim = int(sum(v[0] for v in spec['low_dim'].values())) if 'low_dim' in spec else 0
         else:
             self.obs_dim = int(sum(v[0] for v in spec['low_dim'].values()))
-        self.act_dim = int(env_config['action_spec']['dim'][0])
+        # a discrete spec's dim[0] is the NUMBER of actions: the row holds the
+        # action index in one column (DQNLearner reads it as a float32 column)
+        self.discrete = env_config['action_spec'].get('type') == 'discrete'
+        self.act_dim = 1 if self.discrete else int(env_config['action_spec']['dim'][0])
         self.width = 2 * self.obs_dim + self.act_dim + 2
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.table = torch.zeros(self.memory_size, self.width, dtype=torch.float32,

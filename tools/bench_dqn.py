@@ -1,0 +1,106 @@
+"""Times one DQNLearner.learn() (dueling double-Q, B = 512, D = 17, hidden
+[128, 128], A = 6, importance weights) eagerly and as a hipGraph replay, and in
+the same process DDPGLearner.learn() at the C4 shape (batch 512, 17 -> 6,
+actor 300x200, critic 400x300) as the yardstick: HIP events around each call,
+median of --iters calls after warm-up (as tools/bench_hbm.py).  The launch count
+of a DQN step is taken from the library calls of one eager step (a grouped
+weight-gradient flush is two launches, smi_adam_clip with a norm clip three;
+queued weight gradients and smi_dw_group_begin launch nothing).  Prints one
+JSON line per measurement; reads nothing outside the repository.
+
+Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
+"""
+import argparse
+import copy
+import json
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from surreal_amd import _lib as L  # noqa: E402
+from surreal_amd import synthetic  # noqa: E402
+from surreal_amd.config import (DDPG_DEFAULT_LEARNER_CONFIG, DQN_DEFAULT_LEARNER_CONFIG,  # noqa: E402
+                                discrete_env_config, gym_env_config)
+from surreal_amd.ddpg import DDPGLearner  # noqa: E402
+from surreal_amd.dqn import DQNLearner  # noqa: E402
+
+LAUNCHES = {'smi_dw_group_begin': 0, 'smi_linear_backward_weight': 0, 'smi_dw_group_flush': 2,
+            'smi_adam_clip': 3}
+
+
+def timed(fn, iters, warm):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    evs = []
+    for _ in range(iters):
+        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        s.record()
+        fn()
+        e.record()
+        evs.append((s, e))
+    torch.cuda.synchronize()
+    ts = sorted(s.elapsed_time(e) for s, e in evs)
+    return ts[len(ts) // 2], ts[len(ts) // 4], ts[3 * len(ts) // 4]
+
+
+def count_launches(fn):
+    calls, real = [], L.call
+
+    def counting(name, *a):
+        calls.append(name)
+        return real(name, *a)
+    L.call = counting
+    try:
+        fn()
+    finally:
+        L.call = real
+    return sum(LAUNCHES.get(n, 1) for n in calls), len(calls)
+
+
+def dqn_batch(B, D, A, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {'obs': torch.randn(B, D, generator=g).cuda(),
+            'actions': torch.randint(0, A, (B, 1), generator=g).float().cuda(),
+            'rewards': torch.randn(B, 1, generator=g).cuda(),
+            'obs_next': torch.randn(B, D, generator=g).cuda(),
+            'dones': (torch.rand(B, 1, generator=g) < 0.05).float().cuda(),
+            'weights': (0.3 + 0.7 * torch.rand(B, 1, generator=g)).cuda()}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--iters', type=int, default=40)
+    ap.add_argument('--warmup', type=int, default=10)
+    args = ap.parse_args()
+    B, D, A = 512, 17, 6
+    lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = B
+    lc.model.fc_hidden_sizes = [128, 128]
+    b = dqn_batch(B, D, A, 0)
+    for name, graph in (('dqn_learn_eager', False), ('dqn_learn_graph', True)):
+        learner = DQNLearner(lc, discrete_env_config(D, A), seed=0, use_graph=graph)
+        extra = {}
+        if not graph:
+            learner.learn(b)
+            extra['launches_per_step'], extra['library_calls_per_step'] = \
+                count_launches(lambda: learner.learn(b))
+        med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
+        print(json.dumps(dict({'measurement': name, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                               'q3_ms': round(q3, 4), 'iters': args.iters}, **extra)), flush=True)
+    dlc = copy.deepcopy(DDPG_DEFAULT_LEARNER_CONFIG)
+    dlc.replay.batch_size = B
+    db = {k: v.cuda() for k, v in synthetic.ddpg_batch(B, D, A, seed=0).items()}
+    for name, graph in (('ddpg_c4_learn_eager', False), ('ddpg_c4_learn_graph', True)):
+        learner = DDPGLearner(dlc, gym_env_config(D, A), seed=0, use_graph=graph)
+        med, q1, q3 = timed(lambda: learner.learn(db), args.iters, args.warmup)
+        print(json.dumps({'measurement': name, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                          'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+
+
+if __name__ == '__main__':
+    main()
