@@ -576,8 +576,19 @@ int smi_lstm_forward_x(const float* x, int64_t ldx, int din, const float* w_ih,
 /* Pixel stem: CNNStemNetwork (builders.py:8-33) on obs/255 (ppo_net.py:368-375)
  *   conv 8x8/4 (C->16) -> ReLU -> conv 4x4/2 (16->32) -> ReLU -> Flatten -> Linear(F) -> ReLU
  * Flat parameters [conv1.w (16,C,8,8) | conv1.b | conv2.w (32,16,4,4) | conv2.b |
- * fc.w (F, 32*H2*W2) | fc.b].  Built for C == 3, W % 4 == 0 (84x84 cameras).
- * Images are uint8, 16-byte aligned; activation row n = t*B + b reads
+ * fc.w (F, 32*H2*W2) | fc.b].  C is 3 (one RGB frame) or 9 (three stacked RGB
+ * frames).  With H1 = (H-8)/4 + 1, W1 = (W-8)/4 + 1, H2 = (H1-4)/2 + 1,
+ * W2 = (W1-4)/2 + 1 (integer division), a frame is accepted when
+ *   H1 >= 4 and W1 >= 4 (20x20 is the smallest), H2*W2 <= 96,
+ *   W % 4 == 0, C*H*W % 16 == 0, W1 even, H1*W1 % 4 == 0,
+ *   and one image with its conv-1 activation (C*H*W + 64*H1*W1 bytes; the
+ *   backward: + 132*H2*W2 + 4*H1*W1 + 1024) fits the 160 KiB of LDS of a CU;
+ * H and W may differ (84x84 qualifies; anything else is SMI_E_ARG).  The
+ * backward has two forms: with a next-image prefetch when the frame fits its
+ * register arrays (smi_cnn_backward_prefetch returns 1; 84x84 does for both
+ * channel counts), without it for larger frames.
+ * Images are uint8, 16-byte aligned (both calls check it; else SMI_E_ARG);
+ * activation row n = t*B + b reads
  * pix[b][t] (t < T) or pix_next[b] (t == T) — a plain batch is B = rows, T = 1.
  *   forward: a1 [rows][16][H1*W1] (optional, needed by backward), a2 [rows][32*H2*W2],
  *            feat[n*ldf + f] = ReLU output.
@@ -585,6 +596,8 @@ int smi_lstm_forward_x(const float* x, int64_t ldx, int din, const float* w_ih,
  *            row stride lddz); writes (not accumulates) the flat gradient. */
 int64_t smi_cnn_param_count(int C, int H, int W, int F);
 int64_t smi_cnn_scratch_bytes(int64_t rows, int C, int H, int W, int F);
+/* 1: smi_cnn_backward runs the next-image-prefetch form for this frame, 0: the other */
+int smi_cnn_backward_prefetch(int C, int H, int W);
 int smi_cnn_forward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
                     int64_t T, int64_t rows, int C, int H, int W, int F, float* a1, float* a2,
                     float* feat, int64_t ldf, void* stream);

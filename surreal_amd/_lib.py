@@ -213,6 +213,7 @@ _SIGS = {
     'smi_ppo_rnn_xbuf_floats': (c_i64, [c_int] * 12),
     'smi_cnn_param_count': (c_i64, [c_int] * 4),
     'smi_cnn_scratch_bytes': (c_i64, [c_i64] + [c_int] * 4),
+    'smi_cnn_backward_prefetch': (c_int, [c_int] * 3),
     'smi_cnn_forward': (c_int, [P, P, P, c_i64, c_i64, c_i64] + [c_int] * 4 + [P, P, P, c_i64, P]),
     'smi_cnn_backward': (c_int, [P, P, P, c_i64, c_i64, c_i64] + [c_int] * 4 +
                          [P, P, P, c_i64, P, P, c_i64, P]),

@@ -775,6 +775,10 @@ int64_t smi_cnn_scratch_bytes(int64_t rows, int C, int H, int W, int F) {
   return 4 * (rows * g.flat + (int64_t)cnn_bwd_grid(rows) * g.nconv);
 }
 
+int smi_cnn_backward_prefetch(int C, int H, int W) {
+  return cnn_bwd_prefetch(cnn_geom(C, H, W, 1), C) ? 1 : 0;
+}
+
 int smi_cnn_forward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
                     int64_t T, int64_t rows, int C, int H, int W, int F, float* a1, float* a2,
                     float* feat, int64_t ldf, void* stream) {

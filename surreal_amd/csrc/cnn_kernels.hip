@@ -51,14 +51,9 @@ __host__ __device__ inline int64_t lds_img_bytes(const CnnGeom& g) { return (g.i
 // waves at 176: 132 vs 143 us per 2688-image forward (tools/bench_cnn.py).
 // Three stacked RGB frames (C = 9, DDPG's frame_stacks = 3, ddpg_configs.py:
 // 114): the 144 conv-1 weight registers need one wave per SIMD.
-// per-thread 16-byte chunk counts of an 84 x 84 frame's staging (image, A1,
-// dA2), register arrays of the forward's batched image loads and the
-// backward's next-image prefetch (larger frames: a tail loop / PF off)
-template <int C> struct CnnPf {
-  static constexpr int KI = C <= 3 ? 6 : 16;     // uint4 of the uint8 image
-  static constexpr int KA = 7;                   // float4 of A1 (16 x P1)
-  static constexpr int KD = 3;                   // float4 of dA2 (flat)
-};
+// (CnnPf, the staging register-array sizes, and cnn_bwd_prefetch, the choice of
+// the backward form: smi_shapes.hpp)
+static_assert(kCnnThreads == kWG, "cnn_bwd_prefetch counts chunks per kWG threads");
 
 template <int C>
 __global__ void __launch_bounds__(kWG) __attribute__((amdgpu_waves_per_eu(C <= 3 ? 3 : 1, C <= 3 ? 3 : 1)))
@@ -429,10 +424,12 @@ int cnn_forward(const float* prm, const PixRows& pr, int C, int H, int W, int F,
                 float* A1, float* A2, float* feat, int64_t ldf, hipStream_t st, const int* skip) {
   const CnnGeom g = cnn_geom(C, H, W, F);
   RC_CHECK(cnn_check(g));
+  const size_t lds = cnn_fwd_lds(g);
+  if (lds > (size_t)kCuLdsBytes)
+    return set_error(SMI_E_ARG, "cnn: the frame's image and conv-1 activation exceed the LDS of a CU");
   if (rows < 1) return SMI_OK;
   if ((reinterpret_cast<uintptr_t>(pr.pix) | reinterpret_cast<uintptr_t>(pr.pix_next)) & 15)
     return set_error(SMI_E_ARG, "cnn: pixel buffers must be 16-byte aligned");
-  const size_t lds = cnn_fwd_lds(g);
   auto k = C == 9 ? cnn_fwd_kernel<9> : cnn_fwd_kernel<3>;
   allow_lds(k, lds);
   const int64_t rg = resident_grid(k, kWG, lds);
@@ -450,18 +447,18 @@ int cnn_backward(const float* prm, const PixRows& pr, int C, int H, int W, int F
                  float* dA2, float* part, hipStream_t st, const int* skip) {
   const CnnGeom g = cnn_geom(C, H, W, F);
   RC_CHECK(cnn_check(g));
+  const size_t lds = cnn_bwd_lds(g);
+  if (lds > (size_t)kCuLdsBytes)
+    return set_error(SMI_E_ARG, "cnn: the frame's backward staging exceeds the LDS of a CU");
   if (rows < 1) return SMI_OK;
+  if ((reinterpret_cast<uintptr_t>(pr.pix) | reinterpret_cast<uintptr_t>(pr.pix_next)) & 15)
+    return set_error(SMI_E_ARG, "cnn: pixel buffers must be 16-byte aligned");
   RC_CHECK(launch_linear_bwd_dw(dz, lddz, (int)rows, F, A2, g.flat, g.flat, grad + g.oWf, g.flat,
                                 grad + g.obf, 0, st, skip));
   RC_CHECK(launch_linear_bwd_dx(dz, lddz, (int)rows, F, prm + g.oWf, g.flat, g.flat, A2, g.flat,
                                 dA2, g.flat, st, skip));
-  const size_t lds = cnn_bwd_lds(g);
   // next-image prefetch when the frame fits its register arrays (84 x 84 does)
-  auto fits = [&](auto pf) {
-    using P = decltype(pf);
-    return (g.img >> 4) <= (int64_t)P::KI * kWG && 4 * g.P1 <= P::KA * kWG && (g.flat >> 2) <= P::KD * kWG;
-  };
-  const bool pf = (C == 9 ? fits(CnnPf<9>{}) : fits(CnnPf<3>{}));
+  const bool pf = cnn_bwd_prefetch(g, C);
   auto k = C == 9 ? (pf ? cnn_bwd_kernel<9, true> : cnn_bwd_kernel<9, false>)
                   : (pf ? cnn_bwd_kernel<3, true> : cnn_bwd_kernel<3, false>);
   allow_lds(k, lds);

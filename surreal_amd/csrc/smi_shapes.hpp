@@ -83,6 +83,24 @@ SMI_HD inline CnnGeom cnn_geom(int C, int H, int W, int F) {
 }
 constexpr int kCnnPartials = 512;               // max workgroups (partial slabs) of the backward
 inline int cnn_bwd_grid(int64_t rows) { return (int)(rows < kCnnPartials ? rows : kCnnPartials); }
+constexpr int kCnnThreads = 256;                // threads of a stem workgroup (== kWG)
+// per-thread 16-byte chunk counts of an 84 x 84 frame's staging (image, A1,
+// dA2), register arrays of the forward's batched image loads and the
+// backward's next-image prefetch (larger frames: a tail loop / prefetch off)
+template <int C> struct CnnPf {
+  static constexpr int KI = C <= 3 ? 6 : 16;     // uint4 of the uint8 image
+  static constexpr int KA = 7;                   // float4 of A1 (16 x P1)
+  static constexpr int KD = 3;                   // float4 of dA2 (flat)
+};
+// the backward form: next-image prefetch when the frame's image, A1 and dA2
+// fit the prefetch register arrays (84 x 84 does, for 3 and 9 channels), else
+// the form that stages each image after the previous one's last pass
+inline bool cnn_bwd_prefetch(const CnnGeom& g, int C) {
+  const int ki = C == 9 ? CnnPf<9>::KI : CnnPf<3>::KI, ka = C == 9 ? CnnPf<9>::KA : CnnPf<3>::KA,
+            kd = C == 9 ? CnnPf<9>::KD : CnnPf<3>::KD;
+  return (g.img >> 4) <= (int64_t)ki * kCnnThreads && 4 * g.P1 <= ka * kCnnThreads &&
+         (g.flat >> 2) <= kd * kCnnThreads;
+}
 
 // ---- fused head chains (head_kernels.hip) ----------------------------------
 constexpr int HC_R = 16;                 // rows per workgroup

@@ -21,6 +21,7 @@ from surreal_amd import synthetic
 from surreal_amd.config import pixel_env_config
 from surreal_amd.learner import PPOLearner
 from surreal_amd.model import PPOModel
+from tests import cnn_ref as CR
 from tests.helpers import (copy_weights_to_oracle, load_lstm_flat, load_seq_flat, lstm_flat,
                            oracle_batch, ppo_config, seq_flat)
 from tests.test_gpu_ddpg import _fp32_as_good_as_torch
@@ -86,9 +87,7 @@ def _timemajor_images(pix, pixn, S):
 def test_cnn_forward_backward_vs_torch(B, T, S, F):
     C, H, W = CAM
     torch.manual_seed(B * 100 + S)
-    net = R.cnn_stem_ref(C, H, W, F)
-    net64 = R.cnn_stem_ref(C, H, W, F).double()
-    net64.load_state_dict({k: v.double() for k, v in net.state_dict().items()})
+    net, net64 = CR.nets(C, H, W, F)
     flat = seq_flat(net).to(DEV)
     pix, pixn = _images(B, T, S)
     rows = S * B
@@ -96,25 +95,18 @@ def test_cnn_forward_backward_vs_torch(B, T, S, F):
     pix_d, pixn_d = pix.to(DEV), pixn.to(DEV)      # kept alive until the kernels ran
     a1, a2, feat = _run_fwd(flat, pix_d, pixn_d, B, T, rows, F)
     # torch reference (CPU): activations of each stage
-    xs = x / 255.0
-    r1 = torch.relu(net[0](xs))
-    r2 = torch.relu(net[2](r1))
-    out = net(xs)
-    xs64 = x.double() / 255.0
-    r1_64 = torch.relu(net64[0](xs64))
-    r2_64 = torch.relu(net64[2](r1_64))
-    out64 = net64(xs64)
-    _fp32_as_good_as_torch(a1.cpu().reshape(r1.shape), r1.detach(), r1_64.detach(), 2e-6)
-    _fp32_as_good_as_torch(a2.cpu(), r2.detach().reshape(rows, -1),
-                           r2_64.detach().reshape(rows, -1), 2e-6)
-    _fp32_as_good_as_torch(feat.cpu(), out.detach(), out64.detach(), 2e-6)
+    r1, r2, out = CR.stages(net, x)
+    r1_64, r2_64, out64 = CR.stages(net64, x)
+    _fp32_as_good_as_torch(a1.cpu().reshape(r1.shape), r1, r1_64, 2e-6)
+    _fp32_as_good_as_torch(a2.cpu(), r2, r2_64, 2e-6)
+    _fp32_as_good_as_torch(feat.cpu(), out, out64, 2e-6)
     # backward of sum(out * dy): dz = dy * relu'(out).  The reference backward
     # uses the GPU forward's ReLU masks (A1 > 0, A2 > 0): a pre-activation
     # within fp32 noise of 0 may take either side in any two implementations,
     # and the backward is exactly linear given the masks.
     g = torch.Generator().manual_seed(7)
     dy = torch.randn(rows, F, generator=g)
-    dz = (dy * (out.detach() > 0)).contiguous()
+    dz = (dy * (out > 0)).contiguous()
     dz_d = dz.to(DEV)
     nbytes = int(L.lib().smi_cnn_scratch_bytes(rows, C, H, W, F))
     scratch = torch.empty(nbytes // 4 + 1, device=DEV)
@@ -125,15 +117,8 @@ def test_cnn_forward_backward_vs_torch(B, T, S, F):
     m1 = (a1.cpu().reshape(r1.shape) > 0)
     m2 = (a2.cpu() > 0)
 
-    def masked_grads(model, dt):
-        model.zero_grad()
-        z1 = model[0](x.to(dt) / 255.0) * m1.to(dt)
-        z2 = model[2](z1).reshape(rows, -1) * m2.to(dt)
-        (model[5](z2) * dz.to(dt)).sum().backward()
-        return [p.grad.detach() for p in model.parameters()]
-
-    g32 = masked_grads(net, torch.float32)
-    g64 = masked_grads(net64, torch.float64)
+    g32 = CR.masked_grads(net, x, m1, m2, dz)
+    g64 = CR.masked_grads(net64, x, m1, m2, dz)
     got = grad.cpu()
     o = 0
     for a32, a64 in zip(g32, g64):
@@ -180,16 +165,16 @@ def test_ppo_model_pixel_forward_vs_oracle():
 
 
 def _run_pixel(mode, B, T, H, D, A, Hd, hidden, F, iters=2, zf=True, epochs=(10, 10),
-               lr=(3e-4, 3e-4), rnn=True):
+               lr=(3e-4, 3e-4), rnn=True, cam=CAM):
     lc = _pixel_cfg(mode, B, T, H, Hd, hidden, F, zf and D > 0, epochs, lr, rnn)
-    ec = pixel_env_config(D, A, CAM)
+    ec = pixel_env_config(D, A, cam)
     learner = PPOLearner(lc, ec, seed=9)
-    ref = R.PPOLearnerRef(lc, D, A, pixel=CAM)
+    ref = R.PPOLearnerRef(lc, D, A, pixel=cam)
     copy_weights_to_oracle(learner, ref)
     report = {}
     for it in range(iters):
         batch = synthetic.ppo_batch(B, T, D, A, seed=50 + it, rnn_hidden=Hd if rnn else None,
-                                    pixel=CAM)
+                                    pixel=cam)
         rstats = ref.learn(oracle_batch(batch))
         learner.learn(synthetic.to_device(batch, DEV))
         stats = learner.last_stats()
