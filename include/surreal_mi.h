@@ -572,6 +572,37 @@ int smi_lstm_forward_x(const float* x, int64_t ldx, int din, const float* w_ih,
                        const float* b_ih, const float* w_hh, const float* b_hh,
                        const float* h0, const float* c0, int S, int B, int H, float* hbuf,
                        float* cbuf, float* gates_act, float* xproj_scratch, void* stream);
+/* The transposed weight image of one LSTM layer, image = [W_ihT [din][4H] |
+ * W_hhT [H][4H] | 4H zeros] (4H (din + H + 1) floats, H <= 128), from the
+ * natural rows; the zero row is what the forward's padding columns read. */
+int smi_lstm_weight_image(const float* w_ih, const float* w_hh, int din, int H, float* image,
+                          void* stream);
+/* smi_lstm_forward_x with the recurrence's weights read from that image: the
+ * 4-segment matrix-core form loads its weight columns as consecutive dwords
+ * per lane instead of one row per lane.  Bit-identical to smi_lstm_forward_x
+ * on the same weights.  Returns SMI_E_NOFIT (nothing launched) where that form
+ * does not run: B <= the device's CU count, or H > 128.  w_ih (natural rows)
+ * is read only by the unfused form's xproj GEMM (din > 64 or H > 104), which
+ * also needs xproj_scratch; both may be NULL otherwise.  S == 0 launches
+ * nothing and leaves every buffer untouched. */
+int smi_lstm_forward_x_image(const float* x, int64_t ldx, int din, const float* w_ih,
+                             const float* b_ih, const float* image, const float* b_hh,
+                             const float* h0, const float* c0, int S, int B, int H, float* hbuf,
+                             float* cbuf, float* gates_act, float* xproj_scratch, void* stream);
+/* Float offset, in the smi_ppo_rnn_phase scratch, of the image of the trained
+ * stem's layer-0 weights (same arguments as smi_ppo_rnn_scratch_bytes), or -1
+ * when the shape has none (more than one LSTM layer, rnn_hidden 0 or > 128, or
+ * B * horizon < obs_dim + cnn_feat + rnn_hidden + 1: the image lives in the
+ * steps of the input-projection buffer that only the GAE pass uses, and
+ * smi_ppo_rnn_scratch_bytes is what it was without it).
+ * The GAE phase rebuilds it from `lstm` and both APPLY phases keep it current
+ * (W_hhT always; W_ihT where the input projection is fused, obs_dim + cnn_feat
+ * <= 64 and rnn_hidden <= 104: elsewhere no forward reads it and it stays GAE's),
+ * when B > the device's CU count (the form that reads it); at smaller batches
+ * the region is left alone. */
+int64_t smi_ppo_rnn_wimage_offset(int B, int T, int horizon, int obs_dim, int rnn_hidden,
+                                  int h1, int h2, int act_dim, int critic_h1, int critic_h2,
+                                  int pix_c, int pix_h, int pix_w, int cnn_feat, int rnn_layer);
 
 /* Pixel stem: CNNStemNetwork (builders.py:8-33) on obs/255 (ppo_net.py:368-375)
  *   conv 8x8/4 (C->16) -> ReLU -> conv 4x4/2 (16->32) -> ReLU -> Flatten -> Linear(F) -> ReLU

@@ -222,6 +222,10 @@ _SIGS = {
     'smi_lstm_backward': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
     'smi_lstm_forward_x': (c_int, [P, c_i64, c_int, P, P, P, P, P, P, c_int, c_int, c_int,
                                    P, P, P, P, P]),
+    'smi_lstm_weight_image': (c_int, [P, P, c_int, c_int, P, P]),
+    'smi_lstm_forward_x_image': (c_int, [P, c_i64, c_int, P, P, P, P, P, P, c_int, c_int, c_int,
+                                         P, P, P, P, P]),
+    'smi_ppo_rnn_wimage_offset': (c_i64, [c_int] * 15),
 }
 
 _lib = None

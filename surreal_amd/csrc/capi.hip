@@ -863,6 +863,41 @@ int smi_lstm_forward_x(const float* x, int64_t ldx, int din, const float* w_ih,
                          nullptr);
 }
 
+int64_t smi_ppo_rnn_wimage_offset(int B, int T, int horizon, int obs_dim, int rnn_hidden, int h1,
+                                  int h2, int act_dim, int critic_h1, int critic_h2, int pix_c,
+                                  int pix_h, int pix_w, int cnn_feat, int rnn_layer) {
+  return ppo_rnn_wimage_offset(B, T, horizon, obs_dim, rnn_hidden, rnn_layer, h1, h2, act_dim,
+                               critic_h1, critic_h2, pix_c, pix_h, pix_w, cnn_feat);
+}
+
+int smi_lstm_weight_image(const float* w_ih, const float* w_hh, int din, int H, float* image,
+                          void* stream) {
+  REQUIRE(w_ih && w_hh && image, "lstm_weight_image: bad args");
+  return launch_lstm_weight_image(w_ih, w_hh, din, H, image, SMI_STREAM(stream));
+}
+
+int smi_lstm_forward_x_image(const float* x, int64_t ldx, int din, const float* w_ih,
+                             const float* b_ih, const float* image, const float* b_hh,
+                             const float* h0, const float* c0, int S, int B, int H, float* hbuf,
+                             float* cbuf, float* gates_act, float* xproj_scratch, void* stream) {
+  REQUIRE(x && b_ih && image && b_hh && h0 && c0 && hbuf && S >= 0 && B >= 0 && H >= 1 &&
+          din >= 1 && ldx >= din, "lstm_forward_x_image: bad args");
+  if (S == 0 || B == 0) return SMI_OK;         // no step, no launch (as smi_lstm_forward_x)
+  if (!lstm_fwd_image_ok(B, H)) return SMI_E_NOFIT;
+  const hipStream_t st = SMI_STREAM(stream);
+  const float* w_hhT = image + (int64_t)4 * H * din;
+  const int rf = launch_lstm_fwd_x(x, ldx, din, image, b_ih, w_hhT, b_hh, h0, c0, S, B, H, hbuf,
+                                   cbuf, gates_act, st, nullptr, 0, true);
+  if (rf != SMI_E_NOFIT) return rf;
+  REQUIRE(w_ih && xproj_scratch,
+          "lstm_forward_x_image: the unfused form needs w_ih and xproj_scratch [S][B][4H]");
+  const int rc = launch_linear_fwd(x, ldx, S * B, din, w_ih, din, b_ih, 4 * H, ACT_NONE,
+                                   xproj_scratch, 4 * H, st, nullptr);
+  if (rc) return rc;
+  return launch_lstm_fwd(xproj_scratch, w_hhT, b_hh, h0, c0, S, B, H, hbuf, cbuf, gates_act, st,
+                         nullptr, 0, true);
+}
+
 int smi_lstm_backward(const float* dh, const float* gates_act, const float* cbuf,
                       const float* w_hh, int S, int B, int H, float* dgates, void* stream) {
   REQUIRE(dh && gates_act && cbuf && w_hh && dgates && S >= 0 && B >= 0 && H >= 1,

@@ -358,7 +358,25 @@ __device__ __forceinline__ void load_row_v(const float* r, int n, float* dst) {
   }
 }
 
-template <int KP, int KX, bool VF = false>
+// IMG: a.w_ih / a.w_hh point into the TRANSPOSED image [W_ihT [din][4H]
+// | W_hhT [H][4H] | 4H zeros] (launch_lstm_weight_image, kept current by
+// adam_split_kernel), so the lane's column is w[k] = T[k * 4H + col]: one dword
+// per lane at consecutive addresses, the BPTT's access pattern, instead of 64
+// rows' cache lines behind every load instruction.  No alignment or H % 4
+// requirement; k >= n reads the image's zero row, a zero by address (zoff: its
+// float offset from t; the row offset is a scalar select, no branch).  Same
+// register values as the row loads, same MFMA order: bit-identical results.
+template <int N>
+__device__ __forceinline__ void load_col(const float* t, int n, int ld, uint32_t zoff, int col,
+                                         float* dst) {
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const uint32_t row = k < n ? (uint32_t)(k * ld) : zoff;          // wave-uniform
+    dst[k] = t[row + (uint32_t)col];
+  }
+}
+
+template <int KP, int KX, bool VF = false, bool IMG = false>
 __global__ void __launch_bounds__(kWG8)
 lstm_fwd_r4_kernel(LstmFwdArgs a) {
   if (a.skip && a.skip[0] != 0) return;
@@ -382,7 +400,10 @@ lstm_fwd_r4_kernel(LstmFwdArgs a) {
   // the lane's W_hh (and W_ih) row in registers, loaded in 16- (8-) byte runs
   // where the rows allow (a load per k put 64 rows' lines behind every
   // instruction, 32 instructions per line)
-  if constexpr (VF) {
+  if constexpr (IMG) {
+    load_col<KP>(a.w_hh, H, G4, (uint32_t)(H * G4), colc, w);
+    if constexpr (KX > 0) load_col<KX>(a.w_ih, a.din, G4, (uint32_t)((a.din + H) * G4), colc, wx);
+  } else if constexpr (VF) {
     load_row_v<KP, 4>(a.w_hh + (int64_t)colc * H, H, w);
     if constexpr (KX > 0) load_row_v<KX, 2>(a.w_ih + (int64_t)colc * a.din, a.din, wx);
   } else {
@@ -682,6 +703,38 @@ static int device_cus() {
 // workgroup and 4.42 / 5.12 with the q form at two workgroups per CU, round 6,
 // profiles/r06/ab/lstm_form_*)
 static bool lstm_valu(int B, int H) { return H >= 1 && H <= 128 && B <= device_cus(); }
+// the r4 forward's image form (IMG) runs for (B, H): wherever the r4 form does
+bool lstm_fwd_image_ok(int B, int H) { return H >= 1 && H <= 128 && B >= 1 && !lstm_valu(B, H); }
+
+// image = [W_ihT [din][4H] | W_hhT [H][4H] | 4H zeros] from the natural rows,
+// one output element per thread (coalesced stores; the strided reads are one
+// per thread)
+__global__ void __launch_bounds__(kWG)
+lstm_weight_image_kernel(const float* __restrict__ w_ih, const float* __restrict__ w_hh, int din,
+                         int H, float* __restrict__ image) {
+  const int G4 = 4 * H, nih = G4 * din, nw = nih + G4 * H;
+  const int o = blockIdx.x * kWG + threadIdx.x;
+  if (o >= nw + G4) return;
+  if (o < nih) {
+    const int k = o / G4, col = o - k * G4;
+    image[o] = w_ih[col * din + k];
+  } else if (o < nw) {
+    const int k = (o - nih) / G4, col = (o - nih) - k * G4;
+    image[o] = w_hh[col * H + k];
+  } else {
+    image[o] = 0.f;                 // the zero row the forward's padding k read
+  }
+}
+
+int launch_lstm_weight_image(const float* w_ih, const float* w_hh, int din, int H, float* image,
+                             hipStream_t st) {
+  if (H < 1 || H > 128 || din < 1 || din > 4096)
+    return set_error(SMI_E_ARG, "lstm_weight_image: H must be in [1, 128], din in [1, 4096]");
+  const int n = 4 * H * (din + H + 1);
+  hipLaunchKernelGGL(lstm_weight_image_kernel, dim3((n + kWG - 1) / kWG), dim3(kWG), 0, st, w_ih,
+                     w_hh, din, H, image);
+  return check_launch("lstm_weight_image_kernel");
+}
 
 #ifdef SMI_PROF
 extern "C" int smi_lstm_phase_ticks(unsigned long long* out /* [8] */) {
@@ -706,9 +759,10 @@ static bool r4_vf(const LstmFwdArgs& a, bool fused_x) {
 
 int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, const float* h0,
                     const float* c0, int S, int B, int H, float* hbuf, float* cbuf, float* gates,
-                    hipStream_t st, const int* skip, int keep) {
+                    hipStream_t st, const int* skip, int keep, bool image) {
   if (B <= 0 || S < 0) return SMI_OK;
   if (H < 1 || H > 256) return set_error(SMI_E_ARG, "lstm: hidden size must be in [1, 256]");
+  if (image && !lstm_fwd_image_ok(B, H)) return SMI_E_NOFIT;    // w_hh is W_hhT: the r4 form only
   LstmFwdArgs a{xproj, w_hh, b_hh, h0, c0, S, B, H, hbuf, cbuf, gates, skip};
   a.keep = keep;
   const int kslot = ktime_begin(st);
@@ -721,7 +775,11 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
     const bool vf = r4_vf(a, false);
 #define SMI_R4F(KP_)                                                                        \
     do {                                                                                    \
-      if (vf) {                                                                             \
+      if (image) {                                                                          \
+        hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, 0, false, true>), g4, dim3(kWG8), 0,    \
+                           st, a);                                                          \
+        return check_launch("lstm_fwd_r4_kernel<" #KP_ ",0,img>");                          \
+      } else if (vf) {                                                                      \
         hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, 0, true>), g4, dim3(kWG8), 0, st, a);   \
         return check_launch("lstm_fwd_r4_kernel<" #KP_ ",0,vf>");                           \
       } else {                                                                              \
@@ -747,13 +805,18 @@ int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, co
 int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, const float* b_ih,
                       const float* w_hh, const float* b_hh, const float* h0, const float* c0,
                       int S, int B, int H, float* hbuf, float* cbuf, float* gates,
-                      hipStream_t st, const int* skip, int keep) {
+                      hipStream_t st, const int* skip, int keep, bool image) {
   // no step, no launch (the outputs stay untouched): the fused forms' prologues
   // load x_0 unconditionally, and at S == 0 the K-split form clamps that index
   // to S * KX - 1 = -1
   if (B <= 0 || S <= 0) return SMI_OK;
-  if (din < 1 || din > 64 || H < 1 || H > 104) return SMI_E_NOFIT;
+  if (!lstm_fwd_x_fuses(din, H)) return SMI_E_NOFIT;
   const bool valu = lstm_valu(B, H);
+  // w_ih / w_hh are W_ihT / W_hhT inside one image: the r4 form only (callers
+  // ask lstm_fwd_image_ok first)
+  if (image && valu) return SMI_E_NOFIT;
+  if (image && w_hh != w_ih + (int64_t)4 * H * din)
+    return set_error(SMI_E_ARG, "lstm: W_hhT must follow W_ihT in the weight image");
   if (valu && lstm_fwd_v_lds(S, din <= 48 ? 48 : 64, (4 * H + 63) & ~63) > kVxMax)
     return SMI_E_NOFIT;                            // staged x + x parts > the LDS budget
   LstmFwdArgs a{nullptr, w_hh, b_hh, h0, c0, S, B, H, hbuf, cbuf, gates, skip,
@@ -767,7 +830,11 @@ int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, c
   const bool vf = r4_vf(a, true);
 #define SMI_R4X(KP_, KX_)                                                                     \
   do {                                                                                        \
-    if (vf) {                                                                                 \
+    if (image) {                                                                              \
+      hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, KX_, false, true>), g4, dim3(kWG8), 0, st,  \
+                         a);                                                                  \
+      return check_launch("lstm_fwd_r4_kernel<" #KP_ "," #KX_ ",img>");                       \
+    } else if (vf) {                                                                          \
       hipLaunchKernelGGL((lstm_fwd_r4_kernel<KP_, KX_, true>), g4, dim3(kWG8), 0, st, a);     \
       return check_launch("lstm_fwd_r4_kernel<" #KP_ "," #KX_ ",vf>");                        \
     } else {                                                                                  \

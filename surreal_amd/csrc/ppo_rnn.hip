@@ -130,26 +130,33 @@ static int head_bwd(const Head& h, const float* dZ, const float* X, int64_t ldx,
 // and gate activations of every layer for a backward
 // keep_steps: with keep, the cell states / gates are stored for the first
 // keep_steps steps only (0: all S; the GAE pass over S1 steps keeps E)
+// wimg: the transposed image of P's layer-0 weights (Ctx::wimg; one layer): the
+// recurrence loads its weight columns from it (the xproj GEMM of the unfused
+// form still reads W_ih's rows)
 static int lstm_forward(const RnnDims& d, const float* P, const float* X, int S, const float* h0,
                         const float* c0, const RnnScratch& s, bool keep, hipStream_t st,
-                        const int* skip, int keep_steps = 0) {
+                        const int* skip, int keep_steps = 0, const float* wimg = nullptr) {
   const int64_t BH = (int64_t)d.B * d.H;
   for (int l = 0; l < d.L; ++l) {
     const LstmP lp = lstm_layer(d, P, l);
+    const bool img = wimg && l == 0;
+    const float* rWih = img ? wimg : lp.Wih;
+    const float* rWhh = img ? wimg + (int64_t)d.G4 * d.Din : lp.Whh;
     const float* Xl = l == 0 ? X : hbuf_of(d, s, l - 1) + BH;
     const int64_t ldx = l == 0 ? d.ldx : d.H;
     const int din = l == 0 ? d.Din : d.H;
     float* hb = hbuf_of(d, s, l);
     float* cb = keep ? cbuf_of(d, s, l) : nullptr;
     float* gt = keep ? gates_of(d, s, l) : nullptr;
-    const int rf = launch_lstm_fwd_x(Xl, ldx, din, lp.Wih, lp.bih, lp.Whh, lp.bhh, h0 + l * BH,
-                                     c0 + l * BH, S, d.B, d.H, hb, cb, gt, st, skip, keep_steps);
+    const int rf = launch_lstm_fwd_x(Xl, ldx, din, rWih, lp.bih, rWhh, lp.bhh, h0 + l * BH,
+                                     c0 + l * BH, S, d.B, d.H, hb, cb, gt, st, skip, keep_steps,
+                                     img);
     if (rf == SMI_E_NOFIT) {
       const int64_t rows = (int64_t)S * d.B;
       RC_CHECK(launch_linear_fwd(Xl, ldx, (int)rows, din, lp.Wih, din, lp.bih, d.G4, ACT_NONE,
                                  s.xproj, d.G4, st, skip));
-      RC_CHECK(launch_lstm_fwd(s.xproj, lp.Whh, lp.bhh, h0 + l * BH, c0 + l * BH, S, d.B, d.H, hb,
-                               cb, gt, st, skip, keep_steps));
+      RC_CHECK(launch_lstm_fwd(s.xproj, rWhh, lp.bhh, h0 + l * BH, c0 + l * BH, S, d.B, d.H, hb,
+                               cb, gt, st, skip, keep_steps, img));
     } else if (rf) {
       return rf;
     }
@@ -286,6 +293,12 @@ int64_t ppo_rnn_scratch_bytes(int B, int T, int Hz, int D, int H, int L, int h1,
                  .total_floats;
 }
 
+int64_t ppo_rnn_wimage_offset(int B, int T, int Hz, int D, int H, int L, int h1, int h2, int A, int c1,
+                              int c2, int pc, int ph, int pw, int F) {
+  return rnn_scratch(rnn_dims(B, T, Hz, D, H, h1, h2, A, c1, c2, pc, ph, pw, F, L), nullptr)
+      .wimg_off;
+}
+
 static PolRowArgs pol_rows(const smi_ppo_rnn_args& a, const RnnDims& d, const RnnScratch& s) {
   PolRowArgs p{};
   p.B = d.B; p.T = d.T; p.E = d.E; p.A = d.A; p.mode = a.mode;
@@ -311,6 +324,10 @@ struct Ctx {
   float *gA, *gC;               // [actor head | lstm | cnn], [critic head | lstm | cnn]
   int64_t NEg;                  // training rows of all ranks
   hipStream_t st;
+  // the transposed image of the trained stem's layer-0 weights (s.wimg) when
+  // the epoch forwards load from it (the r4 form runs at this batch), else
+  // null: nobody writes or reads the region
+  float* wimg;
 };
 
 static Ctx make_ctx(const smi_ppo_rnn_args& a, hipStream_t st) {
@@ -321,7 +338,8 @@ static Ctx make_ctx(const smi_ppo_rnn_args& a, hipStream_t st) {
   return Ctx{a, d, s, s.ci + CI_STOP, lstm_params(a.lstm, d.Din, d.H), a.lstm + d.nL,
              Head{a.actor, d.LA, d.Hin, d.h1, d.h2, d.A, 1},
              Head{a.critic, d.LC, d.Hin, d.c1, d.c2, 1, 0},
-             a.xbuf, a.xbuf + d.nA_head + d.nS, (int64_t)d.E * a.B_global, st};
+             a.xbuf, a.xbuf + d.nA_head + d.nS, (int64_t)d.E * a.B_global, st,
+             s.wimg && lstm_fwd_image_ok(d.B, d.H) ? s.wimg : nullptr};
 }
 
 // The choices more than one phase depends on.  Each is a function of
@@ -343,6 +361,9 @@ static Ctx make_ctx(const smi_ppo_rnn_args& a, hipStream_t st) {
 //                    VALUE_GRAD, VALUE_APPLY     bumped the step exactly when APPLY does not
 //   vstats(e)        VALUE_GRAD (head forward,   who summed the last epoch's value statistics,
 //                    value rows, reduction)      and over how many partials
+//   Ctx::wimg        GAE, POLICY_FWD,            GAE built the weight image and every Adam that
+//                    VALUE_GRAD, both APPLYs     ran kept it current exactly when the epoch
+//                                                forwards load from it
 struct Rules {
   const smi_ppo_rnn_args& a;
   const RnnDims& d;
@@ -462,6 +483,13 @@ static int phase_gae(const Ctx& c, const Rules& r) {
   } else if (d.H > 0) {
     RC_CHECK(lstm_forward(d, a.lstm, s.Xz, d.S1, a.h0, a.c0, s, true, st, nullptr, d.E));
   }
+  // the parameters may have been replaced since the last learn (checkpoint
+  // load, DP broadcast): the weight image the epoch forwards load from is
+  // rebuilt from them once per learn, by a launch of its own (57 K floats at
+  // C3); the Adam applies keep it current from here on.  After the recurrence
+  // above: the image lives in the tail of s.xproj (rnn_layout.hpp), which that
+  // pass over S1 steps is the only one to use
+  if (c.wimg) RC_CHECK(launch_lstm_weight_image(c.lm.Wih, c.lm.Whh, d.Din, d.H, c.wimg, st));
   RC_CHECK(head_fwd(c.critic, head_in(d, s, s.Xz), d.Hld, d.NG, s.HA1, s.HA2, s.OUT, st,
                     fwd_only()));
   // (also zeroes the learn()'s device control state)
@@ -512,7 +540,7 @@ static int phase_policy_fwd(const Ctx& c, const Rules& r, int e) {
     RC_CHECK(launch_adv_export(pol_rows(a, d, s), d.NE, a.adv_out, a.ret_out, st));
   RC_CHECK(cnn_features(a, d, c.cnn, d.E, s.Xz, s.A1, s, st, c.stop));
   if (d.H > 0 && e > 0)
-    RC_CHECK(lstm_forward(d, a.lstm, s.Xz, d.E, a.h0, a.c0, s, true, st, c.stop));
+    RC_CHECK(lstm_forward(d, a.lstm, s.Xz, d.E, a.h0, a.c0, s, true, st, c.stop, 0, c.wimg));
   PolRowArgs p = pol_rows(a, d, s);
   p.invN = (float)(1.0 / (double)c.NEg);
   // (the KL check after the last update, e == epoch_policy, has no backward:
@@ -588,7 +616,8 @@ static int adam_apply(const Ctx& c, const Rules& r, bool policy) {
                    a.hyper + (policy ? SMI_HYP_LR_ACTOR : SMI_HYP_LR_CRITIC), a.beta1, a.beta2,
                    a.adam_eps, policy ? a.actor_wd : a.critic_wd, clip ? max_norm : 0.f,
                    c.s.part, g, policy ? c.stop : nullptr, clip ? norm_out : nullptr, nullptr,
-                   fn ? c.s.ci + CI_NP : nullptr};
+                   fn ? c.s.ci + CI_NP : nullptr, c.wimg, d.Din, d.H,
+                   lstm_fwd_x_fuses(d.Din, d.H) ? 1 : 0};
   return launch_adam_split(aa, g, fn ? nullptr : c.s.part, policy ? c.s.ci + CI_RUNS : nullptr,
                            c.st);
 }
@@ -610,7 +639,7 @@ static int phase_value_grad(const Ctx& c, const Rules& r, int e) {
   if (e > 0) {
     RC_CHECK(cnn_features(a, d, c.cnn, d.E, s.Xz, s.A1, s, st, nullptr));
     if (d.H > 0)
-      RC_CHECK(lstm_forward(d, a.lstm, s.Xz, d.E, a.h0, a.c0, s, true, st, nullptr));
+      RC_CHECK(lstm_forward(d, a.lstm, s.Xz, d.E, a.h0, a.c0, s, true, st, nullptr, 0, c.wimg));
   }
   // dV = 2 (V - R) / N: written by the head forward's epilogue, except in
   // the last epoch, whose value_rows pass also sums the statistics of

@@ -937,6 +937,26 @@ adam_split_kernel(AdamSplitArgs a) {
     a.m[i] = mi;
     a.v[i] = vi;
   }
+  // The forward's weight image: the thread reads back the stem elements it
+  // just wrote (W_ih, then W_hh, of layer 0 come first in p1) and stores each
+  // at its transposed position.  A pass of its own, on purpose: with the store
+  // inside the loop above the compiler contracted that loop's multiply-adds
+  // differently, and every parameter moved in its last bit.
+  if (a.wimg) {
+    const int G4 = 4 * a.wH, nih = G4 * a.wdin, nw = nih + G4 * a.wH;
+    for (int64_t i = i_first; i < n; i += (int64_t)gridDim.x * kWG) {
+      const int64_t j = i - a.n0;
+      if (j < (a.wih ? 0 : nih) || j >= nw) continue;
+      const float pn = a.p1[j];
+      if (j < nih) {
+        const int r = (int)j / a.wdin, k = (int)j - r * a.wdin;
+        a.wimg[k * G4 + r] = pn;
+      } else {
+        const int jh = (int)j - nih, r = jh / a.wH, k = jh - r * a.wH;
+        a.wimg[nih + k * G4 + r] = pn;
+      }
+    }
+  }
 }
 
 // also advances the optimizer's step counter (and the applied-epoch count):

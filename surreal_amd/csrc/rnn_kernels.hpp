@@ -65,6 +65,12 @@ struct AdamSplitArgs {
   const double* part; int np;
   const int* skip; float* norm_out; int* runs;
   const int* np_dev;     // non-null: the partial count on the device (a fused sum of squares)
+  // non-null: p1 starts with LSTM layer 0's W_ih [4 wH][wdin] | W_hh [4 wH][wH], and
+  // every new value of those is also stored at its transposed position in wimg
+  // ([W_ihT [wdin][4 wH] | W_hhT [wH][4 wH] | zeros], the r4 forward's weight image)
+  // wih == 0: W_ihT is left as it is (no forward reads it: the unfused form's
+  // xproj GEMM takes W_ih's rows)
+  float* wimg; int wdin, wH, wih;
 };
 // clip_grad_norm_ + Adam over grid workgroups.  sumsq_part non-null: the sums
 // of squares of a.g are formed here first (into sumsq_part == a.part, with the

@@ -63,10 +63,30 @@ struct RnnScratch {
   float *A1, *A2, *dA2, *dF, *cpart;        // pixel stem (empty without one)
   double *part, *gaepart;
   int* ci; float* cf;
+  // the transposed image of LSTM layer 0's weights, [W_ihT [Din][4H] | W_hhT [H][4H]
+  // | 4H zeros] (one-layer stems with H <= 128: the r4 forward loads its
+  // columns from it; written by the GAE phase and kept current by both Adam
+  // applies).  It lives in the tail of xproj: that region holds S1 steps for the
+  // GAE pass, which is done with them before it writes the image, and every
+  // later forward of the learn runs E < S1 steps (PREP has xprojR), so rows
+  // [E B, S1 B) stay idle.  The carve's total does not change.  Empty
+  // (wimg_off == -1) when the shape has no image or the tail cannot hold it.
+  float* wimg;
+  int64_t wimg_off;
   int64_t total_floats;
 };
 
 inline int64_t al64(int64_t n) { return (n + 63) & ~(int64_t)63; }
+// floats of the weight image; 0: the shape has none
+inline int64_t wimg_floats(const RnnDims& d) {
+  return d.L == 1 && d.H >= 1 && d.H <= 128 ? (int64_t)d.G4 * (d.Din + d.H + 1) : 0;
+}
+// its float offset inside xproj (past the E steps an epoch forward writes, on a
+// 64-float boundary), or -1
+inline int64_t wimg_in_xproj(const RnnDims& d) {
+  const int64_t n = wimg_floats(d), at = al64(d.NE * d.G4);
+  return n > 0 && at + n <= d.NG * d.G4 ? at : -1;
+}
 // doubles of s.part: 65536, or the value statistics' five per head workgroup
 inline int64_t part_doubles(const RnnDims& d) {
   const int64_t v = 5 * (int64_t)head_bwd_blocks(d.NE);
@@ -80,7 +100,9 @@ inline RnnScratch rnn_scratch(const RnnDims& d, void* base) {
   const int hmax1 = d.h1 > d.c1 ? d.h1 : d.c1, hmax2 = d.h2 > d.c2 ? d.h2 : d.c2;
   s.Xz = take(d.NG * d.ldx);
   s.Xr = take(d.NE * d.ldx);
+  s.wimg_off = wimg_in_xproj(d) >= 0 ? o + wimg_in_xproj(d) : -1;
   s.xproj = take(d.NG * d.G4);
+  s.wimg = s.xproj && s.wimg_off >= 0 ? p + s.wimg_off : nullptr;
   s.hbuf = take((int64_t)d.L * (d.S1 + 1) * d.B * d.H);     // per layer (see hbuf_of)
   s.cbuf = take((int64_t)d.L * (d.E + 1) * d.B * d.H);
   s.gates = take((int64_t)d.L * d.NE * d.G4);

@@ -149,15 +149,26 @@ int launch_ppo_epoch_apply(const smi_ppo_args* args, int epoch, hipStream_t stre
 
 int64_t ppo_rnn_scratch_bytes(int B, int T, int Hz, int D, int H, int L, int h1, int h2, int A, int c1,
                               int c2, int pc, int ph, int pw, int F);
+int64_t ppo_rnn_wimage_offset(int B, int T, int Hz, int D, int H, int L, int h1, int h2, int A, int c1,
+                              int c2, int pc, int ph, int pw, int F);
 int ppo_rnn_phase(const smi_ppo_rnn_args& a, int phase, int e, hipStream_t st);
 // keep: cbuf / gates stored for steps t < keep only (0: every step)
 int launch_lstm_fwd(const float* xproj, const float* w_hh, const float* b_hh, const float* h0,
                     const float* c0, int S, int B, int H, float* hbuf, float* cbuf, float* gates,
-                    hipStream_t st, const int* skip, int keep = 0);
+                    hipStream_t st, const int* skip, int keep = 0, bool image = false);
+// image: w_ih / w_hh are W_ihT [din][4H] / W_hhT [H][4H] inside one weight image
+// (launch_lstm_weight_image: [W_ihT | W_hhT | 4H zeros]) and the r4 form loads
+// them by column; only where lstm_fwd_image_ok(B, H), else SMI_E_NOFIT
+bool lstm_fwd_image_ok(int B, int H);
+// the shapes whose input projection launch_lstm_fwd_x fuses (the r4 form then
+// keeps W_ih's column in registers too)
+inline bool lstm_fwd_x_fuses(int din, int H) { return din >= 1 && din <= 64 && H >= 1 && H <= 104; }
+int launch_lstm_weight_image(const float* w_ih, const float* w_hh, int din, int H, float* image,
+                             hipStream_t st);
 int launch_lstm_fwd_x(const float* x, int64_t ldx, int din, const float* w_ih, const float* b_ih,
                       const float* w_hh, const float* b_hh, const float* h0, const float* c0,
                       int S, int B, int H, float* hbuf, float* cbuf, float* gates,
-                      hipStream_t st, const int* skip, int keep = 0);
+                      hipStream_t st, const int* skip, int keep = 0, bool image = false);
 int launch_lstm_bwd(const float* dh, const float* gates, const float* cbuf, const float* w_hh,
                     int S, int B, int H, float* dgates, hipStream_t st, const int* skip);
 
