@@ -9,7 +9,11 @@
 // chain over them; the activations between layers stay in LDS, the weights
 // stream from L2 straight into MFMA registers.  Layer Y = X W^T with W [N][K]
 // row-major (k contiguous):
-//   * output features in 16-column tiles, tile nt on wave nt % 4;
+//   * output features in 16-column tiles, tile nt on wave nt % 4; in the
+//     two-row-tile forms a wave runs exactly the tiles it owns: the k loop
+//     exists unrolled for NT, NT - 1 and NT - 2 tiles and one wave-uniform
+//     branch per layer picks the body (hc_run), so no matrix-pipe time goes to
+//     tiles past the layer's last;
 //   * k in chunks of 16: lane (li, lk) reads X[li][16c + 4lk .. +3] from LDS
 //     and W[16 nt + li][16c + 4lk .. +3] from global memory (16-byte reads),
 //     and MFMA j of the chunk (v_mfma_f32_16x16x4_f32) takes element j of
@@ -17,7 +21,8 @@
 //     operands, so every chunk adds its exact 16-term dot product (an fmaf
 //     chain, like every f32 MFMA);
 //   * the weight reads of the next two chunks are in flight behind the MFMAs
-//     of the current one (register ring, sched_barrier pins the refills);
+//     of the current one (register ring, sched_barrier pins the refills), each
+//     addressed by the matrix's scalar base and one 32-bit offset register;
 //   * the epilogue (bias + ReLU, or the ReLU mask of the backward) writes the
 //     tile to LDS for the next layer and the workgroup copies the rows out to
 //     HBM as 16-byte stores (HA1 / HA2 for the backward, dH2 / dH1 for the
@@ -30,13 +35,16 @@
 // forward of the same phase writes W1^T and W2^T as a side job (the weights do
 // not change between a phase's forward and backward), so the backward's
 // weight reads are 16-byte reads too.  dZ W3 has K = out <= 16 (8 actions or
-// the value): a VALU pass in the order of the streaming small-K kernel.
+// the value): a VALU pass in the order of the streaming small-K kernel; in the
+// two-row-tile forms its W3 rows and HA2 masks are loaded with dZ, ahead of the
+// first barrier, and only the row groups that exist.
 //
 // Rows are the learner's [step][segment] rows; the weight gradients of the
 // three layers stay in the phase's grouped dW launch (linear_dw.hip).
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "pol_rows.hpp"
+#include <type_traits>
 
 namespace smi {
 
@@ -140,7 +148,10 @@ constexpr int HC_XB = 4;
 static_assert(HC_D >= 2, "ring of at least two chunks");
 template <int NT>
 struct HcStream {
-  const float* wp[NT];
+  // tile slot t's weight row as a byte offset from the (wave-uniform) matrix:
+  // a scalar base and one 32-bit address register per slot, not a 64-bit pair
+  const float* W;
+  unsigned wo[NT];
   float4 b[HC_D][NT];
   int K, nch, c0, cst, ntv;
   // k past K (the last chunk of a K % 16 != 0 layer) reads the row's last
@@ -149,23 +160,26 @@ struct HcStream {
   // are issued unconditionally (chunk indices clamped): a load issued on one
   // path only made the waitcnt pass assume the shorter queue everywhere and
   // wait for nearly every load in flight.
+  // (NV: the first NV tile slots only, hc_run's body for a wave of NV tiles)
+  template <int NV = NT>
   __device__ __forceinline__ void ldb(int c, float4 (&bb)[NT]) {
     const int lk = (threadIdx.x & 63) >> 4;
-    const int kk = min(16 * c + 4 * lk, K - 4);     // K % 4 == 0
+    const unsigned kb = 4u * (unsigned)min(16 * c + 4 * lk, K - 4);     // K % 4 == 0
 #pragma unroll
-    for (int t = 0; t < NT; ++t) bb[t] = *reinterpret_cast<const float4*>(wp[t] + kk);
+    for (int t = 0; t < NV; ++t)
+      bb[t] = *reinterpret_cast<const float4*>(reinterpret_cast<const char*>(W) + (size_t)(wo[t] + kb));
   }
-  __device__ __forceinline__ void init(const float* __restrict__ W, int64_t ldw, int K_, int N,
+  __device__ __forceinline__ void init(const float* __restrict__ W_, int ldw, int K_, int N,
                                        int nt0, int ntst, int c0_, int cst_) {
     const int li = threadIdx.x & 15;
     const int CT = (N + 15) >> 4;
-    K = K_; nch = (K + 15) >> 4; c0 = c0_; cst = cst_;
+    W = W_; K = K_; nch = (K + 15) >> 4; c0 = c0_; cst = cst_;
     // tiles of this wave that exist (wave-uniform)
     ntv = __builtin_amdgcn_readfirstlane(nt0 < CT ? (CT - 1 - nt0) / ntst + 1 : 0);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int n = min(16 * (nt0 + ntst * t) + li, N - 1);
-      wp[t] = W + (int64_t)n * ldw;
+      wo[t] = 4u * (unsigned)(n * ldw);          // < 4 HC_MAXK^2 bytes
     }
     ldb(min(c0, nch - 1), b[0]);
     ldb(min(c0 + cst, nch - 1), b[1]);
@@ -174,21 +188,12 @@ struct HcStream {
 
 // acc[rt][t] = A[16 rt .. 16 rt + 15][K] (LDS, lda) x W^T over the stream's
 // tiles and chunks: RT row tiles share every weight chunk (RT = 2 halves the
-// weight traffic per flop at large batches)
-template <int NT, int RT, bool CM = false>
-__device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda,
-                                       f32x4 (&acc)[RT][NT]) {
-  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
-#pragma unroll
-  for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-    for (int t = 0; t < NT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  if (S.ntv == 0) return;
-  const float* ap = sA + li * lda + 4 * lk;
-  // every tile slot runs (a slot past the last tile reads clamped rows and its
-  // result is dropped): per-tile guards made the compiler move the
-  // accumulators out of AGPRs every chunk.  NT is chosen per layer so that at
-  // most one slot per wave is idle.
+// weight traffic per flop at large batches).  hc_body is the k loop over the
+// first NV of the stream's NT tile slots, fully unrolled for that count.
+template <int NT, int NV, int RT, bool CM>
+__device__ __forceinline__ void hc_body(HcStream<NT>& S, const float* ap, int lda,
+                                        f32x4 (&acc)[RT][NT]) {
+  static_assert(NV >= 1 && NV <= NT, "a body for 1 .. NT tiles");
   // tile major (CM false): each tile's four k components back to back, the
   // row tiles interleaved; k-component major (CM): consecutive MFMAs go to
   // different accumulators.  Each accumulator takes x, y, z, w in order either
@@ -197,7 +202,7 @@ __device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda
   auto mm = [&](const float4 (&a)[RT], const float4 (&bb)[NT]) {
     if constexpr (!CM) {
 #pragma unroll
-      for (int t = 0; t < NT; ++t) {
+      for (int t = 0; t < NV; ++t) {
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mfma4(a[rt].x, bb[t].x, acc[rt][t]);
 #pragma unroll
@@ -209,19 +214,19 @@ __device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda
       }
     } else {
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NV; ++t)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mfma4(a[rt].x, bb[t].x, acc[rt][t]);
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NV; ++t)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mfma4(a[rt].y, bb[t].y, acc[rt][t]);
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NV; ++t)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mfma4(a[rt].z, bb[t].z, acc[rt][t]);
 #pragma unroll
-      for (int t = 0; t < NT; ++t)
+      for (int t = 0; t < NV; ++t)
 #pragma unroll
         for (int rt = 0; rt < RT; ++rt) acc[rt][t] = mfma4(a[rt].w, bb[t].w, acc[rt][t]);
     }
@@ -235,7 +240,7 @@ __device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda
   int c = S.c0;
   float4 a[HC_D][RT];
 #pragma unroll
-  for (int d = 2; d < HC_D; ++d) S.ldb(min(c + d * cst, cl), S.b[d]);
+  for (int d = 2; d < HC_D; ++d) S.template ldb<NV>(min(c + d * cst, cl), S.b[d]);
 #pragma unroll
   for (int d = 0; d < HC_D; ++d) lda_(min(c + d * cst, cl), a[d]);
   // steady state without conditionals (HC_D chunks per trip, every refill
@@ -246,7 +251,7 @@ __device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda
     for (int d = 0; d < HC_D; ++d) {
       mm(a[d], S.b[d]);
       lda_(c + (d + HC_D) * cst, a[d]);
-      S.ldb(c + (d + HC_D) * cst, S.b[d]);
+      S.template ldb<NV>(c + (d + HC_D) * cst, S.b[d]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -255,11 +260,46 @@ __device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda
   for (int d = 0; d < HC_D; ++d) {
     if (c + d * cst < nch) mm(a[d], S.b[d]);
     lda_(min(c + (d + HC_D) * cst, cl), a[d]);
-    S.ldb(min(c + (d + HC_D) * cst, cl), S.b[d]);
+    S.template ldb<NV>(min(c + (d + HC_D) * cst, cl), S.b[d]);
   }
 #pragma unroll
   for (int d = 0; d < HC_D; ++d)
     if (c + (d + HC_D) * cst < nch) mm(a[d], S.b[d]);
+}
+
+// A wave runs exactly the tiles it owns: S.ntv is wave-uniform, so ONE branch
+// per layer, outside the k loop, picks the body unrolled for NT, NT - 1 or
+// NT - 2 tiles (a guard per tile inside the loop made the compiler move the
+// accumulators out of AGPRs every chunk).  The slots past the body's count
+// keep their zero accumulators and the epilogues skip them.  NT is rounded up
+// to an instantiation (hc_nt, head_plan), so a wave can own fewer than NT - 2
+// tiles (5 slots, 9 or 10 tiles over four waves: 2 or 3 each): it runs the
+// NT - 2 body, whose surplus slots read clamped rows and are dropped like the
+// others.  At the C3 widths no wave has such a slot.  EX false keeps the one
+// body of NT slots, every slot run: the one-row-tile forms (with the branch
+// the forward's took up to 30 more registers, <5, 4, 1> 116 -> 146 and a wave
+// per SIMD fewer, and the learn at a rank's 128 segments measured 0.5 - 0.8 %
+// slower) and the input-gradient chain's 8-slot forms (their accumulators are
+// VGPRs beside 64 mask values; with the branch they spill 100 - 270 bytes of
+// scratch per lane).
+template <int NT, int RT, bool CM = false, bool EX = true>
+__device__ __forceinline__ void hc_run(HcStream<NT>& S, const float* sA, int lda,
+                                       f32x4 (&acc)[RT][NT]) {
+  const int lane = threadIdx.x & 63, li = lane & 15, lk = lane >> 4;
+#pragma unroll
+  for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+    for (int t = 0; t < NT; ++t) acc[rt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  if (S.ntv == 0) return;
+  const float* ap = sA + li * lda + 4 * lk;
+  constexpr int N1 = NT > 1 ? NT - 1 : 1, N2 = NT > 2 ? NT - 2 : N1;
+  if constexpr (NT == 1 || !EX) {
+    hc_body<NT, NT, RT, CM>(S, ap, lda, acc);
+  } else {
+    if (S.ntv >= NT) hc_body<NT, NT, RT, CM>(S, ap, lda, acc);
+    else if (N2 == N1 || S.ntv >= N1) hc_body<NT, N1, RT, CM>(S, ap, lda, acc);
+    else hc_body<NT, N2, RT, CM>(S, ap, lda, acc);
+  }
 }
 
 // the wave's tiles of a full-width layer into LDS rows: D(row 4lk + i, col li)
@@ -454,7 +494,7 @@ head_fwd_kernel(HeadFwdArgs a) {
       // to vmcnt(4) / vmcnt(1) instead of the ring depth (vmcnt(9..5)): an
       // explicit vmcnt(0) (expcnt / lgkmcnt left at their maxima) clears it
       __builtin_amdgcn_s_waitcnt(0x0F70);
-      hc_run<NT1, RT>(S1, s0, a.ld0, acc);
+      hc_run<NT1, RT, false, RT == 2>(S1, s0, a.ld0, acc);
       HEAD_TICK(0, 1);                            // layer 1 k loop
       S2.init(a.W2, a.h1, a.h1, a.h2, wave, 4, 0, 1);     // layer 2's stream, in flight
       hc_epi_load<NT2, 0, RT>(wave, a.h2, a.b2, nullptr, r0, a.rows, e2);
@@ -470,7 +510,7 @@ head_fwd_kernel(HeadFwdArgs a) {
     HcStream<1> S3;
     {   // layer 2: HA2 = relu(HA1 W2^T + b2)
       f32x4 acc[RT][NT2];
-      hc_run<NT2, RT>(S2, s1, a.ld1, acc);
+      hc_run<NT2, RT, false, RT == 2>(S2, s1, a.ld1, acc);
       HEAD_TICK(0, 4);                            // layer 2 k loop
       S3.init(a.W3, a.h2, a.h2, a.out, 0, 1, wave, 4);    // layer 3's stream
       if constexpr (RT == 2) {
@@ -573,123 +613,186 @@ head_bwd_kernel(HeadBwdArgs a) {
   const int out = a.out;
   HEAD_T0();
   // dZ rows (zero past out: the dH2 pass runs whole groups of 4 k), loaded
-  // first; dH1's weight stream (W2^T) and its masks are issued behind them and
-  // stay in flight through the dZ W3 pass
+  // first, and with them everything the dZ W3 pass's first 64 column groups
+  // read: the W3 row groups that exist (KG = ceil(out / 4), one for the value
+  // head) and the HA2 masks of the wave's rows, whose addresses depend on
+  // nothing the barrier orders — one memory round trip before the pass
+  // instead of two.  dH1's weight stream (W2^T) is issued behind them and
+  // stays in flight through the pass.
   const int zr = threadIdx.x >> 4, zk = threadIdx.x & 15;
+  const int nq = a.h2 >> 2;              // <= 128 column groups: at most two passes of 64
   HcStream<NTA> SA;
+  // The early issue holds 16 KG + 16 RT registers through the prologue and the
+  // branch on KG triples the pass's code: the two-row-tile 5-slot forms (the
+  // learner's at 1024 segments; 201 -> 239 VGPRs where two waves per SIMD
+  // leave 256) take both.  The one-row-tile forms (bound: three waves, 168
+  // VGPRs) spilled 36 - 168 bytes with either, the 2-slot two-row-tile forms
+  // fell from three waves to two: those and the 8-slot forms keep the loads
+  // after the barrier, of four clamped row groups (of the two that exist in
+  // the policy prologue forms, whose out is 8).
+  constexpr bool EARLY = RT == 2 && NTA == 5;
+  PolGradShared* pshp = nullptr;
   if constexpr (PG) {
-    // thread t < R: row r0 + t's inputs, then the weight stream, then the
-    // epoch's loss weights (and, one rank, its decision: every load above is
-    // in flight meanwhile), then the row's dz and d/dstd terms (pol_rows.hpp,
-    // the same ops as policy_rows_grad_kernel's row pass)
-    constexpr int AT = 8;
     __shared__ PolGradShared psh;
-    const int t = threadIdx.x;
-    const int64_t n = r0 + t;
-    const bool own = t < R && n < a.rows;
-    PolGradRow<AT> x;
-    if (own) x.load(a.pg, n, AT);
-    SA.init(a.W2T, a.h2, a.h2, a.h1, wave, 4, 0, 1);
-    float wsurr, wkl;
-    PolGradPre pre;
-    // one 64-partial slab per round trip: a deeper group of slabs in flight
-    // pushed the one-row-tile forms into scratch spills (<5, 2, 1>: 143 -> 168
-    // VGPRs + 80 B); a rank's 128 segments have 42 partials
-    if (pol_grad_weights<1>(a.pg, psh, wsurr, wkl, pre)) return;
-    const PolGradCols<AT> cols(pre, psh, AT);
-    const AdvNorm nadv(a.pg, pre.mom);
-    float glv[AT];
-#pragma unroll
-    for (int j = 0; j < AT; ++j) glv[j] = 0.f;
-    if (t < R) {
-      float dz[AT];
-      if (own) {
-        pol_grad_compute<AT>(a.pg, cols, nadv, x, wsurr, wkl, dz, glv);
-        st_row<AT>(a.pg.dz + n * AT, dz, AT);
-      } else {
-#pragma unroll
-        for (int j = 0; j < AT; ++j) dz[j] = 0.f;
-      }
-#pragma unroll
-      for (int j = 0; j < 16; ++j) sZ[t * 16 + j] = j < AT ? dz[j] : 0.f;
-    }
-    if (wave == 0) {     // R <= 64: every row on wave 0; fixed butterfly order
-#pragma unroll
-      for (int j = 0; j < AT; ++j) {
-        const float sg = wave_sum(glv[j]);
-        if (lane == 0) a.pg.lvpart[(int64_t)blockIdx.x * AT + j] = sg;
-      }
-    }
-  } else {
-    float zv[RT];
+    pshp = &psh;
+  }
+  // dH2 = (dZ W3) * [HA2 > 0], K = out: lane = a 4-column group, wave = 4
+  // rows of each row tile; the k-ordered fmaf chain from 0 (steps k >= out add
+  // 0 * w).  Per column pass, every W3 row group and the HA2 masks of all row
+  // tiles are loaded before the first FMA: one memory round trip per pass
+  // instead of one per (row tile, k group) — the same FMAs in the same order.
+  // Returns true where the policy prologue's decision ends the launch.
+  // (the dZ loads and the weight stream's first chunks ahead of the branch on
+  // KG: what is in flight across it is the same on every path)
+  float zv[RT];
+  if constexpr (!PG) {
 #pragma unroll
     for (int rt = 0; rt < RT; ++rt)
       zv[rt] = a.dZ[min(r0 + 16 * rt + zr, a.rows - 1) * out + min(zk, out - 1)];
     SA.init(a.W2T, a.h2, a.h2, a.h1, wave, 4, 0, 1);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) sZ[(16 * rt + zr) * 16 + zk] = zk < out ? zv[rt] : 0.f;
   }
-  // padding columns of dH2 (the next layer's last chunk)
-  const int h2p = a.ld2 - 4;
-  for (int e = threadIdx.x; e < R * (h2p - a.h2); e += kWG) {
-    const int r = e / (h2p - a.h2), c = e - r * (h2p - a.h2);
-    s2[r * a.ld2 + a.h2 + c] = 0.f;
-  }
-  __syncthreads();
-  // dH2 = (dZ W3) * [HA2 > 0], K = out: lane = a 4-column group, wave = 4
-  // rows of each row tile; the k-ordered fmaf chain from 0 (steps k >= out add
-  // 0 * w).  Per column pass, every W3 row group (out <= 16: <= 4 groups) and
-  // the HA2 masks of all row tiles are loaded before the first FMA: one memory
-  // round trip per pass instead of one per (row tile, k group) — the same FMAs
-  // in the same order
-  const int nq = a.h2 >> 2;              // <= 128: at most two passes, unrolled (a loop
-#pragma unroll                           // header made the first pass drain every load
-  for (int q0 = 0; q0 < 128; q0 += 64) {  // in flight, the weight prefetch included)
-    if (q0 >= nq) break;
-    const bool qv = q0 + lane < nq;
-    const int q = qv ? q0 + lane : nq - 1;
-    constexpr int KGM = 4;               // k groups of 4 (out <= 16)
-    f32x4 w[KGM][4], m[RT][4];
+  auto dz_w3 = [&](auto kgc) -> bool {
+    constexpr int KG = decltype(kgc)::value;     // k groups of 4 loaded (out <= 4 KG)
+    f32x4 w[KG][4], m[RT][4];
+    auto ldwm = [&](int q) {
 #pragma unroll
-    for (int g = 0; g < KGM; ++g)
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        w[g][j] = *reinterpret_cast<const f32x4*>(a.W3 + (int64_t)min(4 * g + j, out - 1) * a.h2 + 4 * q);
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int64_t rr = min(r0 + 16 * rt + 4 * wave + i, a.rows - 1);
-        m[rt][i] = *reinterpret_cast<const f32x4*>(a.HA2 + rr * a.h2 + 4 * q);
-      }
-#pragma unroll
-    for (int rt = 0; rt < RT; ++rt) {
-      f32x4 v[4];
-#pragma unroll
-      for (int i = 0; i < 4; ++i) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int g = 0; g < KGM; ++g) {
-        if (4 * g >= out) break;
+      for (int g = 0; g < KG; ++g)
 #pragma unroll
         for (int j = 0; j < 4; ++j)
+          w[g][j] = *reinterpret_cast<const f32x4*>(a.W3 + (int64_t)min(4 * g + j, out - 1) * a.h2 + 4 * q);
 #pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const float z = sZ[(16 * rt + 4 * wave + i) * 16 + 4 * g + j];
-            v[i][0] = fmaf(z, w[g][j][0], v[i][0]); v[i][1] = fmaf(z, w[g][j][1], v[i][1]);
-            v[i][2] = fmaf(z, w[g][j][2], v[i][2]); v[i][3] = fmaf(z, w[g][j][3], v[i][3]);
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int64_t rr = min(r0 + 16 * rt + 4 * wave + i, a.rows - 1);
+          m[rt][i] = *reinterpret_cast<const f32x4*>(a.HA2 + rr * a.h2 + 4 * q);
+        }
+    };
+    auto fma_store = [&](bool qv, int q) {
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) {
+        f32x4 v[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int g = 0; g < KG; ++g) {
+          if (4 * g >= out) break;
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+              const float z = sZ[(16 * rt + 4 * wave + i) * 16 + 4 * g + j];
+              v[i][0] = fmaf(z, w[g][j][0], v[i][0]); v[i][1] = fmaf(z, w[g][j][1], v[i][1]);
+              v[i][2] = fmaf(z, w[g][j][2], v[i][2]); v[i][3] = fmaf(z, w[g][j][3], v[i][3]);
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+          const int r = 16 * rt + 4 * wave + i;
+          const f32x4 o = {m[rt][i][0] > 0.f ? v[i][0] : 0.f, m[rt][i][1] > 0.f ? v[i][1] : 0.f,
+                           m[rt][i][2] > 0.f ? v[i][2] : 0.f, m[rt][i][3] > 0.f ? v[i][3] : 0.f};
+          if (qv) {
+            *reinterpret_cast<f32x4*>(s2 + r * a.ld2 + 4 * q) = o;
+            if (r0 + r < a.rows) *reinterpret_cast<f32x4*>(a.dH2 + (r0 + r) * a.h2 + 4 * q) = o;
           }
-      }
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int r = 16 * rt + 4 * wave + i;
-        const f32x4 o = {m[rt][i][0] > 0.f ? v[i][0] : 0.f, m[rt][i][1] > 0.f ? v[i][1] : 0.f,
-                         m[rt][i][2] > 0.f ? v[i][2] : 0.f, m[rt][i][3] > 0.f ? v[i][3] : 0.f};
-        if (qv) {
-          *reinterpret_cast<f32x4*>(s2 + r * a.ld2 + 4 * q) = o;
-          if (r0 + r < a.rows) *reinterpret_cast<f32x4*>(a.dH2 + (r0 + r) * a.h2 + 4 * q) = o;
         }
       }
+    };
+    const bool qv0 = lane < nq;
+    const int qa = qv0 ? lane : nq - 1;
+    if constexpr (PG) {
+      // thread t < R: row r0 + t's inputs, then the pass's operands and the
+      // weight stream, then the epoch's loss weights (and, one rank, its
+      // decision: every load above is in flight meanwhile), then the row's dz
+      // and d/dstd terms (pol_rows.hpp, the same ops as
+      // policy_rows_grad_kernel's row pass)
+      constexpr int AT = 8;
+      PolGradShared& psh = *pshp;
+      const int t = threadIdx.x;
+      const int64_t n = r0 + t;
+      const bool own = t < R && n < a.rows;
+      PolGradRow<AT> x;
+      if (own) x.load(a.pg, n, AT);
+      SA.init(a.W2T, a.h2, a.h2, a.h1, wave, 4, 0, 1);
+      if constexpr (EARLY) ldwm(qa);
+      float wsurr, wkl;
+      PolGradPre pre;
+      // one 64-partial slab per round trip: a deeper group of slabs in flight
+      // pushed the one-row-tile forms into scratch spills (<5, 2, 1>: 143 -> 168
+      // VGPRs + 80 B); a rank's 128 segments have 42 partials
+      if (pol_grad_weights<1>(a.pg, psh, wsurr, wkl, pre)) return true;
+      const PolGradCols<AT> cols(pre, psh, AT);
+      const AdvNorm nadv(a.pg, pre.mom);
+      float glv[AT];
+#pragma unroll
+      for (int j = 0; j < AT; ++j) glv[j] = 0.f;
+      if (t < R) {
+        float dz[AT];
+        if (own) {
+          pol_grad_compute<AT>(a.pg, cols, nadv, x, wsurr, wkl, dz, glv);
+          st_row<AT>(a.pg.dz + n * AT, dz, AT);
+        } else {
+#pragma unroll
+          for (int j = 0; j < AT; ++j) dz[j] = 0.f;
+        }
+#pragma unroll
+        for (int j = 0; j < 16; ++j) sZ[t * 16 + j] = j < AT ? dz[j] : 0.f;
+      }
+      if (wave == 0) {     // R <= 64: every row on wave 0; fixed butterfly order
+#pragma unroll
+        for (int j = 0; j < AT; ++j) {
+          const float sg = wave_sum(glv[j]);
+          if (lane == 0) a.pg.lvpart[(int64_t)blockIdx.x * AT + j] = sg;
+        }
+      }
+    } else {
+      if constexpr (EARLY) ldwm(qa);
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt) sZ[(16 * rt + zr) * 16 + zk] = zk < out ? zv[rt] : 0.f;
     }
+    // padding columns of dH2 (the next layer's last chunk)
+    const int h2p = a.ld2 - 4;
+    for (int e = threadIdx.x; e < R * (h2p - a.h2); e += kWG) {
+      const int r = e / (h2p - a.h2), c = e - r * (h2p - a.h2);
+      s2[r * a.ld2 + a.h2 + c] = 0.f;
+    }
+    __syncthreads();
+    if constexpr (EARLY) {
+      // (the barrier waits for every load above; the pins keep the operand
+      // loads on its far side, where the compiler would otherwise sink them to
+      // their first use)
+#pragma unroll
+      for (int g = 0; g < KG; ++g)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) asm volatile("" : "+v"(w[g][j]));
+#pragma unroll
+      for (int rt = 0; rt < RT; ++rt)
+#pragma unroll
+        for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(m[rt][i]));
+    } else {
+      ldwm(qa);
+    }
+    fma_store(qv0, qa);
+    if (nq > 64) {                       // h2 > 256: the second 64 column groups
+      const bool qv = 64 + lane < nq;
+      const int q = qv ? 64 + lane : nq - 1;
+      ldwm(q);
+      fma_store(qv, q);
+    }
+    return false;
+  };
+  {
+    bool stop;
+    if constexpr (PG) {
+      stop = dz_w3(std::integral_constant<int, 2>{});           // out == 8
+    } else if constexpr (!EARLY) {
+      stop = dz_w3(std::integral_constant<int, 4>{});
+    } else {
+      if (out <= 4) stop = dz_w3(std::integral_constant<int, 1>{});
+      else if (out <= 8) stop = dz_w3(std::integral_constant<int, 2>{});
+      else stop = dz_w3(std::integral_constant<int, 4>{});
+    }
+    if (stop) return;
   }
   // dH1's masks, in flight behind its k loop (issued here rather than with the
   // weight prefetch: fewer registers live through the dZ W3 pass)
@@ -700,7 +803,7 @@ head_bwd_kernel(HeadBwdArgs a) {
   HcStream<NTB> SB;
   {   // dH1 = (dH2 W2) * [HA1 > 0] = dH2 (W2^T)^T
     f32x4 acc[RT][NTA];
-    hc_run<NTA, RT, true>(SA, s2, a.ld2, acc);
+    hc_run<NTA, RT, true, (RT == 2 && NTA < 8)>(SA, s2, a.ld2, acc);
     HEAD_TICK(1, 1);                              // dH1 k loop
     if (a.dxn > 0)      // dX's weight stream (rows dx0.. of W1^T), in flight
       SB.init(a.W1T + (int64_t)a.dx0 * a.h1, a.h1, a.h1, a.dxn, wave, 4, 0, 1);
@@ -713,7 +816,7 @@ head_bwd_kernel(HeadBwdArgs a) {
   if (a.dxn <= 0) { HEAD_END(1); return; }
   {   // dX = dH1 W1[:, dx0 : dx0 + dxn]
     f32x4 acc[RT][NTB];
-    hc_run<NTB, RT, true>(SB, s1, a.ld1, acc);
+    hc_run<NTB, RT, true, RT == 2>(SB, s1, a.ld1, acc);
     HEAD_TICK(1, 4);                              // dX k loop
     const int CT = (a.dxn + 15) >> 4;
 #pragma unroll
