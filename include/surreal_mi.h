@@ -637,6 +637,52 @@ int smi_cnn_backward(const float* params, const uint8_t* pix, const uint8_t* pix
                      const float* a2, const float* dz, int64_t lddz, float* grad, void* scratch,
                      int64_t scratch_bytes, void* stream);
 
+/* One general convolution layer over contiguous NCHW tensors: the conv_layers of
+ * FFQfunc (q_net.py:82-102,112-119; SAME-padded there, pad = k / 2), each an
+ * implicit GEMM on the fp32 MFMA (no im2col matrix in memory; the zero halo
+ * comes from the gather).  With Ho = (h + 2 pad - k) / stride + 1 and Wo
+ * likewise (integer division), a layer is accepted when
+ *   1 <= k <= 8, 1 <= stride <= min(k, 4), 0 <= pad < k, 1 <= cin, cout <= 128,
+ *   Ho >= 1, Wo >= 1 (and h, w <= 16384, cin h w and cout Ho Wo below 2^31);
+ * odd h / w, strides that do not divide k, trailing rows or columns no window
+ * covers and channel counts that are no multiple of 16 are all fine.  Anything
+ * else, a NULL pointer or too little scratch is SMI_E_ARG with smi_last_error()
+ * set and nothing launched; n == 0 is SMI_OK without a launch.  Pointers need
+ * element alignment only (weights that are 16-byte aligned with cin k k % 4 == 0
+ * are read with 16-byte loads).  wgt is (cout, cin, k, k), torch's Conv2d order.
+ *   forward: y[n][co][oy][ox] = act(b[co] + sum w[co][ci][ky][kx] *
+ *            x[n][ci][oy s + ky - pad][ox s + kx - pad]), taps outside the image
+ *            0; act 0 none, 1 ReLU.  x is float32, or uint8 when x_u8; with
+ *            div255 the layer computes on x / 255: the kernels feed the
+ *            unscaled values to the MFMA and divide the SUMS by 255 (as the
+ *            pixel stem above does), so it equals conv(fl(x / 255)) to fp32
+ *            rounding of the sum.  Row n of y is the flattened (C, H, W)-order
+ *            feature row (U.flatten_conv).
+ *   backward_input: dx = [relu_mask > 0] * conv^T(dy, w); relu_mask (optional)
+ *            has dx's shape: the layer's own input activation, the convention
+ *            of smi_linear_backward_input.  Dense taps per stride-parity class
+ *            of the input pixels: no scatter, no atomics.
+ *   backward_weight: dw[co][ci][ky][kx] = sum_{n,oy,ox} dy * x (x / 255 with
+ *            div255), db[co] = sum dy; both WRITTEN (not accumulated), anywhere
+ *            in a gradient image.  The reduction over n Ho Wo is split over
+ *            workgroups into `scratch` (smi_conv2d_scratch_bytes; every partial
+ *            is written before it is read) and summed in a fixed order: no
+ *            float atomics, two runs are bit-identical.
+ * smi_conv2d_scratch_bytes returns -1 for a geometry out of range. */
+int smi_conv2d_out_hw(int h, int w, int k, int stride, int pad, int* ho, int* wo);
+int64_t smi_conv2d_scratch_bytes(int64_t n, int cin, int h, int w, int cout, int k, int stride,
+                                 int pad);
+int smi_conv2d_forward(const void* x, int x_u8, int div255, int64_t n, int cin, int h, int w,
+                       const float* wgt, const float* bias, int cout, int k, int stride, int pad,
+                       int act, float* y, void* stream);
+int smi_conv2d_backward_input(const float* dy, int64_t n, int cin, int h, int w, const float* wgt,
+                              int cout, int k, int stride, int pad, const float* relu_mask,
+                              float* dx, void* stream);
+int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                               int cin, int h, int w, int cout, int k, int stride, int pad,
+                               float* dw, float* db, void* scratch, int64_t scratch_bytes,
+                               void* stream);
+
 /* running_sum += sum_in, running_sumsq += sumsq_in, count += rows — the
  * data-parallel z_update after the column statistics were all-reduced. */
 int smi_zfilter_accumulate(const float* sum_in, const float* sumsq_in, int dim, float rows,

@@ -217,6 +217,13 @@ _SIGS = {
     'smi_cnn_forward': (c_int, [P, P, P, c_i64, c_i64, c_i64] + [c_int] * 4 + [P, P, P, c_i64, P]),
     'smi_cnn_backward': (c_int, [P, P, P, c_i64, c_i64, c_i64] + [c_int] * 4 +
                          [P, P, P, c_i64, P, P, c_i64, P]),
+    'smi_conv2d_out_hw': (c_int, [c_int] * 5 + [P, P]),
+    'smi_conv2d_scratch_bytes': (c_i64, [c_i64] + [c_int] * 7),
+    'smi_conv2d_forward': (c_int, [P, c_int, c_int, c_i64, c_int, c_int, c_int, P, P] + [c_int] * 5 +
+                           [P, P]),
+    'smi_conv2d_backward_input': (c_int, [P, c_i64, c_int, c_int, c_int, P] + [c_int] * 4 + [P, P, P]),
+    'smi_conv2d_backward_weight': (c_int, [P, P, c_int, c_int, c_i64] + [c_int] * 7 +
+                                   [P, P, P, c_i64, P]),
     'smi_ppo_rnn_phase': (c_int, [ctypes.POINTER(RNNArgs), c_int, c_int, P]),
     'smi_lstm_forward': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     'smi_lstm_backward': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),

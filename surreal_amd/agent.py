@@ -347,10 +347,10 @@ class QAgentBatch(object):
 
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
         from .config import ConfigError
-        from .dqn import FFQfunc, dqn_specs
+        from .dqn import FFQfunc, dqn_model_kwargs
         lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
         ec = env_config if isinstance(env_config, Config) else Config(env_config)
-        D, A, hidden, dueling = dqn_specs(lc, ec)
+        D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)
         ex = lc.algo.exploration
         if str(ex.schedule).lower() != 'linear':
             raise ConfigError('QAgentBatch runs the linear exploration schedule only, got '
@@ -363,7 +363,8 @@ class QAgentBatch(object):
         self.action_dim, self.obs_dim = A, D
         self.device = torch.device(device) if device is not None else torch.device('cuda')
         self._ctx = L.Context(self.device)      # own workspace (re-entrancy)
-        self.q_func = FFQfunc(D, A, hidden, dueling, self.device, torch.Generator().manual_seed(0))
+        self.q_func = FFQfunc(D, A, hidden, dueling, self.device, torch.Generator().manual_seed(0),
+                              **conv_kw)
         self.T = np.zeros(self.n, dtype=np.int64)           # q_agent.py:33, per agent
         self._bufs = {}
         self._greedy = torch.zeros(self.n, dtype=torch.int32, device=self.device)
@@ -382,16 +383,25 @@ class QAgentBatch(object):
         return 1.0 + fraction * (self.final_eps - 1.0)
 
     def act(self, obs):
-        """obs: (N, D) low-dim observations or {'low_dim': {key: (N, D)}};
+        """obs: (N, D) low-dim observations or {'low_dim': {key: (N, D)}}; for a
+        conv model uint8 (N, C, H, W) frames or {'pixel': {camera: frames}};
         returns the N actions (int64 numpy)."""
         import random
         from .dqn import _QNet
         self._ctx.make_current()
-        if isinstance(obs, dict):
-            obs = obs['low_dim'][list(obs['low_dim'])[0]]
-        x = np.ascontiguousarray(obs, dtype=np.float32)
-        if x.ndim != 2 or x.shape != (self.n, self.obs_dim):
-            raise ValueError(f'expected observations ({self.n}, {self.obs_dim}), got {x.shape}')
+        if self.q_func.convs:
+            if isinstance(obs, dict):
+                obs = obs['pixel'][list(obs['pixel'])[0]]
+            x = np.ascontiguousarray(obs)
+            if x.dtype != np.uint8 or x.shape != (self.n,) + self.q_func.input_shape:
+                raise ValueError(f'expected uint8 frames {(self.n,) + self.q_func.input_shape}, got '
+                                 f'{x.dtype} {x.shape}')
+        else:
+            if isinstance(obs, dict):
+                obs = obs['low_dim'][list(obs['low_dim'])[0]]
+            x = np.ascontiguousarray(obs, dtype=np.float32)
+            if x.ndim != 2 or x.shape != (self.n, self.obs_dim):
+                raise ValueError(f'expected observations ({self.n}, {self.obs_dim}), got {x.shape}')
         A = self.action_dim
         actions = np.zeros(self.n, dtype=np.int64)
         greedy = np.zeros(self.n, dtype=bool)

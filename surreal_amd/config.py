@@ -245,6 +245,26 @@ def discrete_env_config(obs_dim, n_actions):
     })
 
 
+def discrete_pixel_env_config(camera, n_actions, frame_stacks=1):
+    """env_config of an Atari-style env: one uint8 camera, n_actions discrete
+    actions, no low-dim modality.  `camera` is ONE frame's (C, H, W); the
+    observation stacks frame_stacks of them along the channels
+    (frame_stack_concatenate_on_env), so obs_spec.pixel.camera0 is
+    (frame_stacks * C, H, W): the shape FFQfunc's first convolution reads and
+    the frame-shared replay stores one frame at a time."""
+    C, H, W = (int(v) for v in camera)
+    fs = int(frame_stacks)
+    if fs < 1:
+        raise ConfigError('frame_stacks must be a positive integer')
+    return Config({
+        'pixel_input': True,
+        'frame_stacks': fs,
+        'frame_stack_concatenate_on_env': True,
+        'obs_spec': {'pixel': {'camera0': (fs * C, H, W)}},
+        'action_spec': {'dim': (int(n_actions),), 'type': 'discrete'},
+    })
+
+
 def gym_env_config(obs_dim, act_dim, pixel_input=False):
     """env_config with obs_spec/action_spec as make_env_config fills them
     (surreal/env/make_env.py:16-38) for a flat low-dim gym env."""

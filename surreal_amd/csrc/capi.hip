@@ -7,6 +7,7 @@
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "rnn_layout.hpp"
+#include "conv_plan.hpp"
 
 namespace smi {
 
@@ -804,6 +805,66 @@ int smi_cnn_backward(const float* params, const uint8_t* pix, const uint8_t* pix
   return cnn_backward(params, pr, C, H, W, F, rows, a1, a2, dz, lddz, grad, dA2, part,
                       SMI_STREAM(stream), nullptr);
 }
+
+int smi_conv2d_out_hw(int h, int w, int k, int stride, int pad, int* ho, int* wo) {
+  REQUIRE(ho && wo, "conv2d_out_hw: null output");
+  REQUIRE(conv_geom_ok(1, h, w, 1, k, stride, pad),
+          "conv2d: need 1 <= k <= 8, 1 <= stride <= min(k, 4), 0 <= pad < k, Ho, Wo >= 1");
+  const ConvGeom g = conv_geom(1, h, w, 1, k, stride, pad);
+  *ho = g.ho;
+  *wo = g.wo;
+  return SMI_OK;
+}
+
+int64_t smi_conv2d_scratch_bytes(int64_t n, int cin, int h, int w, int cout, int k, int stride,
+                                 int pad) {
+  if (n < 0 || !conv_geom_ok(cin, h, w, cout, k, stride, pad)) {
+    set_error(SMI_E_ARG, "conv2d_scratch_bytes: geometry out of range");
+    return -1;
+  }
+  return conv_scratch_bytes(conv_geom(cin, h, w, cout, k, stride, pad), n);
+}
+
+#define CONV_GEOM_CHECK(what)                                                                     \
+  REQUIRE(conv_geom_ok(cin, h, w, cout, k, stride, pad),                                          \
+          what ": need 1 <= k <= 8, 1 <= stride <= min(k, 4), 0 <= pad < k, 1 <= cin, cout <= "   \
+               "128, Ho, Wo >= 1")
+
+int smi_conv2d_forward(const void* x, int x_u8, int div255, int64_t n, int cin, int h, int w,
+                       const float* wgt, const float* bias, int cout, int k, int stride, int pad,
+                       int act, float* y, void* stream) {
+  REQUIRE(x && wgt && bias && y && n >= 0, "conv2d_forward: null pointer or negative n");
+  REQUIRE(act == ACT_NONE || act == ACT_RELU, "conv2d_forward: act is 0 (none) or 1 (ReLU)");
+  CONV_GEOM_CHECK("conv2d_forward");
+  return conv2d_forward(x, x_u8 != 0, div255 != 0, n, conv_geom(cin, h, w, cout, k, stride, pad),
+                        wgt, bias, act, y, SMI_STREAM(stream));
+}
+
+int smi_conv2d_backward_input(const float* dy, int64_t n, int cin, int h, int w, const float* wgt,
+                              int cout, int k, int stride, int pad, const float* relu_mask,
+                              float* dx, void* stream) {
+  REQUIRE(dy && wgt && dx && n >= 0, "conv2d_backward_input: null pointer or negative n");
+  CONV_GEOM_CHECK("conv2d_backward_input");
+  return conv2d_backward_input(dy, n, conv_geom(cin, h, w, cout, k, stride, pad), wgt, relu_mask,
+                               dx, SMI_STREAM(stream));
+}
+
+int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                               int cin, int h, int w, int cout, int k, int stride, int pad,
+                               float* dw, float* db, void* scratch, int64_t scratch_bytes,
+                               void* stream) {
+  REQUIRE(dy && x && dw && db && n >= 0, "conv2d_backward_weight: null pointer or negative n");
+  CONV_GEOM_CHECK("conv2d_backward_weight");
+  const ConvGeom g = conv_geom(cin, h, w, cout, k, stride, pad);
+  if (n == 0) return SMI_OK;
+  REQUIRE(scratch && scratch_bytes >= conv_scratch_bytes(g, n) &&
+          (reinterpret_cast<uintptr_t>(scratch) & 3) == 0,
+          "conv2d_backward_weight: scratch missing, misaligned or smaller than "
+          "smi_conv2d_scratch_bytes");
+  return conv2d_backward_weight(dy, x, x_u8 != 0, div255 != 0, n, g, dw, db,
+                                static_cast<float*>(scratch), SMI_STREAM(stream));
+}
+#undef CONV_GEOM_CHECK
 
 int smi_ppo_rnn_phase(const smi_ppo_rnn_args* a, int phase, int epoch, void* stream) {
   REQUIRE(a, "ppo_rnn: null args");

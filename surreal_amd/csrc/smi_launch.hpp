@@ -10,6 +10,7 @@ namespace smi {
 
 struct PolRowArgs;     // pol_rows.hpp
 struct LstmFwdArgs;    // lstm_cell.hpp
+struct ConvGeom;       // conv_plan.hpp
 
 // ---- ops_kernels.hip
 int launch_zfilter_apply(const float* x, float* out, int64_t rows, int dim, const float* s,
@@ -72,6 +73,14 @@ int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
                   float* y_out, float* stats, hipStream_t st);
 int launch_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t vs, int64_t rows,
                       int A, int dueling, int32_t* out, hipStream_t st);
+// ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
+int conv2d_forward(const void* x, int x_u8, int div255, int64_t n, const ConvGeom& g,
+                   const float* wgt, const float* bias, int act, float* y, hipStream_t st);
+int conv2d_backward_input(const float* dy, int64_t n, const ConvGeom& g, const float* wgt,
+                          const float* mask, float* dx, hipStream_t st);
+// part: conv_scratch_bytes(g, n) of scratch, written before it is read
+int conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                           const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st);
 // ---- linear_kernels.hip
 int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,

@@ -29,10 +29,36 @@ half of H1 (and write their half of dH1) through its leading dimension.
 state_dict names are the reference's: fc_action_layers.k.{weight,bias} and
 fc_state_layers.k.{weight,bias}, each an nn.Parameter view of the flat buffer.
 
-Out of scope (ConfigError): model.convs (the reference's Q-net convolutions
-are SAME-padded and of free shape; the CNN kernels here are the fixed
-VALID-padded PPO / DDPG stem), a 'pixel' obs spec, a non-discrete action spec.
-There is no data-parallel form.
+Pixel observations (model.convs on a pixel-only obs spec; dqn_conv_specs): the
+reference's conv_layers (q_net.py:82-102,112-119: nn.Conv2d(padding = k // 2),
+'SAME' mode, ReLU after each, U.flatten_conv) run on the general convolution
+layer of conv_kernels.hip (smi_conv2d_*), one launch per layer and direction.
+The flat buffer then starts with the conv layers, [w (cout, cin, k, k) | b]
+each, followed by the layout above with D = prod(pre-FC shape); state_dict
+names and order are the reference's: conv_layers.k.{weight,bias}, then
+fc_action_layers.*, then fc_state_layers.*.  One learn() is: target stem +
+heads on obs_next, online stem + heads on obs (activations kept), online on
+obs_next with double_q, smi_dqn_td, the heads' backward, the first FC layer's
+input gradient masked by the last conv activation, per conv layer the weight
+gradient and (except layer 0) the input gradient into the same gradient image,
+and the one smi_adam_clip over the whole flat buffer: the norm clip covers
+conv and FC parameters together, as clip_grad_norm_ over q_func.parameters().
+Frames stay uint8 on the device and are read in place (a replay's
+sample_batch() output is not copied); model.is_uint8 (x / 255.0, q_net.py:
+113-115) defaults to True here, where the reference's build_ffqfunc leaves
+FFQfunc.is_uint8 at False and so feeds 0..255 to the first convolution: Atari
+frames are bytes and the scaled input is what the class documents; False runs
+the reference builder's behaviour.  The 1 / 255 is folded into the kernels'
+epilogues (conv_kernels.hip).
+Initialisation of every view (Linear and Conv) is this build's own rule,
+torch's default for nn.Linear / nn.Conv2d (U(+-1/sqrt(fan_in)) for weight and
+bias); U.conv_fc_init is torchx-side and unpinned, parity tests load weights.
+
+Out of scope (ConfigError): model.convs on a low-dimensional obs spec, a
+'pixel' obs spec without convs or together with 'low_dim' (FFQfunc has one
+input), more than 4 conv layers or a layer outside the kernel's ranges
+(1 <= k <= 8, 1 <= stride <= min(k, 4), 1 <= channels <= 128), a non-discrete
+action spec.  There is no data-parallel form.
 """
 import numpy as np
 import torch
@@ -61,55 +87,190 @@ class _LinearAt(_LinearView):
         self.bias = nn.Parameter(flat[b_off:b_off + d_out])
 
 
-def dqn_specs(learner_config, env_config):
-    """(D, A, hidden sizes, dueling) of build_ffqfunc (q_net.py:122-134) for the
-    configurations this package runs; everything else raises ConfigError."""
-    lc, ec = learner_config, env_config
+def _action_dim(ec):
     spec = ec['action_spec']
     if spec.get('type') != 'discrete':
         raise ConfigError('DQN needs a discrete action spec, got {!r}'.format(spec.get('type')))
     if len(spec['dim']) != 1:
         raise ConfigError('DQN action_spec.dim must have one entry')
-    if list(lc['model'].get('convs') or []):
-        raise ConfigError('DQN model.convs is not supported (SAME-padded free-shape convolutions; '
-                          'only low-dimensional observations)')
-    obs = ec['obs_spec']
-    if 'pixel' in obs or bool(ec.get('pixel_input', False)):
-        raise ConfigError('DQN pixel observations are not supported')
-    D = int(sum(v[0] for v in obs['low_dim'].values()))
+    return int(spec['dim'][0])
+
+
+def _hidden_sizes(lc):
     hidden = [int(h) for h in lc['model']['fc_hidden_sizes']]
     if not 1 <= len(hidden) <= 3 or min(hidden) < 1:
         raise ConfigError('DQN model.fc_hidden_sizes must hold 1 to 3 positive widths')
-    return D, int(spec['dim'][0]), hidden, bool(lc['model']['dueling'])
+    return hidden
+
+
+def dqn_specs(learner_config, env_config):
+    """(D, A, hidden sizes, dueling) of build_ffqfunc (q_net.py:122-134) for a
+    low-dimensional obs spec; everything else raises ConfigError (a pixel-only
+    spec with model.convs goes through dqn_conv_specs)."""
+    lc, ec = learner_config, env_config
+    A = _action_dim(ec)
+    if list(lc['model'].get('convs') or []):
+        raise ConfigError('DQN model.convs needs a pixel-only obs spec (SAME-padded convolutions '
+                          'over camera0); this spec is low-dimensional')
+    obs = ec['obs_spec']
+    if 'pixel' in obs or bool(ec.get('pixel_input', False)):
+        raise ConfigError('DQN pixel observations need model.convs and no low_dim modality '
+                          '(dqn_conv_specs)')
+    D = int(sum(v[0] for v in obs['low_dim'].values()))
+    return D, A, _hidden_sizes(lc), bool(lc['model']['dueling'])
+
+
+MAX_CONVS = 4
+
+
+def conv_chain(input_shape, convs):
+    """([(cin, H, W, cout, k, stride, pad)] per layer, pre-FC shape (C, H, W)) of
+    q_net.py:85-102: pad = k // 2 and U.infer_shape_conv2d's
+    (H + 2 pad - k) // stride + 1.  ValueError for an invalid input or pre-FC
+    shape (q_net.py:83,104-105)."""
+    if len(input_shape) != 3:
+        raise ValueError('convs need a 3-D input_shape (C, H, W), got {}'.format(tuple(input_shape)))
+    C, H, W = (int(v) for v in input_shape)
+    layers = []
+    for cout, k, s in convs:
+        cout, k, s = int(cout), int(k), int(s)
+        if min(C, H, W) < 1:
+            break
+        layers.append((C, H, W, cout, k, s, k // 2))
+        H, W = (H + 2 * (k // 2) - k) // s + 1, (W + 2 * (k // 2) - k) // s + 1
+        C = cout
+    if min(C, H, W) < 1:
+        raise ValueError('Pre-FC shape has invalid size: {}'.format((C, H, W)))
+    return layers, (C, H, W)
+
+
+def check_convs(convs, in_channels):
+    """model.convs as [[cout, k, stride]] within the ranges of smi_conv2d_*"""
+    convs = [list(c) for c in (convs or [])]
+    if not 1 <= len(convs) <= MAX_CONVS:
+        raise ConfigError('DQN model.convs must hold 1 to {} layers, got {}'.format(MAX_CONVS,
+                                                                                    len(convs)))
+    if not 1 <= int(in_channels) <= 128:
+        raise ConfigError('DQN pixel input must have 1 to 128 channels, got {}'.format(in_channels))
+    for c in convs:
+        if len(c) != 3:
+            raise ConfigError('DQN model.convs entries are [cout, kernel_size, stride], got '
+                              '{!r}'.format(c))
+        cout, k, s = (int(v) for v in c)
+        if not (1 <= cout <= 128 and 1 <= k <= 8 and 1 <= s <= min(k, 4)):
+            raise ConfigError('DQN model.convs layer {!r} is outside 1 <= cout <= 128, 1 <= k <= 8, '
+                              '1 <= stride <= min(k, 4)'.format(c))
+    return [[int(v) for v in c] for c in convs]
+
+
+def dqn_conv_specs(learner_config, env_config):
+    """(input shape (C, H, W), convs, A, hidden sizes, dueling, is_uint8) of
+    build_ffqfunc for a pixel-only obs spec with 1 to 4 conv layers and discrete
+    actions.  model.is_uint8 defaults to True (module docstring)."""
+    lc, ec = learner_config, env_config
+    A = _action_dim(ec)
+    obs = ec['obs_spec']
+    if 'pixel' not in obs:
+        raise ConfigError('dqn_conv_specs takes a pixel obs spec')
+    if 'low_dim' in obs:
+        raise ConfigError('DQN takes a pixel-only obs spec or a low_dim-only one (FFQfunc has one '
+                          'input), got both')
+    if len(obs['pixel']) != 1:
+        raise ConfigError('DQN pixel observations: exactly one camera, got {}'.format(
+            sorted(obs['pixel'])))
+    convs = list(lc['model'].get('convs') or [])
+    if not convs:
+        raise ConfigError('DQN pixel observations need model.convs')
+    shape = tuple(int(v) for v in list(obs['pixel'].values())[0])
+    if len(shape) != 3:
+        raise ConfigError('DQN pixel observations are (C, H, W), got {}'.format(shape))
+    convs = check_convs(convs, shape[0])
+    conv_chain(shape, convs)
+    return (shape, convs, A, _hidden_sizes(lc), bool(lc['model']['dueling']),
+            bool(lc['model'].get('is_uint8', True)))
+
+
+def dqn_model_kwargs(learner_config, env_config):
+    """(D, A, hidden, dueling, FFQfunc keyword arguments): dqn_conv_specs for a
+    spec with pixels, dqn_specs otherwise.  Host only."""
+    if 'pixel' in env_config['obs_spec']:
+        shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
+        D = int(np.prod(conv_chain(shape, convs)[1]))
+        return D, A, hidden, dueling, {'convs': convs, 'input_shape': shape, 'is_uint8': u8}
+    D, A, hidden, dueling = dqn_specs(learner_config, env_config)
+    return D, A, hidden, dueling, {}
+
+
+def ffq_param_names(n_convs, n_hidden, dueling):
+    """state_dict keys in the reference's construction order (q_net.py:25-39,87-98)"""
+    names = [f'conv_layers.{i}.{p}' for i in range(n_convs) for p in ('weight', 'bias')]
+    for stream in ('fc_action_layers', 'fc_state_layers')[:2 if dueling else 1]:
+        names += [f'{stream}.{i}.{p}' for i in range(n_hidden + 1) for p in ('weight', 'bias')]
+    return names
+
+
+class _ConvAt(_LinearView):
+    """weight (cout, cin, k, k) and bias (cout) at `off` of a flat buffer"""
+
+    def __init__(self, flat, off, cin, cout, k):
+        nn.Module.__init__(self)
+        self.in_features, self.out_features = cin * k * k, cout      # fan-in of reset_parameters
+        self.weight = nn.Parameter(flat[off:off + cout * cin * k * k].view(cout, cin, k, k))
+        off += cout * cin * k * k
+        self.bias = nn.Parameter(flat[off:off + cout])
+        self.end = off + cout
 
 
 class FFQfunc(nn.Module):
-    """q_net.py:9-119 for low-dimensional observations over ONE flat fp32
-    buffer (layout: module docstring)."""
+    """q_net.py:9-119 over ONE flat fp32 buffer (layout: module docstring).
+    With convs ([[cout, k, stride]], input_shape (C, H, W)) the input is a
+    uint8 or float32 (rows, C, H, W) device tensor and D_in is ignored."""
 
-    def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None):
+    def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
+                 convs=None, input_shape=None, is_uint8=False):
         super().__init__()
-        L.require_gpu()
-        self.device = torch.device(device) if device is not None else torch.device('cuda')
         hs = [int(h) for h in fc_hidden_sizes]
         if not 1 <= len(hs) <= 3:
             raise ConfigError('FFQfunc takes 1 to 3 hidden widths')
+        self.convs = [[int(v) for v in c] for c in (convs or [])]
+        self.is_uint8 = bool(is_uint8)
+        self.input_shape = None
+        self.conv_geoms = []
+        if self.convs:
+            if input_shape is None or len(tuple(input_shape)) != 3:          # q_net.py:82-83
+                raise ValueError('convs need a 3-D input_shape (C, H, W), got {!r}'.format(input_shape))
+            self.input_shape = tuple(int(v) for v in input_shape)
+            check_convs(self.convs, max(self.input_shape[0], 1))
+            self.conv_geoms, pre = conv_chain(self.input_shape, self.convs)
+            D_in = int(np.prod(pre))
+        L.require_gpu()
+        self.device = torch.device(device) if device is not None else torch.device('cuda')
         self.dims = (int(D_in), tuple(hs), int(action_dim))
         self.dueling = bool(dueling)
         D, A, S = int(D_in), int(action_dim), 2 if dueling else 1
         h1 = hs[0]
         deep = lambda out: sum(hs[k] * hs[k - 1] + hs[k] for k in range(1, len(hs))) + \
             out * hs[-1] + out                                              # noqa: E731
-        n = S * h1 * D + S * h1 + deep(A) + (deep(1) if dueling else 0)
+        fc0 = sum(co * ci * k * k + co for ci, _, _, co, k, _, _ in self.conv_geoms)
+        n = fc0 + S * h1 * D + S * h1 + deep(A) + (deep(1) if dueling else 0)
         flat = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.__dict__['flat'] = flat
-        b1 = S * h1 * D
-        self.__dict__['w1'] = flat[:b1].view(S * h1, D)
+        if self.convs:
+            off, cl = 0, []
+            for ci, _, _, co, k, _, _ in self.conv_geoms:
+                cl.append(_ConvAt(flat, off, ci, co, k))
+                off = cl[-1].end
+            assert off == fc0
+            self.conv_layers = nn.ModuleList(cl)                  # q_net.py:87-98, built first
+            for conv in self.conv_layers:
+                conv.reset_parameters(generator)
+        b1 = fc0 + S * h1 * D
+        self.__dict__['w1'] = flat[fc0:b1].view(S * h1, D)
         self.__dict__['b1'] = flat[b1:b1 + S * h1]
         off = b1 + S * h1
         streams = []
         for s, out in enumerate((A, 1)[:S]):
-            layers = [_LinearAt(flat, s * h1 * D, b1 + s * h1, D, h1)]
+            layers = [_LinearAt(flat, fc0 + s * h1 * D, b1 + s * h1, D, h1)]
             for k in range(1, len(hs)):
                 layers.append(_LinearView(flat, off, hs[k - 1], hs[k]))
                 off = layers[-1].end
@@ -139,13 +300,15 @@ class FFQfunc(nn.Module):
 
     def clone(self):
         D, hs, A = self.dims
-        c = FFQfunc(D, A, hs, self.dueling, self.device)
+        c = FFQfunc(D, A, hs, self.dueling, self.device, convs=self.convs,
+                    input_shape=self.input_shape, is_uint8=self.is_uint8)
         c.copy_from(self)
         return c
 
     def forward(self, x):
-        """q values [rows][A] (q_net.py:41-65) of a float32 device matrix"""
-        x = x if x.stride(-1) == 1 else x.contiguous()
+        """q values [rows][A] (q_net.py:41-65,112-119) of a float32 device matrix
+        (with convs: of a uint8 or float32 (rows, C, H, W) device tensor)"""
+        x = x.contiguous() if self.convs else (x if x.stride(-1) == 1 else x.contiguous())
         adv, val = _QNet(self, {}).fwd(x, x.shape[0], 'f')
         if not self.dueling:
             return adv.clone()
@@ -171,12 +334,59 @@ class _QNet(object):
         L.call('smi_linear_forward', _p(x), ldx, rows, k, _p(w), ldw, _p(b), n, act, _p(y), ldy,
                self.st)
 
+    def conv_fwd(self, x, rows, pre):
+        """the conv stem on (rows, C, H, W) uint8 or float32 frames, read in
+        place; layer i's ReLU output stays in pre_c{i} and the last one, seen
+        as [rows][F], is the feature matrix (U.flatten_conv)"""
+        m = self.m
+        if (x.dim() != 4 or x.shape[0] < rows or tuple(x.shape[1:]) != m.input_shape
+                or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous()):
+            raise ValueError(f'q_func input: expected contiguous uint8 or float32 frames '
+                             f'({rows}, {m.input_shape}), got {x.dtype} {tuple(x.shape)}')
+        for i, (ci, H, W, co, k, s, p) in enumerate(m.conv_geoms):
+            ho, wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+            y = self.buf(f'{pre}_c{i}', (rows, co, ho, wo))
+            conv = m.conv_layers[i]
+            L.call('smi_conv2d_forward', _p(x), int(x.dtype == torch.uint8),
+                   int(i == 0 and m.is_uint8), rows, ci, H, W, _p(conv.weight), _p(conv.bias), co, k,
+                   s, p, RELU, _p(y), self.st)
+            x = y
+        return x.view(rows, -1)
+
+    def conv_bwd(self, x, rows, pre, dH1, g):
+        """from dH1 (both streams' first-layer gradient) through the stem: the
+        first FC layer's input gradient masked by the last conv activation, then
+        per layer the weight gradient and (except layer 0) the input gradient"""
+        m = self.m
+        D, hs, A = m.dims
+        S = 2 if m.dueling else 1
+        n = len(m.conv_geoms)
+        acts = [x] + [self.bufs[f'{pre}_c{i}'] for i in range(n)]
+        need = max(int(L.lib().smi_conv2d_scratch_bytes(rows, *geo)) for geo in m.conv_geoms)
+        scratch = self.buf('conv_scratch', ((need + 3) // 4,))
+        dy = self.buf(f'{pre}_dc{n - 1}', tuple(acts[n].shape))
+        L.call('smi_linear_backward_input', _p(dH1), S * hs[0], rows, S * hs[0], _p(m.w1), D, D,
+               _p(acts[n]), D, _p(dy), D, self.st)
+        for i in range(n - 1, -1, -1):
+            ci, H, W, co, k, s, p = m.conv_geoms[i]
+            conv, xi = m.conv_layers[i], acts[i]
+            L.call('smi_conv2d_backward_weight', _p(dy), _p(xi), int(xi.dtype == torch.uint8),
+                   int(i == 0 and m.is_uint8), rows, ci, H, W, co, k, s, p,
+                   _p(g[m.off(conv.weight):]), _p(g[m.off(conv.bias):]), _p(scratch), need, self.st)
+            if i:
+                dx = self.buf(f'{pre}_dc{i - 1}', tuple(xi.shape))
+                L.call('smi_conv2d_backward_input', _p(dy), rows, ci, H, W, _p(conv.weight), co, k, s,
+                       p, _p(xi), _p(dx), self.st)
+                dy = dx
+
     def fwd(self, x, rows, pre):
         """(ADV [rows][A], VAL [rows][1] | None); the hidden activations stay in
         the buffers pre_h1 ([rows][S h1], both streams) and pre_h{k}_{s}"""
         m = self.m
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
+        if m.convs:
+            x = self.conv_fwd(x, rows, pre)
         if (x.dim() != 2 or x.shape[0] < rows or x.shape[1] != D or x.stride(1) != 1
                 or x.dtype != torch.float32):
             raise ValueError(f'q_func input: expected a float32 [{rows}][{D}] matrix, got '
@@ -207,6 +417,9 @@ class _QNet(object):
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
         st = self.st
+        frames = x
+        if m.convs:
+            x = self.bufs[f'{pre}_c{len(m.convs) - 1}'].view(rows, -1)
         H1 = self.bufs[pre + '_h1']
         dH1 = self.buf(pre + '_dh1', (rows, S * hs[0]))
         for s, layers in enumerate(m.streams()):
@@ -227,7 +440,9 @@ class _QNet(object):
                 dy, ldg = dx, lddx
         # both streams' first layers: one weight-gradient GEMM over dH1 [rows][S h1]
         L.call('smi_linear_backward_weight', _p(dH1), S * hs[0], rows, S * hs[0], _p(x), x.stride(0),
-               D, _p(g), D, _p(g[S * hs[0] * D:]), 0, st)
+               D, _p(g[m.off(m.w1):]), D, _p(g[m.off(m.b1):]), 0, st)
+        if m.convs:
+            self.conv_bwd(frames, rows, pre, dH1, g)
 
 
 class TargetUpdateTracker(object):
@@ -257,8 +472,8 @@ def _column(t, B, what):
 
 
 class DQNLearner(LearnerHooks):
-    """dqn.py:9-126 on MI355X (low-dimensional observations, discrete
-    actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
+    """dqn.py:9-126 on MI355X (low-dimensional observations, or uint8 frames
+    with model.convs; discrete actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
     replay.PrioritizedReplay.sample_batch) weights the Huber loss; after every
     learn() `td_error` is a device view [B] of Q(s, a) - y
     (PrioritizedReplay.update_priorities_from_td)."""
@@ -269,7 +484,7 @@ class DQNLearner(LearnerHooks):
         self.learner_config = lc = learner_config if isinstance(learner_config, Config) \
             else Config(learner_config)
         self.env_config = ec = env_config if isinstance(env_config, Config) else Config(env_config)
-        D, A, hidden, dueling = dqn_specs(lc, ec)
+        D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)
         self.algo = algo = lc.algo
         self.target_update_tracker = TargetUpdateTracker(algo.target_network_update_freq)
         L.require_gpu()
@@ -286,7 +501,8 @@ class DQNLearner(LearnerHooks):
         clip = algo.get('grad_norm_clipping')
         self.max_norm = float(clip) if clip else 0.0          # None or 0: no clip (dqn.py:33-35)
         gen = torch.Generator().manual_seed(seed)
-        self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen)
+        self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
+        self.pixel = bool(conv_kw)
         self.q_target = self.q_func.clone()                   # dqn.py:17
         flat, dev = self.q_func.flat, self.device
         self.opt = {'m': torch.zeros_like(flat), 'v': torch.zeros_like(flat),
@@ -304,6 +520,16 @@ class DQNLearner(LearnerHooks):
     def _update_target(self):                                            # dqn.py:27-28
         self.q_target.copy_from(self.q_func)
 
+    def _obs_of(self, v):
+        """the one input of FFQfunc inside an obs dict: the camera of a pixel
+        model ({'pixel': {'camera0': uint8 (B, C, H, W)}}), low_dim.flat_inputs
+        otherwise; anything else is returned as given"""
+        if not isinstance(v, dict):
+            return v
+        if self.pixel:
+            return list(v['pixel'].values())[0]
+        return v['low_dim']['flat_inputs']
+
     def preprocess(self, batch):
         """host batch (SSARAggregator.aggregate: int32 actions) -> device
         tensors; the action indices become the float32 column the kernel reads.
@@ -314,10 +540,15 @@ class DQNLearner(LearnerHooks):
             raise ValueError(f'actions must be integers in [0, {self.action_dim})')
         out = {}
         for k in ('obs', 'obs_next'):
-            v = batch[k]
-            if isinstance(v, dict):
-                v = v['low_dim']['flat_inputs']
-            out[k] = torch.as_tensor(v, dtype=torch.float32).to(self.device, non_blocking=True)
+            v = self._obs_of(batch[k])
+            if self.pixel:
+                v = torch.as_tensor(v)
+                if v.dtype != torch.uint8 or v.dim() != 4:
+                    raise ValueError(f'{k}: pixel observations are uint8 (B, C, H, W), got '
+                                     f'{v.dtype} {tuple(v.shape)}')
+                out[k] = v.contiguous().to(self.device, non_blocking=True)
+            else:
+                out[k] = torch.as_tensor(v, dtype=torch.float32).to(self.device, non_blocking=True)
         out['actions'] = torch.as_tensor(a.astype(np.float32).reshape(-1, 1)).to(
             self.device, non_blocking=True)
         for k in ('rewards', 'dones'):
@@ -368,9 +599,7 @@ class DQNLearner(LearnerHooks):
         self._ctx.make_current()
         if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
             batch = self.preprocess(batch)
-        obs, obs_next = batch['obs'], batch['obs_next']
-        obs = obs['low_dim']['flat_inputs'] if isinstance(obs, dict) else obs
-        obs_next = obs_next['low_dim']['flat_inputs'] if isinstance(obs_next, dict) else obs_next
+        obs, obs_next = self._obs_of(batch['obs']), self._obs_of(batch['obs_next'])
         actions = batch['actions']
         if actions.dtype != torch.float32:
             actions = actions.to(torch.float32)
@@ -401,8 +630,8 @@ class DQNLearner(LearnerHooks):
             self._graph = None
         if self._graph is None:
             self._optimize(*ins[:5], weights=weights)
-            self._gin = [torch.zeros(tuple(t.shape), dtype=torch.float32, device=self.device)
-                         for t in ins]
+            self._gin = [torch.zeros(tuple(t.shape), dtype=t.dtype, device=self.device)
+                         for t in ins]           # (uint8 frames of a pixel model stay uint8)
             g = torch.cuda.CUDAGraph()
             with L.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
                 self._optimize(*self._gin[:5], weights=self._gin[5] if weights is not None else None)

@@ -8,7 +8,14 @@ weight-gradient flush is two launches, smi_adam_clip with a norm clip three;
 queued weight gradients and smi_dw_group_begin launch nothing).  Prints one
 JSON line per measurement; reads nothing outside the repository.
 
-Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
+--pixel times the Atari-shaped step instead: 4x84x84 uint8 frames, convs
+[[32, 8, 4], [64, 4, 2], [64, 3, 1]], hidden [512], A = 6, at B = 32 and
+B = 512, eager and as a graph replay, and next to each the same step written in
+eager torch on the same GPU (nn.Conv2d through MIOpen, fp32, Adam eps 1e-4,
+clip_grad_norm_ 10): the expectation a pixel learn() is reported against.  When
+the torch step cannot run, that is printed and the project's numbers stand alone.
+
+Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel]
 """
 import argparse
 import copy
@@ -24,7 +31,7 @@ sys.path.insert(0, ROOT)
 from surreal_amd import _lib as L  # noqa: E402
 from surreal_amd import synthetic  # noqa: E402
 from surreal_amd.config import (DDPG_DEFAULT_LEARNER_CONFIG, DQN_DEFAULT_LEARNER_CONFIG,  # noqa: E402
-                                discrete_env_config, gym_env_config)
+                                discrete_env_config, discrete_pixel_env_config, gym_env_config)
 from surreal_amd.ddpg import DDPGLearner  # noqa: E402
 from surreal_amd.dqn import DQNLearner  # noqa: E402
 
@@ -72,11 +79,95 @@ def dqn_batch(B, D, A, seed):
             'weights': (0.3 + 0.7 * torch.rand(B, 1, generator=g)).cuda()}
 
 
+NATURE = [[32, 8, 4], [64, 4, 2], [64, 3, 1]]
+
+
+def pixel_batch(B, shape, A, seed):
+    g = torch.Generator().manual_seed(seed)
+    return {'obs': torch.randint(0, 256, (B,) + shape, generator=g, dtype=torch.uint8).cuda(),
+            'actions': torch.randint(0, A, (B, 1), generator=g).float().cuda(),
+            'rewards': torch.randn(B, 1, generator=g).cuda(),
+            'obs_next': torch.randint(0, 256, (B,) + shape, generator=g, dtype=torch.uint8).cuda(),
+            'dones': (torch.rand(B, 1, generator=g) < 0.05).float().cuda(),
+            'weights': (0.3 + 0.7 * torch.rand(B, 1, generator=g)).cuda()}
+
+
+class TorchQ(torch.nn.Module):
+    """q_net.py:68-119 in plain torch (dueling, is_uint8)"""
+
+    def __init__(self, shape, A, hidden):
+        super().__init__()
+        nn, c, hw = torch.nn, shape[0], shape[1]
+        convs = []
+        for co, k, s in NATURE:
+            convs += [nn.Conv2d(c, co, k, stride=s, padding=k // 2), nn.ReLU()]
+            c, hw = co, (hw + 2 * (k // 2) - k) // s + 1
+        self.stem = nn.Sequential(*convs, nn.Flatten())
+        F = c * hw * hw
+        self.adv = nn.Sequential(nn.Linear(F, hidden), nn.ReLU(), nn.Linear(hidden, A))
+        self.val = nn.Sequential(nn.Linear(F, hidden), nn.ReLU(), nn.Linear(hidden, 1))
+
+    def forward(self, x):
+        f = self.stem(x / 255.0)
+        a = self.adv(f)
+        return a - a.mean(1, keepdim=True) + self.val(f)
+
+
+def torch_step(q, qt, opt, b, gamma=0.99):
+    """dqn.py:42-73 (double-Q, Huber, importance weights, norm clip 10)"""
+    a = b['actions'].long()
+    qa = q(b['obs']).gather(1, a)
+    with torch.no_grad():
+        best = q(b['obs_next']).max(1, keepdim=True)[1]
+        y = b['rewards'] + gamma * (1.0 - b['dones']) * qt(b['obs_next']).gather(1, best)
+    td = qa - y
+    loss = (b['weights'] * torch.where(td.abs() < 1.0, 0.5 * td * td, td.abs() - 0.5)).mean()
+    opt.zero_grad()
+    loss.backward()
+    torch.nn.utils.clip_grad_norm_(q.parameters(), 10)
+    opt.step()
+
+
+def pixel_main(args):
+    shape, A, hidden = (4, 84, 84), 6, 512
+    ec = discrete_pixel_env_config(shape, A)
+    for B in (32, 512):
+        lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+        lc.replay.batch_size = B
+        lc.model.convs, lc.model.fc_hidden_sizes = NATURE, [hidden]
+        b = pixel_batch(B, shape, A, 0)
+        for name, graph in (('dqn_pixel_learn_eager', False), ('dqn_pixel_learn_graph', True)):
+            learner = DQNLearner(lc, ec, seed=0, use_graph=graph)
+            extra = {}
+            if not graph:
+                learner.learn(b)
+                extra['library_calls_per_step'] = count_launches(lambda: learner.learn(b))[1]
+            med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
+            print(json.dumps(dict({'measurement': name, 'B': B, 'median_ms': round(med, 4),
+                                   'q1_ms': round(q1, 4), 'q3_ms': round(q3, 4),
+                                   'iters': args.iters}, **extra)), flush=True)
+            del learner
+        try:
+            torch.manual_seed(0)
+            q, qt = TorchQ(shape, A, hidden).cuda(), TorchQ(shape, A, hidden).cuda()
+            opt = torch.optim.Adam(q.parameters(), lr=1e-3, eps=1e-4)
+            med, q1, q3 = timed(lambda: torch_step(q, qt, opt, b), args.iters, args.warmup)
+            print(json.dumps({'measurement': 'torch_eager_pixel_step', 'B': B,
+                              'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                              'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+        except RuntimeError as e:
+            print(json.dumps({'measurement': 'torch_eager_pixel_step', 'B': B,
+                              'not_measured': str(e).splitlines()[0][:200]}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=10)
+    ap.add_argument('--pixel', action='store_true')
     args = ap.parse_args()
+    if args.pixel:
+        return pixel_main(args)
     B, D, A = 512, 17, 6
     lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
     lc.replay.batch_size = B
