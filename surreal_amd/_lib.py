@@ -351,6 +351,21 @@ def gc_paused():
             gc.enable()
 
 
+class dw_group(object):
+    """with dw_group(stream): the weight-gradient GEMMs issued inside queue into
+    one grouped launch (smi_dw_group_*); leaving always flushes, so nothing
+    stays queued.  (A class, not a generator: it sits on the eager hot path.)"""
+
+    def __init__(self, stream):
+        self.stream = stream
+
+    def __enter__(self):
+        call('smi_dw_group_begin')
+
+    def __exit__(self, *exc):
+        call('smi_dw_group_flush', self.stream)
+
+
 def require_gpu():
     if not torch.cuda.is_available():
         raise RuntimeError('surreal_amd requires an AMD GPU (HIP); none is visible and there is '

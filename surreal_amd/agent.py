@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .config import Config
+from .device_learner import as_config
 from .model import PPOModel
 
 
@@ -37,8 +37,7 @@ class PPOAgentBatch(object):
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None,
                  seed=0):
         L.require_gpu()
-        lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
-        ec = env_config if isinstance(env_config, Config) else Config(env_config)
+        lc, ec = as_config(learner_config), as_config(env_config)
         self.n = int(n_agents)
         self.agent_mode = agent_mode
         self.action_dim = ec.action_spec['dim'][0]
@@ -135,8 +134,7 @@ class DDPGAgentBatch(object):
         for a single agent, else max_sigma * id / num_agents)."""
         from .ddpg import DDPGModel
         L.require_gpu()
-        lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
-        ec = env_config if isinstance(env_config, Config) else Config(env_config)
+        lc, ec = as_config(learner_config), as_config(env_config)
         self.n = int(n_agents)
         self.agent_mode = agent_mode
         self.action_dim = ec.action_spec['dim'][0]
@@ -348,8 +346,7 @@ class QAgentBatch(object):
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
         from .config import ConfigError
         from .dqn import FFQfunc, dqn_model_kwargs
-        lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
-        ec = env_config if isinstance(env_config, Config) else Config(env_config)
+        lc, ec = as_config(learner_config), as_config(env_config)
         D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)
         ex = lc.algo.exploration
         if str(ex.schedule).lower() != 'linear':

@@ -29,8 +29,8 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .session import LearnerHooks
 from .config import Config, ConfigError
+from .device_learner import DeviceLearner, LaunchNet, p
 from .model import CNNStemNetwork, _FlatViews, _LinearView
 
 RELU, TANH, NONE = 1, 2, 0
@@ -183,45 +183,20 @@ class DDPGModel(nn.Module):
         return action, value
 
 
-def _p(t):
-    return L.ptr(t)
-
-
-def _check_rows(x, rows, width, what):
-    """x must be a [>= rows][width] fp32 device matrix with unit column stride
-    (the kernels read rows x width through its row stride)"""
-    if (x.dim() != 2 or x.shape[0] < rows or x.shape[1] != width or x.stride(1) != 1
-            or x.dtype != torch.float32):
-        raise ValueError(f'{what} input: expected a float32 [{rows}][{width}] matrix, got '
-                         f'{x.dtype} {tuple(x.shape)}')
-
-
-class _Net(object):
+class _Net(LaunchNet):
     """Launch helpers over a DDPGModel's flat buffers."""
 
     def __init__(self, model, bufs=None):
+        super().__init__(model.device, bufs if bufs is not None else {})
         self.m = model
-        self.st = L.stream(model.device)
-        self.bufs = bufs if bufs is not None else {}
-
-    def buf(self, name, shape):
-        t = self.bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.zeros(shape, dtype=torch.float32, device=self.m.device)
-            self.bufs[name] = t
-        return t
-
-    def lin(self, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
-        L.call('smi_linear_forward', _p(x), ldx, rows, k, _p(w), ldw, _p(b), n, act, _p(y), ldy,
-               self.st)
 
     def norm(self, net, j, x, rows, y, ldy, tag):
         """LayerNorm block j over x [rows][n] (post-ReLU) into y; mean / rstd kept
         under tag for the backward"""
         ln = net.norms[j]
         mu, rs = self.buf(tag + '_mu', (rows,)), self.buf(tag + '_rs', (rows,))
-        L.call('smi_layernorm_forward', _p(x), x.stride(0), rows, ln.n, _p(ln.weight), _p(ln.bias),
-               1e-5, _p(y), ldy, _p(mu), _p(rs), self.st)
+        L.call('smi_layernorm_forward', p(x), x.stride(0), rows, ln.n, p(ln.weight), p(ln.bias),
+               1e-5, p(y), ldy, p(mu), p(rs), self.st)
 
     def norm_bwd(self, net, j, dy, x, rows, dx, g, tag):
         """backward of LayerNorm block j (and of the ReLU before it) from dy;
@@ -231,9 +206,9 @@ class _Net(object):
             dg, db = self.buf('ln_dg', (ln.n,)), self.buf('ln_db', (ln.n,))
         else:
             dg, db = g[net.off(ln.weight):], g[net.off(ln.bias):]
-        L.call('smi_layernorm_backward', _p(dy), dy.stride(0), _p(x), x.stride(0),
-               _p(self.bufs[tag + '_mu']), _p(self.bufs[tag + '_rs']), _p(ln.weight), rows, ln.n, 1,
-               _p(dx), dx.stride(0), _p(dg), _p(db), self.st)
+        L.call('smi_layernorm_backward', p(dy), dy.stride(0), p(x), x.stride(0),
+               p(self.bufs[tag + '_mu']), p(self.bufs[tag + '_rs']), p(ln.weight), rows, ln.n, 1,
+               p(dx), dx.stride(0), p(dg), p(db), self.st)
 
     def perception_fwd(self, model, pix, low, rows, store, keep=False):
         """[cnn(pix / 255) | low] (ddpg_net.py:69-79) into buffer store_P; keep:
@@ -247,10 +222,10 @@ class _Net(object):
         A2 = self.buf(pre + '_A2', (rows, cnn.flat_dim))
         if pix.dtype != torch.uint8:
             raise TypeError('DDPG camera observations must be uint8 (scaled by 1/255 in the kernel)')
-        L.call('smi_cnn_forward', _p(cnn.flat), _p(pix), None, rows, 1, rows, C, H, W, F,
-               _p(A1) if A1 is not None else None, _p(A2), _p(P), F + D, self.st)
+        L.call('smi_cnn_forward', p(cnn.flat), p(pix), None, rows, 1, rows, C, H, W, F,
+               p(A1) if A1 is not None else None, p(A2), p(P), F + D, self.st)
         if D:
-            L.call('smi_copy_cols', _p(low), low.stride(0), rows, D, _p(P[:, F:]), F + D, self.st)
+            L.call('smi_copy_cols', p(low), low.stride(0), rows, D, p(P[:, F:]), F + D, self.st)
         return P
 
     def perception_bwd(self, model, pix, rows, store, dH1, wo, ldwo, c1, grad):
@@ -261,18 +236,18 @@ class _Net(object):
         F, D = model.cnn_dim, model.low_dim
         P = self.bufs[store + '_P']
         dF = self.buf(store + '_dF', (rows, F))
-        L.call('smi_linear_backward_input', _p(dH1), c1, rows, c1, _p(wo), ldwo, F, _p(P), F + D,
-               _p(dF), F, self.st)
+        L.call('smi_linear_backward_input', p(dH1), c1, rows, c1, p(wo), ldwo, F, p(P), F + D,
+               p(dF), F, self.st)
         nb = int(L.lib().smi_cnn_scratch_bytes(rows, C, H, W, F))
         scratch = self.buf('cnn_scratch', ((nb + 3) // 4,))
-        L.call('smi_cnn_backward', _p(cnn.flat), _p(pix), None, rows, 1, rows, C, H, W, F,
-               _p(self.bufs[store + '_A1']), _p(self.bufs[store + '_A2']), _p(dF), F, _p(grad),
-               _p(scratch), nb, self.st)
+        L.call('smi_cnn_backward', p(cnn.flat), p(pix), None, rows, 1, rows, C, H, W, F,
+               p(self.bufs[store + '_A1']), p(self.bufs[store + '_A2']), p(dF), F, p(grad),
+               p(scratch), nb, self.st)
 
     def actor_fwd(self, obs, rows, store='a', actor=None):
         actor = actor if actor is not None else self.m.actor
         D, h1, h2, A = actor.dims
-        _check_rows(obs, rows, D, 'actor')
+        self.check_rows(obs, rows, D, 'actor')
         pre = store or 'tmp'
         H1 = self.buf(pre + '_h1', (rows, h1))
         H2 = self.buf(pre + '_h2', (rows, h2))
@@ -293,8 +268,8 @@ class _Net(object):
 
     def critic_fwd(self, critic, obs, act, rows, store):
         D, c1, c2, A = critic.dims
-        _check_rows(obs, rows, D, 'critic')
-        _check_rows(act, rows, A, 'critic action')
+        self.check_rows(obs, rows, D, 'critic')
+        self.check_rows(act, rows, A, 'critic action')
         pre = store or 'ctmp'
         CAT = self.buf(pre + '_cat', (rows, c1 + A))
         H2 = self.buf(pre + '_h2', (rows, c2))
@@ -304,11 +279,11 @@ class _Net(object):
             H1 = self.buf(pre + '_h1', (rows, c1))
             self.lin(obs, obs.stride(0), rows, D, wo, D, bo, c1, RELU, H1, c1)
             self.norm(critic, 0, H1, rows, CAT, c1 + A, pre + '_ln1')
-            L.call('smi_copy_cols', _p(act), act.stride(0), rows, A, _p(CAT[:, c1:]), c1 + A,
+            L.call('smi_copy_cols', p(act), act.stride(0), rows, A, p(CAT[:, c1:]), c1 + A,
                    self.st)
         else:   # relu(obs W^T + b) and the action block of the concat in one launch
-            L.call('smi_linear_forward_cat', _p(obs), obs.stride(0), rows, D, _p(wo), D, _p(bo), c1,
-                   RELU, _p(CAT), c1 + A, _p(act), act.stride(0), A, self.st)
+            L.call('smi_linear_forward_cat', p(obs), obs.stride(0), rows, D, p(wo), D, p(bo), c1,
+                   RELU, p(CAT), c1 + A, p(act), act.stride(0), A, self.st)
         self.lin(CAT, c1 + A, rows, c1 + A, wc, c1 + A, bc, c2, RELU, H2, c2)
         X2 = H2
         if critic.use_layernorm:
@@ -318,7 +293,7 @@ class _Net(object):
         return Q if store else Q.clone()
 
 
-class DDPGLearner(LearnerHooks):
+class DDPGLearner(DeviceLearner):
     """ddpg.py:12-440 on MI355X (low-dim or pixel observations; optional
     layernorm, TD3 options).  A batch with a 'weights' entry (float32 [B, 1],
     replay.PrioritizedReplay.sample_batch) weights both critics' loss; after
@@ -339,18 +314,9 @@ class DDPGLearner(LearnerHooks):
         metrics / checkpoint: as PPOLearner's (session.py): learn() reports the
         statistics and calls periodic_checkpoint(global_steps=
         current_iteration) as ddpg.py:371-376 does."""
-        L.require_gpu()
-        self.checkpoint_full_state = bool(checkpoint_full_state)
+        lc, ec = self._init_device(learner_config, env_config, session_config, metrics, checkpoint,
+                                   device, checkpoint_full_state)
         self.dp = dp if dp is not None and dp.world_size > 1 else None
-        self.learner_config = lc = learner_config if isinstance(learner_config, Config) else Config(learner_config)
-        self.env_config = ec = env_config if isinstance(env_config, Config) else Config(env_config)
-        self.session_config = session_config
-        self._init_hooks(metrics, checkpoint)
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        L.ensure_workspace(self.device)
-        self._ctx = L.Context(self.device)      # this learner's own workspace (re-entrancy)
-        self.current_iteration = 0
         self.batch_size = lc.replay.batch_size
         self.discount_factor = lc.algo.gamma
         self.n_step = lc.algo.n_step
@@ -431,19 +397,13 @@ class DDPGLearner(LearnerHooks):
                  'critic2': self._critic_pack[nc + nq:2 * nc + nq],
                  'critic2_cnn': self._critic_pack[2 * nc + nq:], 'actor': self._actor_pack[:na]}
         for name, flat, lr, wd in groups:
-            self.opt[name] = {'m': torch.zeros_like(flat), 'v': torch.zeros_like(flat),
-                              'step': torch.zeros(1, dtype=torch.int32, device=dev),
-                              'lr': torch.tensor([lr], dtype=torch.float32, device=dev),
-                              'wd': float(wd), 'g': packs[name]}
+            self.opt[name] = self.adam_state(flat, lr, packs[name], wd)
         self.stats_buf = self._actor_pack[na:]
-        self._bufs = {}
         self.kernel_events = None
-        # hipGraph replay of the update (learn() -> _optimize_graphed); the TD3
+        # hipGraph replay of the update (_learn_device -> _graph_step); the TD3
         # smoothing noise is a fresh host draw per step, so that option stays eager
         self.use_graph = bool(use_graph) and self.dp is None and not (
             self.use_double_critic and self.use_action_regularization)
-        self._graph = None
-        self._gin = None
 
     # ------------------------------------------------------------ helpers
     def _target_pairs(self, perception=True):
@@ -470,10 +430,7 @@ class DDPGLearner(LearnerHooks):
             t.mul_(1.0 / self.dp.world_size)
 
     def _adam(self, name, flat, clip_value, st):
-        o = self.opt[name]
-        L.call('smi_adam_clip', _p(flat), _p(o['g']), _p(o['m']), _p(o['v']), flat.numel(),
-               _p(o['step']), _p(o['lr']), 0.9, 0.999, 1e-8, o['wd'], 0.0, float(clip_value),
-               None, None, st)
+        self.adam_step(self.opt[name], flat, 1e-8, 0.0, clip_value, st)
 
     def preprocess(self, batch):                                         # ddpg.py:186-242
         """numpy -> device tensors; camera frames stay uint8 (the reference's
@@ -502,7 +459,7 @@ class DDPGLearner(LearnerHooks):
 
     # --------------------------------------------------------- _optimize
     def _optimize(self, obs, actions, rewards, obs_next, done,           # ddpg.py:244-352
-                  target_update=True, weights=None):
+                  weights=None, target_update=True):
         """weights (float32 [B] or [B, 1], contiguous; a prioritized replay's
         importance-sampling weights): both critics' loss becomes mean(w (Q -
         y)^2); the actor loss stays unweighted.  The first critic's Q - y
@@ -556,18 +513,19 @@ class DDPGLearner(LearnerHooks):
         y = net.buf('y', (B, 1))
         r1 = rewards if rewards.is_contiguous() else rewards.contiguous()
         d1 = done if done.is_contiguous() else done.contiguous()
-        L.call('smi_ddpg_target', _p(r1), _p(d1), _p(q_t), _p(q_t2) if q_t2 is not None else None,
-               B, float(pow(self.discount_factor, self.n_step)), _p(y), st)
+        L.call('smi_ddpg_target', p(r1), p(d1), p(q_t), p(q_t2) if q_t2 is not None else None,
+               B, float(pow(self.discount_factor, self.n_step)), p(y), st)
         # critic update (ddpg.py:287-310)
         crit = self.model.critic
         q = net.critic_fwd(crit, obs, actions, B, store='c')
         dq = net.buf('dq', (B, 1))
         self.td_error = net.buf('td', (B,))
-        L.call('smi_mse_grad_weighted', _p(q), 1, _p(y), _p(weights), B, _p(dq),
-               _p(self.stats_buf[1:2]), _p(self.td_error), st)
+        L.call('smi_mse_grad_weighted', p(q), 1, p(y), p(weights), B, p(dq),
+               p(self.stats_buf[1:2]), p(self.td_error), st)
         g = self.opt['critic']['g']
         cnn = (self.model, pix, 'cp', self.opt['critic_cnn']['g']) if self.is_pixel_input else None
-        self._critic_backward(net, crit, obs, B, dq, 'c', g, st, need_obs_grad=True, cnn=cnn)
+        with L.dw_group(st):
+            self._critic_backward(net, crit, obs, B, dq, 'c', g, st, need_obs_grad=True, cnn=cnn)
         cclip = self.critic_gradient_clip_value if self.clip_critic_gradient else 0.0
         if self.use_double_critic:                      # second critic (ddpg.py:312-320)
             # its gradient does not depend on the first critic's step: both are
@@ -576,15 +534,16 @@ class DDPGLearner(LearnerHooks):
             q_2 = net.critic_fwd(crit2, obs2, actions, B, store='q2c')
             dq_2 = net.buf('dq_2', (B, 1))
             # the reference reports this critic's loss as 'critic_loss'
-            L.call('smi_mse_grad_weighted', _p(q_2), 1, _p(y), _p(weights), B, _p(dq_2),
-                   _p(self.stats_buf[1:2]), None, st)
+            L.call('smi_mse_grad_weighted', p(q_2), 1, p(y), p(weights), B, p(dq_2),
+                   p(self.stats_buf[1:2]), None, st)
             cnn2 = (self.model2, pix, 'q2p', self.opt['critic2_cnn']['g']) if self.is_pixel_input \
                 else None
-            self._critic_backward(net, crit2, obs2, B, dq_2, 'q2c', self.opt['critic2']['g'], st,
-                                  need_obs_grad=True, cnn=cnn2)
-            L.call('smi_ddpg_stats', _p(actions), actions.stride(0), self.action_dim, _p(rewards),
-                   rewards.stride(0) if rewards.dim() == 2 else 1, _p(y), _p(q_2), 1, B,
-                   _p(self.stats_buf[8:12]), st)         # [.., .., .., Q_policy2]
+            with L.dw_group(st):
+                self._critic_backward(net, crit2, obs2, B, dq_2, 'q2c', self.opt['critic2']['g'], st,
+                                      need_obs_grad=True, cnn=cnn2)
+            L.call('smi_ddpg_stats', p(actions), actions.stride(0), self.action_dim, p(rewards),
+                   rewards.stride(0) if rewards.dim() == 2 else 1, p(y), p(q_2), 1, B,
+                   p(self.stats_buf[8:12]), st)         # [.., .., .., Q_policy2]
         self._dp_mean_(self._critic_pack)
         self._adam('critic', crit.flat, cclip, st)
         if self.is_pixel_input:         # the perception: critic optimizer, no value clip
@@ -598,13 +557,14 @@ class DDPGLearner(LearnerHooks):
         a = net.actor_fwd(obs, B, store='a')
         q2 = net.critic_fwd(crit, obs, a, B, store='c2')
         dq2 = net.buf('dq2', (B, 1))
-        L.call('smi_neg_mean_grad', _p(q2), 1, B, _p(dq2), _p(self.stats_buf[0:1]), st)
+        L.call('smi_neg_mean_grad', p(q2), 1, B, p(dq2), p(self.stats_buf[0:1]), st)
         dA = self._critic_backward(net, crit, obs, B, dq2, 'c2', None, st, need_obs_grad=False)
-        self._actor_backward(net, act, obs, B, dA, self.opt['actor']['g'], st)
+        with L.dw_group(st):
+            self._actor_backward(net, act, obs, B, dA, self.opt['actor']['g'], st)
         # statistics (ddpg.py:335-345); shard means -> global means together with
         # the actor gradient (one exchange)
-        L.call('smi_ddpg_stats', _p(actions), actions.stride(0), A, _p(rewards), rs, _p(y), _p(q), 1,
-               B, _p(self.stats_buf[2:6]), st)
+        L.call('smi_ddpg_stats', p(actions), actions.stride(0), A, p(rewards), rs, p(y), p(q), 1,
+               B, p(self.stats_buf[2:6]), st)
         self._dp_mean_(self._actor_pack)
         self._adam('actor', act.flat,
                    self.actor_gradient_clip_value if self.clip_actor_gradient else 0.0, st)
@@ -613,19 +573,10 @@ class DDPGLearner(LearnerHooks):
 
     def _critic_backward(self, net, crit, obs, B, dq, pre, g, st, need_obs_grad, cnn=None):
         """Backward through CriticNetworkX.  With g: weight grads into g (flat),
-        the three weight-gradient GEMMs as one grouped launch (smi_dw_group_*);
-        cnn = (model, pixels, perception store, gradient) continues through the
-        model's perception (pixel inputs).  Always returns d loss / d action
-        (B, A) when g is None."""
-        if g is None:
-            return self._critic_backward_body(net, crit, obs, B, dq, pre, g, st, cnn)
-        L.call('smi_dw_group_begin')
-        try:
-            return self._critic_backward_body(net, crit, obs, B, dq, pre, g, st, cnn)
-        finally:
-            L.call('smi_dw_group_flush', st)   # always flush: nothing stays queued
-
-    def _critic_backward_body(self, net, crit, obs, B, dq, pre, g, st, cnn=None):
+        the three weight-gradient GEMMs queued into the caller's open group
+        (L.dw_group: one grouped launch); cnn = (model, pixels, perception
+        store, gradient) continues through the model's perception (pixel
+        inputs).  Always returns d loss / d action (B, A) when g is None."""
         D, c1, c2, A = crit.dims
         ln = crit.use_layernorm
         CAT = net.bufs[pre + '_cat']
@@ -635,47 +586,40 @@ class DDPGLearner(LearnerHooks):
         dH2 = net.buf('dH2', (B, c2))
         if ln:      # d/d(norm output), then through the norm and the ReLU
             dN2 = net.buf('dN2', (B, c2))
-            L.call('smi_linear_backward_input', _p(dq), 1, B, 1, _p(wq), c2, c2, None, 0, _p(dN2),
+            L.call('smi_linear_backward_input', p(dq), 1, B, 1, p(wq), c2, c2, None, 0, p(dN2),
                    c2, st)
             net.norm_bwd(crit, 1, dN2, H2, B, dH2, g, pre + '_ln2')
         else:
-            L.call('smi_linear_backward_input', _p(dq), 1, B, 1, _p(wq), c2, c2, _p(H2), c2,
-                   _p(dH2), c2, st)
+            L.call('smi_linear_backward_input', p(dq), 1, B, 1, p(wq), c2, c2, p(H2), c2,
+                   p(dH2), c2, st)
         if g is not None:
-            L.call('smi_linear_backward_weight', _p(dq), 1, B, 1, _p(X2), c2, c2,
-                   _p(g[crit.off(wq):]), c2, _p(g[crit.off(bq):]), 0, st)
-            L.call('smi_linear_backward_weight', _p(dH2), c2, B, c2, _p(CAT), c1 + A, c1 + A,
-                   _p(g[crit.off(wc):]), c1 + A, _p(g[crit.off(bc):]), 0, st)
+            L.call('smi_linear_backward_weight', p(dq), 1, B, 1, p(X2), c2, c2,
+                   p(g[crit.off(wq):]), c2, p(g[crit.off(bq):]), 0, st)
+            L.call('smi_linear_backward_weight', p(dH2), c2, B, c2, p(CAT), c1 + A, c1 + A,
+                   p(g[crit.off(wc):]), c1 + A, p(g[crit.off(bc):]), 0, st)
             dH1 = net.buf('dH1c', (B, c1))
             if ln:
                 dN1 = net.buf('dN1c', (B, c1))
-                L.call('smi_linear_backward_input', _p(dH2), c2, B, c2, _p(wc), c1 + A, c1, None, 0,
-                       _p(dN1), c1, st)
+                L.call('smi_linear_backward_input', p(dH2), c2, B, c2, p(wc), c1 + A, c1, None, 0,
+                       p(dN1), c1, st)
                 net.norm_bwd(crit, 0, dN1, net.bufs[pre + '_h1'], B, dH1, g, pre + '_ln1')
             else:
-                L.call('smi_linear_backward_input', _p(dH2), c2, B, c2, _p(wc), c1 + A, c1, _p(CAT),
-                       c1 + A, _p(dH1), c1, st)
-            L.call('smi_linear_backward_weight', _p(dH1), c1, B, c1, _p(obs), obs.stride(0), D,
-                   _p(g[crit.off(wo):]), D, _p(g[crit.off(bo):]), 0, st)
+                L.call('smi_linear_backward_input', p(dH2), c2, B, c2, p(wc), c1 + A, c1, p(CAT),
+                       c1 + A, p(dH1), c1, st)
+            L.call('smi_linear_backward_weight', p(dH1), c1, B, c1, p(obs), obs.stride(0), D,
+                   p(g[crit.off(wo):]), D, p(g[crit.off(bo):]), 0, st)
             if cnn is not None:
                 model, pix, store, gc = cnn
                 net.perception_bwd(model, pix, B, store, dH1, wo, D, c1, gc)
             return None
         dA = net.buf('dA', (B, A))
-        L.call('smi_linear_backward_input', _p(dH2), c2, B, c2, _p(wc[:, c1:]), c1 + A, A, None, 0,
-               _p(dA), A, st)
+        L.call('smi_linear_backward_input', p(dH2), c2, B, c2, p(wc[:, c1:]), c1 + A, A, None, 0,
+               p(dA), A, st)
         return dA
 
     def _actor_backward(self, net, act, obs, B, dA, g, st):
         """Backward through ActorNetworkX into g; its three weight-gradient
-        GEMMs as one grouped launch (smi_dw_group_*)."""
-        L.call('smi_dw_group_begin')
-        try:
-            self._actor_backward_body(net, act, obs, B, dA, g, st)
-        finally:
-            L.call('smi_dw_group_flush', st)
-
-    def _actor_backward_body(self, net, act, obs, B, dA, g, st):
+        GEMMs queue into the caller's open group (L.dw_group)."""
         D, h1, h2, A = act.dims
         ln = act.use_layernorm
         H1, H2, out = net.bufs['a_h1'], net.bufs['a_h2'], net.bufs['a_act']
@@ -683,104 +627,61 @@ class DDPGLearner(LearnerHooks):
         X2 = net.bufs['a_n2'] if ln else H2
         (w1, b1), (w2, b2), (w3, b3) = act.wb(0), act.wb(1), act.wb(2)
         dZ = net.buf('dZ3', (B, A))
-        L.call('smi_tanh_backward', _p(dA), A, _p(out), A, B, A, _p(dZ), A, st)
-        L.call('smi_linear_backward_weight', _p(dZ), A, B, A, _p(X2), h2, h2, _p(g[act.off(w3):]), h2,
-               _p(g[act.off(b3):]), 0, st)
+        L.call('smi_tanh_backward', p(dA), A, p(out), A, B, A, p(dZ), A, st)
+        L.call('smi_linear_backward_weight', p(dZ), A, B, A, p(X2), h2, h2, p(g[act.off(w3):]), h2,
+               p(g[act.off(b3):]), 0, st)
         dH2 = net.buf('dH2a', (B, h2))
         if ln:
             dN2 = net.buf('dN2a', (B, h2))
-            L.call('smi_linear_backward_input', _p(dZ), A, B, A, _p(w3), h2, h2, None, 0, _p(dN2), h2,
+            L.call('smi_linear_backward_input', p(dZ), A, B, A, p(w3), h2, h2, None, 0, p(dN2), h2,
                    st)
             net.norm_bwd(act, 1, dN2, H2, B, dH2, g, 'a_ln2')
         else:
-            L.call('smi_linear_backward_input', _p(dZ), A, B, A, _p(w3), h2, h2, _p(H2), h2, _p(dH2),
+            L.call('smi_linear_backward_input', p(dZ), A, B, A, p(w3), h2, h2, p(H2), h2, p(dH2),
                    h2, st)
-        L.call('smi_linear_backward_weight', _p(dH2), h2, B, h2, _p(X1), h1, h1, _p(g[act.off(w2):]), h1,
-               _p(g[act.off(b2):]), 0, st)
+        L.call('smi_linear_backward_weight', p(dH2), h2, B, h2, p(X1), h1, h1, p(g[act.off(w2):]), h1,
+               p(g[act.off(b2):]), 0, st)
         dH1 = net.buf('dH1a', (B, h1))
         if ln:
             dN1 = net.buf('dN1a', (B, h1))
-            L.call('smi_linear_backward_input', _p(dH2), h2, B, h2, _p(w2), h1, h1, None, 0, _p(dN1),
+            L.call('smi_linear_backward_input', p(dH2), h2, B, h2, p(w2), h1, h1, None, 0, p(dN1),
                    h1, st)
             net.norm_bwd(act, 0, dN1, H1, B, dH1, g, 'a_ln1')
         else:
-            L.call('smi_linear_backward_input', _p(dH2), h2, B, h2, _p(w2), h1, h1, _p(H1), h1,
-                   _p(dH1), h1, st)
-        L.call('smi_linear_backward_weight', _p(dH1), h1, B, h1, _p(obs), obs.stride(0), D,
-               _p(g[act.off(w1):]), D, _p(g[act.off(b1):]), 0, st)
+            L.call('smi_linear_backward_input', p(dH2), h2, B, h2, p(w2), h1, h1, p(H1), h1,
+                   p(dH1), h1, st)
+        L.call('smi_linear_backward_weight', p(dH1), h1, B, h1, p(obs), obs.stride(0), D,
+               p(g[act.off(w1):]), D, p(g[act.off(b1):]), 0, st)
 
     def _target_update(self):                                            # ddpg.py:403-428
         st = L.stream(self.device)
         if self.target_update_type == 'soft':
             for t, s in self._target_pairs():
-                L.call('smi_soft_update', _p(t), _p(s), t.numel(), float(self.target_update_tau), st)
+                L.call('smi_soft_update', p(t), p(s), t.numel(), float(self.target_update_tau), st)
         else:
             self.target_update_counter += 1
             if self.target_update_counter % self.target_update_interval == 0:
                 self._hard_update()
 
     # ------------------------------------------------------- reference API
-    def learn(self, batch):                                              # ddpg.py:354-376
-        self.current_iteration += 1
-        self._ctx.make_current()
-        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
-            batch = self.preprocess(batch)
+    def _learn_device(self, batch):                                      # ddpg.py:354-376
         obs, obs_next = batch['obs'], batch['obs_next']
         if not self.is_pixel_input:
             obs = obs['low_dim']['flat_inputs'] if isinstance(obs, dict) else obs
             obs_next = obs_next['low_dim']['flat_inputs'] if isinstance(obs_next, dict) else obs_next
         ins = (obs, batch['actions'], batch['rewards'], obs_next, batch['dones'])
         weights = batch.get('weights')
-        if self.use_graph and not self.is_pixel_input:
-            self._optimize_graphed(*ins, weights=weights)
-        else:
+        if self.is_pixel_input or not self.use_graph:
             self._optimize(*ins, weights=weights)
-        self._report_metrics(self.current_iteration)                     # ddpg.py:371
-        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
-
-    def _optimize_graphed(self, obs, actions, rewards, obs_next, done, weights=None):
-        """One _optimize as a hipGraph replay (the step is ~40 small launches at
-        batch 512, so host launch overhead, not the GPU, bounds it).  The first
-        call runs eagerly (it is that call's update, and it sizes every scratch
-        buffer), then captures the same launch sequence over static input
-        buffers; later calls copy their inputs in (skipped when the caller
-        already wrote them: graph_inputs()) and replay.  The target update stays
-        on the host, where its interval counter lives (ddpg.py:403-428).
-        Importance-sampling weights are one more static input; a graph captured
-        without them is not reused with them (nor the other way round): the
-        step is captured again."""
-        ins = (obs, actions, rewards, obs_next, done)
-        if weights is not None:
-            ins = ins + (weights,)
-        if self._graph is not None and len(self._gin) != len(ins):
-            self._graph = None
-        if self._graph is None:
-            self._optimize(*ins[:5], weights=weights)
-            self._gin = [torch.zeros(tuple(t.shape), dtype=torch.float32, device=self.device)
-                         for t in ins]
-            g = torch.cuda.CUDAGraph()
-            with L.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._optimize(*self._gin[:5], target_update=False,
-                               weights=self._gin[5] if weights is not None else None)
-            self._graph = g
             return
-        for s, t in zip(self._gin, ins):
-            if s.data_ptr() != t.data_ptr():
-                s.copy_(t)
-        self._graph.replay()
-        self._target_update()
-
-    def graph_inputs(self):
-        """Static (obs, actions, rewards, obs_next, dones) buffers of the captured
-        step (None before the first learn() in graph mode)."""
-        return None if self._gin is None else dict(zip(
-            ('obs', 'actions', 'rewards', 'obs_next', 'dones', 'weights'), self._gin))
-
-    def _host_scalars(self):
-        return {}
-
-    def last_stats(self):
-        return self._stats_dict(self.stats_buf.cpu().numpy(), {})
+        # the target update stays on the host, where its interval counter lives
+        # (ddpg.py:403-428): the eager first call makes it, the capture leaves it
+        # out and every replay is followed by it.  Importance-sampling weights
+        # are one more static input
+        self._graph_step(
+            ins if weights is None else ins + (weights,),
+            lambda *a: self._optimize(*a, target_update=not torch.cuda.is_current_stream_capturing()),
+            after=self._target_update)
 
     def _stats_dict(self, v, host):
         out = {'actor_loss': float(v[0]), 'critic_loss': float(v[1]), 'action_norm': float(v[2]),

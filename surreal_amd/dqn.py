@@ -65,15 +65,11 @@ import torch
 import torch.nn as nn
 
 from . import _lib as L
-from .session import LearnerHooks
 from .config import Config, ConfigError
+from .device_learner import DeviceLearner, LaunchNet, as_config, p
 from .model import _LinearView
 
 RELU, NONE = 1, 0
-
-
-def _p(t):
-    return L.ptr(t)
 
 
 class _LinearAt(_LinearView):
@@ -315,24 +311,12 @@ class FFQfunc(nn.Module):
         return (adv - adv.mean(dim=1, keepdim=True)) + val
 
 
-class _QNet(object):
+class _QNet(LaunchNet):
     """Launch helpers over an FFQfunc's flat buffer."""
 
     def __init__(self, model, bufs):
+        super().__init__(model.device, bufs)
         self.m = model
-        self.st = L.stream(model.device)
-        self.bufs = bufs
-
-    def buf(self, name, shape):
-        t = self.bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.zeros(shape, dtype=torch.float32, device=self.m.device)
-            self.bufs[name] = t
-        return t
-
-    def lin(self, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
-        L.call('smi_linear_forward', _p(x), ldx, rows, k, _p(w), ldw, _p(b), n, act, _p(y), ldy,
-               self.st)
 
     def conv_fwd(self, x, rows, pre):
         """the conv stem on (rows, C, H, W) uint8 or float32 frames, read in
@@ -343,13 +327,13 @@ class _QNet(object):
                 or x.dtype not in (torch.uint8, torch.float32) or not x.is_contiguous()):
             raise ValueError(f'q_func input: expected contiguous uint8 or float32 frames '
                              f'({rows}, {m.input_shape}), got {x.dtype} {tuple(x.shape)}')
-        for i, (ci, H, W, co, k, s, p) in enumerate(m.conv_geoms):
-            ho, wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        for i, (ci, H, W, co, k, s, pad) in enumerate(m.conv_geoms):
+            ho, wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
             y = self.buf(f'{pre}_c{i}', (rows, co, ho, wo))
             conv = m.conv_layers[i]
-            L.call('smi_conv2d_forward', _p(x), int(x.dtype == torch.uint8),
-                   int(i == 0 and m.is_uint8), rows, ci, H, W, _p(conv.weight), _p(conv.bias), co, k,
-                   s, p, RELU, _p(y), self.st)
+            L.call('smi_conv2d_forward', p(x), int(x.dtype == torch.uint8),
+                   int(i == 0 and m.is_uint8), rows, ci, H, W, p(conv.weight), p(conv.bias), co, k,
+                   s, pad, RELU, p(y), self.st)
             x = y
         return x.view(rows, -1)
 
@@ -365,18 +349,18 @@ class _QNet(object):
         need = max(int(L.lib().smi_conv2d_scratch_bytes(rows, *geo)) for geo in m.conv_geoms)
         scratch = self.buf('conv_scratch', ((need + 3) // 4,))
         dy = self.buf(f'{pre}_dc{n - 1}', tuple(acts[n].shape))
-        L.call('smi_linear_backward_input', _p(dH1), S * hs[0], rows, S * hs[0], _p(m.w1), D, D,
-               _p(acts[n]), D, _p(dy), D, self.st)
+        L.call('smi_linear_backward_input', p(dH1), S * hs[0], rows, S * hs[0], p(m.w1), D, D,
+               p(acts[n]), D, p(dy), D, self.st)
         for i in range(n - 1, -1, -1):
-            ci, H, W, co, k, s, p = m.conv_geoms[i]
+            ci, H, W, co, k, s, pad = m.conv_geoms[i]
             conv, xi = m.conv_layers[i], acts[i]
-            L.call('smi_conv2d_backward_weight', _p(dy), _p(xi), int(xi.dtype == torch.uint8),
-                   int(i == 0 and m.is_uint8), rows, ci, H, W, co, k, s, p,
-                   _p(g[m.off(conv.weight):]), _p(g[m.off(conv.bias):]), _p(scratch), need, self.st)
+            L.call('smi_conv2d_backward_weight', p(dy), p(xi), int(xi.dtype == torch.uint8),
+                   int(i == 0 and m.is_uint8), rows, ci, H, W, co, k, s, pad,
+                   p(g[m.off(conv.weight):]), p(g[m.off(conv.bias):]), p(scratch), need, self.st)
             if i:
                 dx = self.buf(f'{pre}_dc{i - 1}', tuple(xi.shape))
-                L.call('smi_conv2d_backward_input', _p(dy), rows, ci, H, W, _p(conv.weight), co, k, s,
-                       p, _p(xi), _p(dx), self.st)
+                L.call('smi_conv2d_backward_input', p(dy), rows, ci, H, W, p(conv.weight), co, k, s,
+                       pad, p(xi), p(dx), self.st)
                 dy = dx
 
     def fwd(self, x, rows, pre):
@@ -387,10 +371,7 @@ class _QNet(object):
         S = 2 if m.dueling else 1
         if m.convs:
             x = self.conv_fwd(x, rows, pre)
-        if (x.dim() != 2 or x.shape[0] < rows or x.shape[1] != D or x.stride(1) != 1
-                or x.dtype != torch.float32):
-            raise ValueError(f'q_func input: expected a float32 [{rows}][{D}] matrix, got '
-                             f'{x.dtype} {tuple(x.shape)}')
+        self.check_rows(x, rows, D, 'q_func')
         H1 = self.buf(pre + '_h1', (rows, S * hs[0]))
         self.lin(x, x.stride(0), rows, D, m.w1, D, m.b1, S * hs[0], RELU, H1, S * hs[0])
         outs = []
@@ -433,14 +414,14 @@ class _QNet(object):
                 n_out = lin.out_features
                 xk, ldx = acts[k - 1]
                 dx, lddx = grads[k - 1]
-                L.call('smi_linear_backward_weight', _p(dy), ldg, rows, n_out, _p(xk), ldx, hs[k - 1],
-                       _p(g[m.off(lin.weight):]), hs[k - 1], _p(g[m.off(lin.bias):]), 0, st)
-                L.call('smi_linear_backward_input', _p(dy), ldg, rows, n_out, _p(lin.weight),
-                       hs[k - 1], hs[k - 1], _p(xk), ldx, _p(dx), lddx, st)
+                L.call('smi_linear_backward_weight', p(dy), ldg, rows, n_out, p(xk), ldx, hs[k - 1],
+                       p(g[m.off(lin.weight):]), hs[k - 1], p(g[m.off(lin.bias):]), 0, st)
+                L.call('smi_linear_backward_input', p(dy), ldg, rows, n_out, p(lin.weight),
+                       hs[k - 1], hs[k - 1], p(xk), ldx, p(dx), lddx, st)
                 dy, ldg = dx, lddx
         # both streams' first layers: one weight-gradient GEMM over dH1 [rows][S h1]
-        L.call('smi_linear_backward_weight', _p(dH1), S * hs[0], rows, S * hs[0], _p(x), x.stride(0),
-               D, _p(g[m.off(m.w1):]), D, _p(g[m.off(m.b1):]), 0, st)
+        L.call('smi_linear_backward_weight', p(dH1), S * hs[0], rows, S * hs[0], p(x), x.stride(0),
+               D, p(g[m.off(m.w1):]), D, p(g[m.off(m.b1):]), 0, st)
         if m.convs:
             self.conv_bwd(frames, rows, pre, dH1, g)
 
@@ -471,7 +452,7 @@ def _column(t, B, what):
     return t, (t.stride(0) if B > 1 else 1)
 
 
-class DQNLearner(LearnerHooks):
+class DQNLearner(DeviceLearner):
     """dqn.py:9-126 on MI355X (low-dimensional observations, or uint8 frames
     with model.convs; discrete actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
     replay.PrioritizedReplay.sample_batch) weights the Huber loss; after every
@@ -481,21 +462,11 @@ class DQNLearner(LearnerHooks):
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  device=None, seed=0, use_graph=False, checkpoint=None,
                  checkpoint_full_state=False):
-        self.learner_config = lc = learner_config if isinstance(learner_config, Config) \
-            else Config(learner_config)
-        self.env_config = ec = env_config if isinstance(env_config, Config) else Config(env_config)
-        D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)
+        lc, ec = as_config(learner_config), as_config(env_config)
+        D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)      # host checks come first
         self.algo = algo = lc.algo
         self.target_update_tracker = TargetUpdateTracker(algo.target_network_update_freq)
-        L.require_gpu()
-        self.checkpoint_full_state = bool(checkpoint_full_state)
-        self.session_config = session_config
-        self._init_hooks(metrics, checkpoint)
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        L.ensure_workspace(self.device)
-        self._ctx = L.Context(self.device)      # this learner's own workspace (re-entrancy)
-        self.current_iteration = 0
+        self._init_device(lc, ec, session_config, metrics, checkpoint, device, checkpoint_full_state)
         self.action_dim, self.obs_dim = A, D
         self.double_q = bool(algo.double_q)
         clip = algo.get('grad_norm_clipping')
@@ -504,17 +475,10 @@ class DQNLearner(LearnerHooks):
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
         self.pixel = bool(conv_kw)
         self.q_target = self.q_func.clone()                   # dqn.py:17
-        flat, dev = self.q_func.flat, self.device
-        self.opt = {'m': torch.zeros_like(flat), 'v': torch.zeros_like(flat),
-                    'step': torch.zeros(1, dtype=torch.int32, device=dev),
-                    'lr': torch.tensor([algo.lr], dtype=torch.float32, device=dev),
-                    'g': torch.zeros_like(flat)}
-        self.stats_buf = torch.zeros(2, dtype=torch.float32, device=dev)
+        self.opt = self.adam_state(self.q_func.flat, algo.lr)
+        self.stats_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.td_error = None
-        self._bufs = {}
         self.use_graph = bool(use_graph)
-        self._graph = None
-        self._gin = None
 
     # ------------------------------------------------------------ helpers
     def _update_target(self):                                            # dqn.py:27-28
@@ -579,80 +543,29 @@ class DQNLearner(LearnerHooks):
         dadv = net.buf('dadv', (B, A))
         dval = net.buf('dval', (B, 1)) if dueling else None
         self.td_error = net.buf('td', (B,))
-        L.call('smi_dqn_td', _p(adv), A, _p(adv_n), A, _p(adv_t), A, _p(val), 1, _p(val_n), 1,
-               _p(val_t), 1, _p(act), a_s, _p(rew), r_s, _p(don), d_s, _p(weights), B, A,
-               float(self.algo.gamma), int(dueling), int(self.double_q), _p(dadv), A, _p(dval),
-               _p(self.td_error), None, _p(self.stats_buf), st)
-        o = self.opt
-        L.call('smi_dw_group_begin')
-        try:
-            net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], o['g'])
-        finally:
-            L.call('smi_dw_group_flush', st)       # always flush: nothing stays queued
-        flat = self.q_func.flat
-        L.call('smi_adam_clip', _p(flat), _p(o['g']), _p(o['m']), _p(o['v']), flat.numel(),
-               _p(o['step']), _p(o['lr']), 0.9, 0.999, 1e-4, 0.0, self.max_norm, 0.0, None, None, st)
+        L.call('smi_dqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
+               p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, A,
+               float(self.algo.gamma), int(dueling), int(self.double_q), p(dadv), A, p(dval),
+               p(self.td_error), None, p(self.stats_buf), st)
+        with L.dw_group(st):
+            net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'])
+        self.adam_step(self.opt, self.q_func.flat, 1e-4, self.max_norm, 0.0, st)
 
     # ------------------------------------------------------- reference API
-    def learn(self, batch):                                              # dqn.py:75-92
-        self.current_iteration += 1
-        self._ctx.make_current()
-        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
-            batch = self.preprocess(batch)
+    def _learn_device(self, batch):                                      # dqn.py:75-92
         obs, obs_next = self._obs_of(batch['obs']), self._obs_of(batch['obs_next'])
         actions = batch['actions']
         if actions.dtype != torch.float32:
             actions = actions.to(torch.float32)
         ins = (obs, actions, batch['rewards'], obs_next, batch['dones'])
         weights = batch.get('weights')
-        if self.use_graph:
-            self._optimize_graphed(*ins, weights=weights)
+        if self.use_graph:      # the weights are one more static input (uint8 frames stay uint8)
+            self._graph_step(ins if weights is None else ins + (weights,), self._optimize)
         else:
             self._optimize(*ins, weights=weights)
+        # the target copy stays on the host, where its counter lives
         if self.target_update_tracker.track_increment(int(obs.shape[0])):
             self._update_target()
-        self._report_metrics(self.current_iteration)
-        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
-
-    def _optimize_graphed(self, obs, actions, rewards, obs_next, dones, weights=None):
-        """One _optimize as a hipGraph replay, as DDPGLearner._optimize_graphed:
-        the first call runs eagerly (it is that call's update and sizes every
-        buffer), then the same launch sequence is captured over static input
-        buffers; later calls copy their inputs in and replay.  The weights are
-        one more static input (a graph captured without them is captured again
-        when they appear, and the other way round).  The target copy stays on
-        the host, where its counter lives."""
-        ins = (obs, actions, rewards, obs_next, dones)
-        if weights is not None:
-            ins = ins + (weights,)
-        if self._graph is not None and (len(self._gin) != len(ins) or
-                                        self._gin[0].shape[0] != obs.shape[0]):
-            self._graph = None
-        if self._graph is None:
-            self._optimize(*ins[:5], weights=weights)
-            self._gin = [torch.zeros(tuple(t.shape), dtype=t.dtype, device=self.device)
-                         for t in ins]           # (uint8 frames of a pixel model stay uint8)
-            g = torch.cuda.CUDAGraph()
-            with L.gc_paused(), torch.cuda.graph(g, capture_error_mode='thread_local'):
-                self._optimize(*self._gin[:5], weights=self._gin[5] if weights is not None else None)
-            self._graph = g
-            return
-        for s, t in zip(self._gin, ins):
-            if s.data_ptr() != t.data_ptr():
-                s.copy_(t)
-        self._graph.replay()
-
-    def graph_inputs(self):
-        """Static (obs, actions, rewards, obs_next, dones[, weights]) buffers of
-        the captured step (None before the first learn() in graph mode)."""
-        return None if self._gin is None else dict(zip(
-            ('obs', 'actions', 'rewards', 'obs_next', 'dones', 'weights'), self._gin))
-
-    def _host_scalars(self):
-        return {}
-
-    def last_stats(self):
-        return self._stats_dict(self.stats_buf.cpu().numpy(), {})
 
     def _stats_dict(self, v, host):
         """'td_error' is the reference's scalar mean |td| (dqn.py:89-92)"""

@@ -27,12 +27,9 @@ import torch
 from . import _lib as L
 from .aggregator import MultistepAggregatorWithInfo, SSARAggregator, StagingArena
 from .config import Config, ConfigError
+from .device_learner import DeviceLearner, as_config, named_buf
 from .model import DiagGauss, PPOModel, RewardFilter
 from .session import LearnerHooks
-
-
-def _as_config(c):
-    return c if isinstance(c, Config) else Config(c or {})
 
 
 class LinearWithMinLR(object):
@@ -165,6 +162,8 @@ class PPOLearner(LearnerHooks):
     publish_parameter/checkpoint_attributes/preprocess/_prefetcher_preprocess/
     periodic_checkpoint."""
 
+    _init_device = DeviceLearner._init_device      # the constructor preamble, shared
+
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  publisher=None, device=None, seed=0, dp=None, checkpoint_full_state=False,
                  use_graph=False, checkpoint=None):
@@ -190,20 +189,10 @@ class PPOLearner(LearnerHooks):
         current_iteration) to (ppo.py:606-609): a PeriodicCheckpoint-like
         object (the reference's own, or session.PeriodicCheckpoint) or a
         callable(global_steps=, score=)."""
-        L.require_gpu()
+        lc, ec = self._init_device(learner_config, env_config, as_config(session_config), metrics,
+                                   checkpoint, device, checkpoint_full_state)
         self.dp = dp
-        self.checkpoint_full_state = bool(checkpoint_full_state)
-        self.learner_config = lc = _as_config(learner_config)
-        self.env_config = ec = _as_config(env_config)
-        self.session_config = _as_config(session_config)
-        self._init_hooks(metrics, checkpoint)
         self.publisher = publisher
-        self.device = torch.device(device) if device is not None else \
-            torch.device('cuda', torch.cuda.current_device())
-        L.ensure_workspace(self.device)
-        self._ctx = L.Context(self.device)      # this learner's own workspace (re-entrancy)
-
-        self.current_iteration = 0
         self.global_step = 0
         algo = lc.algo
         self.gamma = algo.gamma
@@ -302,7 +291,6 @@ class PPOLearner(LearnerHooks):
         idx = torch.tensor(range(self.n_step), dtype=torch.float32)
         self.gamma_tab = torch.pow(self.gamma, idx).to(dev)        # ppo.py:372-374
         self.lam_tab = torch.pow(self.lam, idx).to(dev)
-        self._bufs = {}
         self._arena = StagingArena(self.device)
         self._args = L.PPOArgs()
         # optional per-kernel HIP event timing: {kernel name: [(start, end), ...]}
@@ -316,8 +304,6 @@ class PPOLearner(LearnerHooks):
         # the GAE, so that combination stays eager.
         self.use_graph = bool(use_graph) and (
             dp is None or (getattr(dp, 'capturable', False) and not self.use_r_filter))
-        self._graph = None
-        self._gin = None
         # LSTM / pixel phases: ref_pol on a second stream beside the GAE pass
         self.prep_side_stream = os.environ.get('SMI_PREP_SIDE', '0') == '1'
         self._side = None
@@ -376,11 +362,7 @@ class PPOLearner(LearnerHooks):
         self.hyper.copy_(torch.from_numpy(h))
 
     def _buf(self, name, shape, dtype=torch.float32):
-        t = self._bufs.get(name)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = torch.zeros(shape, dtype=dtype, device=self.device)
-            self._bufs[name] = t
-        return t
+        return named_buf(self._bufs, self.device, name, shape, dtype)
 
     def _low_dim(self, obs):
         if isinstance(obs, torch.Tensor):

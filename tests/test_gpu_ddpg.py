@@ -463,3 +463,27 @@ def test_ddpg_graph_replay_bit_exact(target):
                                getattr(graph.model_target, name).flat), (it, name)
         assert eager.last_stats() == graph.last_stats(), it
     assert graph._graph is not None
+
+
+def test_ddpg_graph_recaptures_on_batch_size():
+    """a graph-mode learner handed another batch size captures the step again
+    (three calls at B = 64, then three at B = 32: eager + capture, two replays,
+    each): bit-identical to the eager learner after every call.  The smallest
+    shapes that still reach the split-K weight-gradient path."""
+    D, A = 5, 3
+    lc = _cfg(64, 'hard')
+    lc.model.actor_fc_hidden_sizes, lc.model.critic_fc_hidden_sizes = [16, 8], [16, 8]
+    eager = DDPGLearner(lc, gym_env_config(D, A), seed=3)
+    graph = DDPGLearner(lc, gym_env_config(D, A), seed=3, use_graph=True)
+    for it, B in enumerate((64, 64, 64, 32, 32, 32)):
+        b = {k: v.cuda() for k, v in synthetic.ddpg_batch(B, D, A, seed=10 + it).items()}
+        eager.learn(b)
+        graph.learn(b)
+        torch.cuda.synchronize()
+        for name in ('actor', 'critic'):
+            assert torch.equal(getattr(eager.model, name).flat, getattr(graph.model, name).flat), (it, name)
+            assert torch.equal(getattr(eager.model_target, name).flat,
+                               getattr(graph.model_target, name).flat), (it, name)
+        assert torch.equal(eager.stats_buf, graph.stats_buf), it
+        assert eager.last_stats() == graph.last_stats(), it
+        assert graph._graph is not None and graph._gin[0].shape[0] == B
