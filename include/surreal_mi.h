@@ -851,6 +851,30 @@ int smi_dqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn
                int64_t done_stride, const float* w, int64_t B, int A, float gamma, int dueling,
                int double_q, float* dadv, int64_t ldd, float* dval, float* td_out, float* y_out,
                float* stats, void* stream);
+/* One rank's shard of smi_dqn_td over a global batch (data-parallel DQN): the
+ * B rows given are rows [row0, row0 + B) of a draw of B_global rows.  Per row
+ * the operation order is smi_dqn_td's (the same kernel; smi_dqn_td is
+ * B_global = B, row0 = 0), except:
+ *   g = (w * clamp(td, -1, 1)) / (float)B_global, so the plain sum of the ranks'
+ *     gradients is the gradient of mean(w l) over the global batch;
+ *   td_all [B_global]: td_all[row0 + i] = td_i, and every other entry is written
+ *     +0.0f by the same launch.  A SUM all-reduce of the ranks' td_all is then an
+ *     exact all-gather (x + 0 + ... + 0 = x in IEEE arithmetic), except that a
+ *     td of -0.0 arrives as +0.0, which priorities (|td|) do not see;
+ *   stats[2] = the shard's fixed-order fp64 sums / B_global: the ranks' values
+ *     sum to the global { mean(w l), mean |td| }.
+ * dadv [B][ldd], dval [B], y_out [B] and w [B] are the shard's own rows.
+ * SMI_E_ARG: everything smi_dqn_td rejects, B_global < B, row0 < 0,
+ * row0 + B > B_global. */
+int smi_dqn_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                     const float* adv_target, int64_t ldt, const float* val, int64_t val_stride,
+                     const float* val_next, int64_t val_next_stride, const float* val_target,
+                     int64_t val_target_stride, const float* actions, int64_t action_stride,
+                     const float* rewards, int64_t reward_stride, const float* dones,
+                     int64_t done_stride, const float* w, int64_t B, int64_t B_global,
+                     int64_t row0, int A, float gamma, int dueling, int double_q, float* dadv,
+                     int64_t ldd, float* dval, float* td_all, float* y_out, float* stats,
+                     void* stream);
 /* out[i] = first index of the maximum of row i's q_j (the combination and the
  * scan of smi_dqn_td) over adv [rows][lda >= A] (+ val with dueling):
  * QAgent.act's q_values.max(1)[1] (surreal/agent/q_agent.py:45-46). */

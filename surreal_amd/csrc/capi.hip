@@ -476,8 +476,37 @@ int smi_dqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn
           "dqn_td: dueling needs val, val_target, dval (and val_next with double_q)");
   return launch_dqn_td(adv, lda, adv_next, ldn, adv_target, ldt, val, val_stride, val_next,
                        val_next_stride, val_target, val_target_stride, actions, action_stride,
-                       rewards, reward_stride, dones, done_stride, w, B, A, gamma, dueling,
+                       rewards, reward_stride, dones, done_stride, w, B, B, 0, A, gamma, dueling,
                        double_q, dadv, ldd, dval, td_out, y_out, stats, SMI_STREAM(stream));
+}
+
+int smi_dqn_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                     const float* adv_target, int64_t ldt, const float* val, int64_t val_stride,
+                     const float* val_next, int64_t val_next_stride, const float* val_target,
+                     int64_t val_target_stride, const float* actions, int64_t action_stride,
+                     const float* rewards, int64_t reward_stride, const float* dones,
+                     int64_t done_stride, const float* w, int64_t B, int64_t B_global,
+                     int64_t row0, int A, float gamma, int dueling, int double_q, float* dadv,
+                     int64_t ldd, float* dval, float* td_all, float* y_out, float* stats,
+                     void* stream) {
+  REQUIRE(adv && adv_target && actions && rewards && dones && dadv && td_all && stats,
+          "dqn_td_shard: null pointer");
+  REQUIRE(!double_q || adv_next,
+          "dqn_td_shard: double_q without the online scores at s' (null pointer)");
+  REQUIRE(B >= 1, "dqn_td_shard: B < 1");
+  REQUIRE(A >= 1, "dqn_td_shard: A < 1");
+  REQUIRE(B_global >= B, "dqn_td_shard: B_global < B");
+  REQUIRE(row0 >= 0, "dqn_td_shard: row0 < 0");
+  REQUIRE(row0 <= B_global - B, "dqn_td_shard: row0 + B > B_global");
+  REQUIRE(lda >= A && ldt >= A && ldd >= A && (!double_q || ldn >= A),
+          "dqn_td_shard: leading dims too small");
+  REQUIRE(!dueling || (val && val_target && dval && (!double_q || val_next)),
+          "dqn_td_shard: dueling needs val, val_target, dval (and val_next with double_q)");
+  return launch_dqn_td(adv, lda, adv_next, ldn, adv_target, ldt, val, val_stride, val_next,
+                       val_next_stride, val_target, val_target_stride, actions, action_stride,
+                       rewards, reward_stride, dones, done_stride, w, B, B_global, row0, A, gamma,
+                       dueling, double_q, dadv, ldd, dval, td_all, y_out, stats,
+                       SMI_STREAM(stream));
 }
 
 int smi_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t val_stride,

@@ -6,6 +6,9 @@
 //                   (q_net.py:55-63), double-Q arg-max and gather (dqn.py:53-61),
 //                   Bellman target (dqn.py:63-67), TD error, Huber loss and its
 //                   gradient w.r.t. the online net's outputs, in ONE launch
+//                   smi_dqn_td_shard runs the SAME kernel on one rank's rows
+//                   [row0, row0 + B) of a global batch of B_global rows
+//                   (data-parallel DQN); smi_dqn_td is B_global = B, row0 = 0
 //   dqn_greedy<DUELING>   the same combination and arg-max rule over one score
 //                   matrix: int32 action per row (the agent's acting)
 //
@@ -24,6 +27,18 @@
 //   g   = (w * clamp(td, -1, 1)) / B                 (w == NULL: w = 1, same bits)
 //   dadv[j] = g * ([j == a] - 1/A) (dueling) | g * [j == a];  dval = g
 //   stats = { mean(w l), mean |td| }, fixed-order fp64 block sums
+// A shard (B rows of B_global) differs in three places only:
+//   g     = (w * clamp(td)) / B_global: the plain SUM of the ranks' gradients is
+//           the gradient of mean(w * l) over the global batch.
+//   td    goes to td_all[row0 + i]; every other entry of td_all[0, B_global) is
+//           written +0.0f by the same launch.  A SUM all-reduce of the ranks'
+//           td_all is then an exact all-gather: each entry is x + 0 + ... + 0 in
+//           some order, which is x in IEEE arithmetic for every x (NaN and Inf
+//           included) except x = -0.0, which comes out +0.0 (priorities read
+//           |td|, so they do not see it).
+//   stats = the shard's fixed-order fp64 sums / B_global: the ranks' values sum
+//           to the global means.
+// dadv, dval and y_out stay shard-local ([B] rows).
 //
 // Decisions where the reference's text does not settle it:
 //   1. U.huber_loss_per_element is not defined in the reference; it is read as
@@ -53,6 +68,7 @@ struct DqnTdArgs {
   const float* done; int64_t ds;
   const float* w;
   int64_t B; int A; float gamma;
+  int64_t Bg, row0;        // the global batch and the shard's first row in it (whole batch: B, 0)
   float* dadv; int64_t ldd;
   float* dval; float* td; float* y; float* stats;
 };
@@ -93,8 +109,12 @@ __global__ void __launch_bounds__(kWG) dqn_td_kernel(DqnTdArgs p) {
 #pragma clang fp contract(off)
   __shared__ double scr[kNW];
   const int A = p.A;
-  const float Bf = (float)p.B, invA = 1.f / (float)A;
+  const float Bf = (float)p.Bg, invA = 1.f / (float)A;
   double sl = 0.0, st = 0.0;
+  // the other ranks' entries of td_all (none for the whole batch): disjoint from
+  // the rows written below
+  for (int64_t i = threadIdx.x; i < p.Bg - p.B; i += kWG)
+    p.td[i < p.row0 ? i : i + p.B] = 0.f;
   for (int64_t i = threadIdx.x; i < p.B; i += kWG) {
     const float* a = p.adv + i * p.lda;
     const float* at = p.adv_t + i * p.ldt;
@@ -133,7 +153,7 @@ __global__ void __launch_bounds__(kWG) dqn_td_kernel(DqnTdArgs p) {
       da[j] = DUELING ? g * (e - invA) : g * e;
     }
     if (DUELING) p.dval[i] = g;
-    p.td[i] = td;
+    p.td[p.row0 + i] = td;
     if (p.y) p.y[i] = y;
     sl += (double)(wi * l);
     st += (double)ab;
@@ -141,8 +161,8 @@ __global__ void __launch_bounds__(kWG) dqn_td_kernel(DqnTdArgs p) {
   sl = block_sum_d(sl, scr);
   st = block_sum_d(st, scr);
   if (threadIdx.x == 0) {
-    p.stats[0] = (float)(sl / (double)p.B);
-    p.stats[1] = (float)(st / (double)p.B);
+    p.stats[0] = (float)(sl / (double)p.Bg);
+    p.stats[1] = (float)(st / (double)p.Bg);
   }
 }
 
@@ -166,11 +186,13 @@ int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
                   const float* adv_t, int64_t ldt, const float* val, int64_t vs,
                   const float* val_n, int64_t vns, const float* val_t, int64_t vts,
                   const float* actions, int64_t as, const float* rewards, int64_t rs,
-                  const float* dones, int64_t ds, const float* w, int64_t B, int A, float gamma,
-                  int dueling, int double_q, float* dadv, int64_t ldd, float* dval, float* td_out,
-                  float* y_out, float* stats, hipStream_t st) {
+                  const float* dones, int64_t ds, const float* w, int64_t B, int64_t B_global,
+                  int64_t row0, int A, float gamma, int dueling, int double_q, float* dadv,
+                  int64_t ldd, float* dval, float* td_all, float* y_out, float* stats,
+                  hipStream_t st) {
   const DqnTdArgs p{adv, lda, adv_n, ldn, adv_t, ldt, val, vs, val_n, vns, val_t, vts, actions, as,
-                    rewards, rs, dones, ds, w, B, A, gamma, dadv, ldd, dval, td_out, y_out, stats};
+                    rewards, rs, dones, ds, w, B, A, gamma, B_global, row0, dadv, ldd, dval,
+                    td_all, y_out, stats};
   if (dueling && double_q) {
     hipLaunchKernelGGL((dqn_td_kernel<true, true>), dim3(1), dim3(kWG), 0, st, p);
     return check_launch("dqn_td_kernel<1,1>");

@@ -68,9 +68,10 @@ int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
                   const float* adv_t, int64_t ldt, const float* val, int64_t vs,
                   const float* val_n, int64_t vns, const float* val_t, int64_t vts,
                   const float* actions, int64_t as, const float* rewards, int64_t rs,
-                  const float* dones, int64_t ds, const float* w, int64_t B, int A, float gamma,
-                  int dueling, int double_q, float* dadv, int64_t ldd, float* dval, float* td_out,
-                  float* y_out, float* stats, hipStream_t st);
+                  const float* dones, int64_t ds, const float* w, int64_t B, int64_t B_global,
+                  int64_t row0, int A, float gamma, int dueling, int double_q, float* dadv,
+                  int64_t ldd, float* dval, float* td_all, float* y_out, float* stats,
+                  hipStream_t st);
 int launch_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t vs, int64_t rows,
                       int A, int dueling, int32_t* out, hipStream_t st);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)

@@ -58,7 +58,19 @@ Out of scope (ConfigError): model.convs on a low-dimensional obs spec, a
 'pixel' obs spec without convs or together with 'low_dim' (FFQfunc has one
 input), more than 4 conv layers or a layer outside the kernel's ranges
 (1 <= k <= 8, 1 <= stride <= min(k, 4), 1 <= channels <= 128), a non-discrete
-action spec.  There is no data-parallel form.
+action spec.
+
+Data parallel (DQNLearner(dp=...), the protocol of DDPGLearner's dp): N ranks
+each learn on B / N rows of one global draw (replay.sample_shard) and end with
+the parameters, statistics, TD errors and, through
+update_priorities_from_td(idx_all, learner.td_error), the priority trees that
+one learner on the B rows would have.  smi_dqn_td_shard divides by the global
+batch, so the SUM of the ranks' gradient images is the global-batch gradient;
+it writes its rows of td_all [B] and +0.0 elsewhere, so the same SUM gathers
+the TD errors exactly; its statistics sum to the global means.  The three sit
+in ONE exchange image [gradient | td_all | stats] and one all-reduce per
+learn(), between the backward and smi_adam_clip, so the norm clip acts on the
+global-batch gradient.  Every rank then runs the same Adam on the same bits.
 """
 import numpy as np
 import torch
@@ -457,11 +469,26 @@ class DQNLearner(DeviceLearner):
     with model.convs; discrete actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
     replay.PrioritizedReplay.sample_batch) weights the Huber loss; after every
     learn() `td_error` is a device view [B] of Q(s, a) - y
-    (PrioritizedReplay.update_priorities_from_td)."""
+    (PrioritizedReplay.update_priorities_from_td).  With dp, `td_error` is
+    [B_global]: the TD errors of the WHOLE draw, in draw order, on every rank
+    (replay.sample_shard's idx_all names their slots)."""
 
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  device=None, seed=0, use_graph=False, checkpoint=None,
-                 checkpoint_full_state=False):
+                 checkpoint_full_state=False, **parallel):
+        """The one keyword `parallel` takes is dp (keyword only; anything else is
+        a TypeError, as for a named parameter).
+        dp: None (one GPU) or a data-parallel group exposing `world_size`,
+        `rank` and `allreduce_(tensor)` (in-place SUM, stream-ordered), e.g.
+        learner.TorchDistAllReduce().  Each rank passes its own
+        replay.batch_size = B_global / world rows of one global draw
+        (sample_shard); initial weights are broadcast from rank 0.  A group of
+        world 1 is dp=None.  use_graph with world > 1 runs eagerly (the
+        collective is not captured)."""
+        dp = parallel.pop('dp', None)
+        if parallel:
+            raise TypeError('DQNLearner() got an unexpected keyword argument {!r}'.format(
+                sorted(parallel)[0]))
         lc, ec = as_config(learner_config), as_config(env_config)
         D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)      # host checks come first
         self.algo = algo = lc.algo
@@ -475,10 +502,15 @@ class DQNLearner(DeviceLearner):
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
         self.pixel = bool(conv_kw)
         self.q_target = self.q_func.clone()                   # dqn.py:17
+        self.dp = dp if dp is not None and dp.world_size > 1 else None
+        if self.dp is not None:
+            from .learner import replicate_from_rank0
+            replicate_from_rank0(self.dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
         self.stats_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.td_error = None
-        self.use_graph = bool(use_graph)
+        self._xbuf = None             # the exchange image (dp only), sized by the first batch
+        self.use_graph = bool(use_graph) and self.dp is None
 
     # ------------------------------------------------------------ helpers
     def _update_target(self):                                            # dqn.py:27-28
@@ -522,8 +554,31 @@ class DQNLearner(DeviceLearner):
                 self.device, non_blocking=True)
         return Config(out)
 
+    def _exchange_image(self, B_global):
+        """[ gradient image (P floats, padded to a multiple of 4) | td_all
+        (B_global) | stats (2) ]: what one all-reduce per learn() carries.  The
+        optimizer's gradient, td_error and stats_buf are views of it."""
+        P = self.q_func.flat.numel()
+        P4 = (P + 3) // 4 * 4
+        if self._xbuf is None or self._xbuf.numel() != P4 + B_global + 2:
+            self._xbuf = x = torch.zeros(P4 + B_global + 2, dtype=torch.float32, device=self.device)
+            self.opt['g'] = x[:P]
+            self.td_error = x[P4:P4 + B_global]
+            self.stats_buf = x[P4 + B_global:]
+        return self._xbuf
+
     # --------------------------------------------------------- _optimize
     def _optimize(self, obs, actions, rewards, obs_next, dones, weights=None):   # dqn.py:42-73
+        self._gradient(obs, actions, rewards, obs_next, dones, weights)
+        self._apply()
+
+    def _apply(self):
+        self.adam_step(self.opt, self.q_func.flat, 1e-4, self.max_norm, 0.0, L.stream(self.device))
+
+    def _gradient(self, obs, actions, rewards, obs_next, dones, weights=None):
+        """everything of _optimize before the Adam step: the gradient image, the
+        TD errors and the statistics of this learner's rows (with dp: its shard's
+        part of the exchange image)"""
         B, A = obs.shape[0], self.action_dim
         act, a_s = _column(actions, B, 'actions')
         rew, r_s = _column(rewards, B, 'rewards')
@@ -542,29 +597,70 @@ class DQNLearner(DeviceLearner):
             adv_n, val_n = net.fwd(obs_next, B, 'n')
         dadv = net.buf('dadv', (B, A))
         dval = net.buf('dval', (B, 1)) if dueling else None
-        self.td_error = net.buf('td', (B,))
-        L.call('smi_dqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
-               p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, A,
-               float(self.algo.gamma), int(dueling), int(self.double_q), p(dadv), A, p(dval),
-               p(self.td_error), None, p(self.stats_buf), st)
+        if self.dp is None:
+            self.td_error = net.buf('td', (B,))
+            L.call('smi_dqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
+                   p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, A,
+                   float(self.algo.gamma), int(dueling), int(self.double_q), p(dadv), A, p(dval),
+                   p(self.td_error), None, p(self.stats_buf), st)
+        else:
+            world = self.dp.world_size
+            self._exchange_image(B * world)
+            L.call('smi_dqn_td_shard', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
+                   p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, B * world,
+                   self.dp.rank * B, A, float(self.algo.gamma), int(dueling), int(self.double_q),
+                   p(dadv), A, p(dval), p(self.td_error), None, p(self.stats_buf), st)
         with L.dw_group(st):
             net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'])
-        self.adam_step(self.opt, self.q_func.flat, 1e-4, self.max_norm, 0.0, st)
 
     # ------------------------------------------------------- reference API
-    def _learn_device(self, batch):                                      # dqn.py:75-92
+    def _learn_phases(self, batch):
+        """learn() as a generator of the buffers a data-parallel learner must
+        all-reduce (SUM) between its launches: the exchange image, once, after
+        the backward and before smi_adam_clip.  Without dp it yields nothing."""
+        self.current_iteration += 1
+        self._ctx.make_current()
+        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
+            batch = self.preprocess(batch)
+        if self.dp is None:
+            self._learn_device(batch)
+        else:
+            ins = self._inputs(batch)
+            self._gradient(*ins, weights=batch.get('weights'))
+            yield self._xbuf
+            self._ctx.make_current()      # whatever ran on this thread meanwhile
+            self._apply()
+            # samples of the GLOBAL batch: every rank copies the target on the
+            # step the single learner would
+            if self.target_update_tracker.track_increment(
+                    int(ins[0].shape[0]) * self.dp.world_size):
+                self._update_target()
+        self._report_metrics(self.current_iteration)
+        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
+
+    def learn(self, batch):
+        if self.dp is None:           # the one-GPU frame the off-policy learners share
+            return super().learn(batch)
+        for buf in self._learn_phases(batch):
+            self.dp.allreduce_(buf)
+
+    def _inputs(self, batch):
+        """(obs, actions, rewards, obs_next, dones) of a device batch"""
         obs, obs_next = self._obs_of(batch['obs']), self._obs_of(batch['obs_next'])
         actions = batch['actions']
         if actions.dtype != torch.float32:
             actions = actions.to(torch.float32)
-        ins = (obs, actions, batch['rewards'], obs_next, batch['dones'])
+        return (obs, actions, batch['rewards'], obs_next, batch['dones'])
+
+    def _learn_device(self, batch):                                      # dqn.py:75-92
+        ins = self._inputs(batch)
         weights = batch.get('weights')
         if self.use_graph:      # the weights are one more static input (uint8 frames stay uint8)
             self._graph_step(ins if weights is None else ins + (weights,), self._optimize)
         else:
             self._optimize(*ins, weights=weights)
         # the target copy stays on the host, where its counter lives
-        if self.target_update_tracker.track_increment(int(obs.shape[0])):
+        if self.target_update_tracker.track_increment(int(ins[0].shape[0])):
             self._update_target()
 
     def _stats_dict(self, v, host):

@@ -375,6 +375,12 @@ class UniformReplay(object):
         {'flat_inputs': [n, D]}}, 'obs_next': likewise, 'actions', 'rewards',
         'dones'} ('low_dim' omitted when D == 0).  The output buffers are
         allocated once per n and overwritten by the next call."""
+        idx_all, batch = self._draw_shard(batch_size, rank, world)
+        n = batch_size // world
+        return idx_all[rank * n:(rank + 1) * n], batch
+
+    def _draw_shard(self, batch_size, rank, world):
+        """sample_shard without a subclass's additions (sample_batch's body)"""
         if world < 1 or not 0 <= rank < world or batch_size % world:
             raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
         n = batch_size // world
@@ -385,12 +391,30 @@ class UniformReplay(object):
                 self._out = (rows,
                              torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device),
                              torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device))
-        if not self.is_pixel:
-            mine, rows = self.sample(batch_size, out=self._out[0], rank=rank, world=world)
-            return mine, self.split(rows)
-        rows, pix, pix_next = self._out
         idx = self.sample_indices(batch_size)
         mine = idx[rank * n:(rank + 1) * n]
+        return idx, self._gather_batch(mine, n)
+
+    def sample_shard(self, batch_size, rank, world):
+        """Returns (idx_all, batch) for one rank of a data-parallel learner
+        (DQNLearner(dp=...)): idx_all is the WHOLE draw, int64 [batch_size] on
+        the device (overwritten by the next draw), and batch is sample_batch's
+        dict for rows [rank * n, (rank + 1) * n) of it, n = batch_size / world,
+        gathered by the same kernels over the index slice.  Every replica draws
+        all batch_size indices from the one CPython-exact stream, so replicas
+        seeded and fed alike keep identical generators.  ValueError (before
+        anything is drawn) unless batch_size % world == 0 and
+        0 <= rank < world."""
+        return self._draw_shard(batch_size, rank, world)
+
+    def _gather_batch(self, mine, n):
+        """sample_batch's dict for the n drawn slots `mine`, into self._out"""
+        if not self.is_pixel:
+            rows = self._out[0]
+            L.call('smi_gather_rows', L.ptr(self.table), self.width, L.ptr(mine), n, L.ptr(rows),
+                   L.stream(self.device))
+            return self.split(rows)
+        rows, pix, pix_next = self._out
         if self.share_frames:
             L.call('smi_replay_gather_shared', L.ptr(self.table), self.width,
                    L.ptr(self.frame_store), L.ptr(self.frame_ids), self.frame_stacks, self.fbytes,
@@ -404,8 +428,8 @@ class UniformReplay(object):
         if self.obs_dim:
             obs['low_dim'] = {'flat_inputs': flat['obs']}
             obs_next['low_dim'] = {'flat_inputs': flat['obs_next']}
-        return mine, {'obs': obs, 'obs_next': obs_next, 'actions': flat['actions'],
-                      'rewards': flat['rewards'], 'dones': flat['dones']}
+        return {'obs': obs, 'obs_next': obs_next, 'actions': flat['actions'],
+                'rewards': flat['rewards'], 'dones': flat['dones']}
 
     def split(self, rows):
         D, A = self.obs_dim, self.act_dim
@@ -427,8 +451,13 @@ class PrioritizedReplay(UniformReplay):
     (p_i * len) ** -beta / max_w; a repeated index keeps its last priority.
 
     alpha is read from learner_config.replay.alpha, as the reference does.
-    Data parallelism is out of scope: replicated trees would need an
-    all-gather of the TD errors, so world > 1 raises ValueError."""
+    Data parallel: every rank keeps a replicated replay (same seed, same
+    inserts) and calls sample_shard(), which draws the whole global batch on
+    every rank and gathers the rank's rows; after DQNLearner(dp=...).learn()
+    every rank applies update_priorities_from_td(idx_all, learner.td_error),
+    the TD errors of the whole draw in draw order, so the trees stay
+    bit-identical.  sample() and sample_batch() are the one-rank calls:
+    world != 1 raises ValueError there."""
 
     def __init__(self, learner_config, env_config, session_config=None, index=0, seed=0,
                  device=None):
@@ -473,8 +502,9 @@ class PrioritizedReplay(UniformReplay):
     @staticmethod
     def _one_rank(world):
         if world != 1:
-            raise ValueError('a prioritized replay is not data parallel (world must be 1): '
-                             'replicated trees need an all-gather of the TD errors')
+            raise ValueError('sample() and sample_batch() of a prioritized replay take world = 1: '
+                             'a data-parallel rank calls sample_shard(batch_size, rank, world), '
+                             'which keeps the replicated trees identical')
 
     def sample(self, batch_size, out=None, rank=0, world=1, beta=0):
         """(indices, rows, weights [batch] float32) on the device"""
@@ -505,6 +535,22 @@ class PrioritizedReplay(UniformReplay):
                 self._beta = None
         batch['weights'] = self.weights.view(-1, 1)
         return idx, batch
+
+    def sample_shard(self, batch_size, rank, world, beta=0):
+        """UniformReplay.sample_shard over the proportional draw: smi_per_sample
+        draws the whole batch on every rank, and batch['weights'] is this
+        rank's slice, float32 [n, 1] (the weights are normalised by the tree
+        minimum, not by the batch, so they do not depend on the shard).  After
+        learn(), every rank calls update_priorities_from_td(idx_all,
+        learner.td_error)."""
+        self._beta = beta
+        try:
+            idx_all, batch = super().sample_shard(batch_size, rank, world)
+        finally:
+            self._beta = None
+        n = batch_size // world
+        batch['weights'] = self.weights[rank * n:(rank + 1) * n].view(-1, 1)
+        return idx_all, batch
 
     def _indices(self, indices):
         if isinstance(indices, torch.Tensor):

@@ -1,0 +1,106 @@
+"""Data-parallel DQN over the real exchange: two processes share cuda:0 and
+all-reduce over torch.distributed (gloo: RCCL refuses two ranks on one GPU; a
+multi-GPU node runs the same code over 'nccl', tools/bench_dqn.py --gpus N)
+through learner.TorchDistAllReduce.  Each rank holds a PrioritizedReplay
+replica (same seed, same inserts) and runs sample_shard -> learn ->
+update_priorities_from_td(idx_all, td_error) for 3 steps of the b96_duel_dq
+case.  Required: the ranks end bit-identical (parameters, target, statistics,
+TD errors, draws and the saved priority trees), and rank 0 lies on the single
+learner's envelope (tests/dqn_ref.py envelope_check) for the 96 drawn rows."""
+import copy
+import os
+import tempfile
+
+import numpy as np
+import pytest
+import torch
+import torch.multiprocessing as mp
+
+from tests.test_gpu_dp_procs import _free_port
+
+pytestmark = pytest.mark.gpu
+
+CASE, NROWS, SEED, STEPS, BETA = 'b96_duel_dq', 300, 2468, 3, 0.4
+
+
+def _case():
+    from tests import dqn_ref as R
+    lc, D, A, init, _ = R.envelope_case(CASE)
+    lc = copy.deepcopy(lc)
+    lc.replay.memory_size, lc.replay.sampling_start_size = 400, 10
+    g = torch.Generator().manual_seed(1)
+    rows = torch.randn(NROWS, 2 * D + 3, generator=g)
+    rows[:, D] = torch.randint(0, A, (NROWS,), generator=g).float()
+    rows[:, 2 * D + 2] = (torch.rand(NROWS, generator=g) < 0.1).float()
+    return lc, D, A, init, rows
+
+
+def _worker(rank, world, port, outdir):
+    os.environ['MASTER_ADDR'] = '127.0.0.1'
+    os.environ['MASTER_PORT'] = str(port)
+    import torch.distributed as dist
+    torch.cuda.set_device(0)
+    dist.init_process_group('gloo', rank=rank, world_size=world)
+    from surreal_amd.config import discrete_env_config
+    from surreal_amd.dqn import DQNLearner
+    from surreal_amd.learner import TorchDistAllReduce
+    from surreal_amd.replay import PrioritizedReplay
+    from tests import dqn_ref as R
+    lc, D, A, init, rows = _case()
+    ec = discrete_env_config(D, A)
+    rep = PrioritizedReplay(lc, ec, seed=SEED, device='cuda:0')
+    rep.insert_rows(rows)
+    Bg = lc.replay.batch_size
+    lc_rank = copy.deepcopy(lc)
+    lc_rank.replay.batch_size = Bg // world
+    # a different seed per rank: the constructor's broadcast replicates rank 0's weights
+    learner = DQNLearner(lc_rank, ec, seed=5 + rank, device='cuda:0', dp=TorchDistAllReduce())
+    replicated = learner.q_func.flat.cpu().clone()
+    learner.q_func.load_state_dict(init['q_func'])
+    learner.q_target.load_state_dict(init['q_target'])
+    res = []
+    for it in range(STEPS):
+        idx_all, batch = rep.sample_shard(Bg, rank, world, beta=BETA)
+        weights = rep.weights.cpu().clone()
+        learner.learn(batch)
+        rep.update_priorities_from_td(idx_all, learner.td_error)
+        res.append({'idx': idx_all.cpu().clone(), 'weights': weights,
+                    'q_func': learner.q_func.flat.cpu().clone(),
+                    'q_target': learner.q_target.flat.cpu().clone(),
+                    'state': {k: torch.as_tensor(v) for k, v in (
+                        ('q_func', R.flat_of(learner.q_func.state_dict())),
+                        ('q_target', R.flat_of(learner.q_target.state_dict())))},
+                    'stats': learner.last_stats(), 'stats_buf': learner.stats_buf.cpu().clone(),
+                    'td': learner.td_error.cpu().clone(), 'tree': rep.tree.cpu().clone(),
+                    'tracker': learner.target_update_tracker.value})
+    torch.save({'replicated': replicated, 'res': res}, os.path.join(outdir, f'rank{rank}.pt'))
+    dist.destroy_process_group()
+
+
+@pytest.mark.timeout(600)
+def test_two_process_dqn_dp_matches_single_learner():
+    from tests import dqn_ref as R
+    from tests import parity as P
+    world = 2
+    with tempfile.TemporaryDirectory() as outdir:
+        mp.spawn(_worker, args=(world, _free_port(), outdir), nprocs=world, join=True)
+        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True) for r in range(world)]
+    lc, D, A, init, rows = _case()
+    Bg = lc.replay.batch_size
+    assert torch.equal(out[0]['replicated'], out[1]['replicated'])     # replicate_from_rank0
+    batches, got = [], []
+    for it in range(STEPS):
+        r0, r1 = out[0]['res'][it], out[1]['res'][it]
+        for k in ('idx', 'weights', 'q_func', 'q_target', 'stats_buf', 'td', 'tree'):
+            assert torch.equal(r0[k], r1[k]), (it, k)
+        assert r0['stats'] == r1['stats']
+        assert r0['tracker'] == r1['tracker'] == (it + 1) * Bg
+        assert tuple(r0['td'].shape) == (Bg,)
+        assert torch.equal(r0['q_func'], r0['q_target']) == (it == 1)
+        drawn = rows[r0['idx']].numpy()
+        batches.append({'obs': drawn[:, :D], 'actions': drawn[:, D:D + 1].astype(np.int32),
+                        'rewards': drawn[:, D + 1:D + 2], 'obs_next': drawn[:, D + 2:2 * D + 2],
+                        'dones': drawn[:, 2 * D + 2:], 'weights': r0['weights'].numpy().reshape(-1, 1)})
+        got.append(({k: v.numpy() for k, v in r0['state'].items()}, r0['stats'],
+                    r0['td'].double().numpy()))
+    P.print_report(R.envelope_check(lc, D, A, init, batches, got))

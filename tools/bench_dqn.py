@@ -15,7 +15,14 @@ eager torch on the same GPU (nn.Conv2d through MIOpen, fp32, Adam eps 1e-4,
 clip_grad_norm_ 10): the expectation a pixel learn() is reported against.  When
 the torch step cannot run, that is printed and the project's numbers stand alone.
 
-Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel]
+--gpus N (2 <= N <= 16) times the data-parallel loop instead: one process per
+GPU (torch.multiprocessing spawn, 'nccl' = RCCL), each with one
+DQNLearner(dp=TorchDistAllReduce()) and one PrioritizedReplay replica, a step
+being sample_shard -> learn -> update_priorities_from_td at a global batch of
+512 (512 / N rows per rank).  Rank 0 prints the one JSON line.  With fewer than
+N (or fewer than two) GPUs visible it says so and starts nothing.
+
+Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel | --gpus N]
 """
 import argparse
 import copy
@@ -160,12 +167,65 @@ def pixel_main(args):
                               'not_measured': str(e).splitlines()[0][:200]}), flush=True)
 
 
+def dp_worker(rank, world, port, iters, warmup):
+    os.environ['MASTER_ADDR'], os.environ['MASTER_PORT'] = '127.0.0.1', str(port)
+    import torch.distributed as dist
+    from surreal_amd.learner import TorchDistAllReduce
+    from surreal_amd.replay import PrioritizedReplay
+    torch.cuda.set_device(rank)
+    dev = f'cuda:{rank}'
+    dist.init_process_group('nccl', rank=rank, world_size=world)
+    Bg, D, A, rows = 512, 17, 6, 20000
+    lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = Bg // world
+    lc.replay.memory_size, lc.replay.sampling_start_size = rows, 1000
+    lc.model.fc_hidden_sizes = [128, 128]
+    ec = discrete_env_config(D, A)
+    replay = PrioritizedReplay(lc, ec, seed=0, device=dev)
+    g = torch.Generator().manual_seed(0)
+    table = torch.randn(rows, 2 * D + 3, generator=g)
+    table[:, D] = torch.randint(0, A, (rows,), generator=g).float()
+    table[:, 2 * D + 2] = (torch.rand(rows, generator=g) < 0.05).float()
+    replay.insert_rows(table)
+    learner = DQNLearner(lc, ec, seed=0, device=dev, dp=TorchDistAllReduce())
+
+    def step():
+        idx_all, batch = replay.sample_shard(Bg, rank, world, beta=0.4)
+        learner.learn(batch)
+        replay.update_priorities_from_td(idx_all, learner.td_error)
+    med, q1, q3 = timed(step, iters, warmup)
+    if rank == 0:
+        print(json.dumps({'measurement': 'dqn_dp_per_loop', 'gpus': world, 'B_global': Bg,
+                          'backend': 'nccl', 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                          'q3_ms': round(q3, 4), 'iters': iters}), flush=True)
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def dp_main(args):
+    import socket
+    import torch.multiprocessing as mp
+    n, seen = args.gpus, torch.cuda.device_count()
+    if not 2 <= n <= 16 or 512 % n:
+        sys.exit(f'--gpus {n}: takes 2 to 16 processes that divide the batch of 512')
+    if seen < 2 or seen < n:
+        sys.exit(f'--gpus {n}: {seen} GPU(s) visible, nothing started')
+    with socket.socket() as s:
+        s.bind(('127.0.0.1', 0))
+        port = s.getsockname()[1]
+    mp.spawn(dp_worker, args=(n, port, args.iters, args.warmup), nprocs=n, join=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--pixel', action='store_true')
+    ap.add_argument('--gpus', type=int, default=1,
+                    help='N >= 2: the data-parallel loop, one process per GPU')
     args = ap.parse_args()
+    if args.gpus != 1:
+        return dp_main(args)
     if args.pixel:
         return pixel_main(args)
     B, D, A = 512, 17, 6
