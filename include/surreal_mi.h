@@ -683,6 +683,74 @@ int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div
                                float* dw, float* db, void* scratch, int64_t scratch_bytes,
                                void* stream);
 
+/* The pixel stem of free shape: CNNStemNetwork (builders.py:8-33) with the
+ * layers of model.conv_spec (ddpg_configs.py:22-27) on any camera.  n conv
+ * layers, 1 <= n <= 4, layer i = Conv2d(cout[i], k[i], stride[i]) without
+ * padding + ReLU, then Flatten (C, H, W order) -> Linear(F) -> ReLU, all on
+ * obs / 255.  Layer i sees (cin_i, h_i, w_i) = the previous layer's output
+ * ((C, H, W) for layer 0) and gives Ho = (h - k) / stride + 1, Wo likewise
+ * (integer division; trailing rows or columns no window covers are fine).  A
+ * spec is accepted when every layer is inside the ranges of smi_conv2d_* above
+ * with pad = 0 (1 <= k <= 8, 1 <= stride <= min(k, 4), 1 <= channels <= 128,
+ * Ho, Wo >= 1 and the index limits) and F >= 1.
+ *   params / grad: flat, torch module order: [conv_i.weight (cout_i, cin_i, k_i,
+ *            k_i) | conv_i.bias] for each layer, then [fc.weight (F, flat) |
+ *            fc.bias], flat = cout_n Ho_n Wo_n: smi_stem_param_count floats.
+ *            For the default spec {16, 32}, {8, 4}, {4, 2} this is the layout
+ *            of smi_cnn_param_count, bit for bit.
+ *   pix / pix_next / B / T / rows: as in smi_cnn_* (activation row n = t B + b
+ *            is pix[b][t] for t < T, pix_next[b] for t == T).
+ *   act:     the activations, layer i [rows][cout_i Ho_i Wo_i], the layers one
+ *            behind the other: smi_stem_act_floats(rows, ...) floats.
+ * Two implementations compute it, chosen per call from the arguments alone;
+ * smi_stem_fused returns which (1 fused, 0 general, SMI_E_ARG for a spec or
+ * frame that is refused):
+ *   fused    the kernels behind smi_cnn_* (one workgroup per image, the frame
+ *            in LDS): the default spec on a frame smi_cnn_* accepts, forward
+ *            and backward (C 3 or 9, W % 4 == 0, C H W % 16 == 0, even conv-1
+ *            width, conv-1 pixels % 4 == 0, at most 96 conv-2 pixels, both LDS
+ *            limits).  It asks 16-byte aligned pixel buffers; its results are
+ *            those of smi_cnn_*, bit for bit.
+ *   general  one smi_conv2d_* launch per layer and direction, the first layer
+ *            reading its uint8 images through the row map (64-bit bases,
+ *            element alignment), the Linear layer on the GEMM engine: every
+ *            other accepted spec and frame.
+ *   forward: act (optional) receives every layer's activation; a backward
+ *            needs it.  Without it (acting) the intermediates live in `scratch`
+ *            (smi_stem_scratch_bytes).  feat [rows][F] at row stride ldf.
+ *   backward: dz = dL/d(fc pre-activation), the ReLU mask applied, [rows][F] at
+ *            lddz; act as the forward left it.  The whole gradient is WRITTEN
+ *            (not accumulated) into grad.  dA_{i-1} = [A_{i-1} > 0] *
+ *            conv^T(dA_i, w_i); layer 1 computes no input gradient.  Partials
+ *            are summed in a fixed order without float atomics: two runs give
+ *            the same bits.  scratch: smi_stem_scratch_bytes (one size serves
+ *            both calls), every float written before it is read.
+ *   skip:    optional device int; when it is non-zero at launch time every
+ *            kernel of the call returns without writing (the learners' early
+ *            stop).  NULL: run.
+ * An out-of-range spec, a frame smaller than a layer, a NULL pointer, rows >
+ * B T without pix_next or too little scratch is SMI_E_ARG with
+ * smi_last_error() naming the layer, and nothing launched; rows == 0 is SMI_OK
+ * without a launch.  The three size queries return -1 for such a spec. */
+int64_t smi_stem_param_count(int n, const int* cout, const int* k, const int* stride, int C, int H,
+                             int W, int F);
+int64_t smi_stem_act_floats(int64_t rows, int n, const int* cout, const int* k, const int* stride,
+                            int C, int H, int W, int F);
+int64_t smi_stem_scratch_bytes(int64_t rows, int n, const int* cout, const int* k, const int* stride,
+                               int C, int H, int W, int F);
+int smi_stem_fused(int n, const int* cout, const int* k, const int* stride, int C, int H, int W,
+                   int F);
+int smi_stem_forward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
+                     int64_t T, int64_t rows, int n, const int* cout, const int* k,
+                     const int* stride, int C, int H, int W, int F, float* act, void* scratch,
+                     int64_t scratch_bytes, float* feat, int64_t ldf, const int* skip,
+                     void* stream);
+int smi_stem_backward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
+                      int64_t T, int64_t rows, int n, const int* cout, const int* k,
+                      const int* stride, int C, int H, int W, int F, const float* act,
+                      const float* dz, int64_t lddz, float* grad, void* scratch,
+                      int64_t scratch_bytes, const int* skip, void* stream);
+
 /* running_sum += sum_in, running_sumsq += sumsq_in, count += rows — the
  * data-parallel z_update after the column statistics were all-reduced. */
 int smi_zfilter_accumulate(const float* sum_in, const float* sumsq_in, int dim, float rows,

@@ -226,6 +226,14 @@ _SIGS = {
     'smi_conv2d_backward_input': (c_int, [P, c_i64, c_int, c_int, c_int, P] + [c_int] * 4 + [P, P, P]),
     'smi_conv2d_backward_weight': (c_int, [P, P, c_int, c_int, c_i64] + [c_int] * 7 +
                                    [P, P, P, c_i64, P]),
+    'smi_stem_param_count': (c_i64, [c_int, P, P, P] + [c_int] * 4),
+    'smi_stem_act_floats': (c_i64, [c_i64, c_int, P, P, P] + [c_int] * 4),
+    'smi_stem_scratch_bytes': (c_i64, [c_i64, c_int, P, P, P] + [c_int] * 4),
+    'smi_stem_fused': (c_int, [c_int, P, P, P] + [c_int] * 4),
+    'smi_stem_forward': (c_int, [P, P, P, c_i64, c_i64, c_i64, c_int, P, P, P] + [c_int] * 4 +
+                         [P, P, c_i64, P, c_i64, P, P]),
+    'smi_stem_backward': (c_int, [P, P, P, c_i64, c_i64, c_i64, c_int, P, P, P] + [c_int] * 4 +
+                          [P, P, c_i64, P, P, c_i64, P, P]),
     'smi_ppo_rnn_phase': (c_int, [ctypes.POINTER(RNNArgs), c_int, c_int, P]),
     'smi_lstm_forward': (c_int, [P, P, P, P, P, c_int, c_int, c_int, P, P, P, P]),
     'smi_lstm_backward': (c_int, [P, P, P, P, c_int, c_int, c_int, P, P]),
@@ -280,6 +288,14 @@ def ptr(t):
         raise RuntimeError('surreal_amd kernels take device (HIP) tensors; got a CPU tensor '
                            '(there is no CPU fallback)')
     return ctypes.c_void_p(t.data_ptr())
+
+
+def stem_spec(channels, kernel_sizes, strides):
+    """(n, cout, k, stride): the spec arguments of smi_stem_* as one int and three int arrays."""
+    n = len(channels)
+    arr = c_int * max(n, 1)
+    return (n, arr(*[int(v) for v in channels]), arr(*[int(v) for v in kernel_sizes]),
+            arr(*[int(v) for v in strides]))
 
 
 def stream(device=None):

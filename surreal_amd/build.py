@@ -16,7 +16,7 @@ BUILD = os.path.join(ROOT, 'build', 'obj')
 LIB = os.path.join(HERE, 'libsurreal_mi.so')
 HEADERS = ['smi_device.hpp', 'smi_internal.hpp', 'lstm_cell.hpp', 'pol_rows.hpp', 'mt19937.hpp',
            'gemm_args.hpp', 'dw_plan.hpp', 'smi_shapes.hpp', 'smi_launch.hpp', 'rnn_layout.hpp',
-           'rnn_kernels.hpp', 'conv_plan.hpp']
+           'rnn_kernels.hpp', 'conv_plan.hpp', 'stem_plan.hpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-object-version=5',
@@ -32,7 +32,7 @@ UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('linear_kernels.hip', []), ('linear_dw.hip', []), ('ddpg_kernels.hip', []),
          ('dqn_kernels.hip', []),
          ('lstm_mfma.hip', []), ('lstm_valu.hip', ['-fno-slp-vectorize']), ('cnn_kernels.hip', []),
-         ('conv_kernels.hip', []),
+         ('conv_kernels.hip', []), ('stem.hip', []),
          ('head_kernels.hip', []), ('ppo_rnn_kernels.hip', []), ('ppo_rnn.hip', []),
          ('calib_kernels.hip', []), ('capi.hip', [])]
 

@@ -8,6 +8,7 @@
 #include "smi_internal.hpp"
 #include "rnn_layout.hpp"
 #include "conv_plan.hpp"
+#include "stem_plan.hpp"
 
 namespace smi {
 
@@ -895,6 +896,114 @@ int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div
 }
 #undef CONV_GEOM_CHECK
 
+/* ---------------------------------------------- pixel stem of free shape */
+namespace {
+// the layer stem_check refuses, named in smi_last_error()
+int stem_spec_error(const char* what, int bad) {
+  char msg[224];
+  if (bad < 0)
+    snprintf(msg, sizeof msg, "%s: need 1 to %d conv layers (cout, k, stride arrays of that length) "
+             "and F >= 1", what, kStemMaxLayers);
+  else
+    snprintf(msg, sizeof msg, "%s: conv layer %d is outside 1 <= k <= 8, 1 <= stride <= min(k, 4), "
+             "1 <= channels <= 128, or the frame it receives is smaller than its window", what, bad);
+  return set_error(SMI_E_ARG, msg);
+}
+// 0 and *p filled, or SMI_E_ARG
+int stem_args(const char* what, int n, const int* cout, const int* k, const int* stride, int C, int H,
+              int W, int F, StemPlan* p) {
+  if (n >= 1 && n <= kStemMaxLayers && !(cout && k && stride)) return stem_spec_error(what, -1);
+  const StemSpec s = stem_spec(n, cout, k, stride, F);
+  const int bad = stem_check(s, C, H, W);
+  if (bad) return stem_spec_error(what, bad);
+  *p = stem_plan(s, C, H, W);
+  return SMI_OK;
+}
+}  // namespace
+
+int64_t smi_stem_param_count(int n, const int* cout, const int* k, const int* stride, int C, int H,
+                             int W, int F) {
+  StemPlan p;
+  return stem_args("stem_param_count", n, cout, k, stride, C, H, W, F, &p) ? -1 : p.total;
+}
+
+int64_t smi_stem_act_floats(int64_t rows, int n, const int* cout, const int* k, const int* stride,
+                            int C, int H, int W, int F) {
+  StemPlan p;
+  if (rows < 0) { set_error(SMI_E_ARG, "stem_act_floats: negative rows"); return -1; }
+  return stem_args("stem_act_floats", n, cout, k, stride, C, H, W, F, &p) ? -1
+                                                                         : stem_act_floats(p, rows);
+}
+
+int64_t smi_stem_scratch_bytes(int64_t rows, int n, const int* cout, const int* k, const int* stride,
+                               int C, int H, int W, int F) {
+  StemPlan p;
+  if (rows < 0) { set_error(SMI_E_ARG, "stem_scratch_bytes: negative rows"); return -1; }
+  return stem_args("stem_scratch_bytes", n, cout, k, stride, C, H, W, F, &p)
+             ? -1 : stem_scratch_bytes(p, rows);
+}
+
+int smi_stem_fused(int n, const int* cout, const int* k, const int* stride, int C, int H, int W,
+                   int F) {
+  StemPlan p;
+  RC_CHECK(stem_args("stem_fused", n, cout, k, stride, C, H, W, F, &p));
+  return p.fused ? 1 : 0;
+}
+
+int smi_stem_forward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
+                     int64_t T, int64_t rows, int n, const int* cout, const int* k,
+                     const int* stride, int C, int H, int W, int F, float* act, void* scratch,
+                     int64_t scratch_bytes, float* feat, int64_t ldf, const int* skip,
+                     void* stream) {
+  StemPlan p;
+  RC_CHECK(stem_args("stem_forward", n, cout, k, stride, C, H, W, F, &p));
+  REQUIRE(params && pix && feat && B >= 1 && T >= 1 && rows >= 0 && rows <= INT32_MAX && ldf >= F,
+          "stem_forward: null pointer, B or T below 1, rows outside [0, 2^31) or ldf < F");
+  REQUIRE(rows <= B * T || pix_next, "stem_forward: rows beyond B*T need pix_next");
+  if (rows == 0) return SMI_OK;
+  float* A[kStemMaxLayers] = {nullptr, nullptr, nullptr, nullptr};
+  if (act) {
+    for (int i = 0; i < p.n; ++i) A[i] = act + stem_act_off(p, rows, i);
+  } else {
+    REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 3) == 0 &&
+            scratch_bytes >= 4 * stem_fwd_scratch_floats(p, rows),
+            "stem_forward: without an activation buffer the intermediates need scratch "
+            "(smi_stem_scratch_bytes)");
+    float* s = static_cast<float*>(scratch);
+    if (p.fused) A[1] = s;
+    else for (int i = 0; i < p.n; ++i) A[i] = s + stem_act_off(p, rows, i);
+  }
+  const PixRows pr{pix, pix_next, B, T, p.img};
+  return stem_forward(p, params, pr, rows, A, feat, ldf, SMI_STREAM(stream), skip);
+}
+
+int smi_stem_backward(const float* params, const uint8_t* pix, const uint8_t* pix_next, int64_t B,
+                      int64_t T, int64_t rows, int n, const int* cout, const int* k,
+                      const int* stride, int C, int H, int W, int F, const float* act,
+                      const float* dz, int64_t lddz, float* grad, void* scratch,
+                      int64_t scratch_bytes, const int* skip, void* stream) {
+  StemPlan p;
+  RC_CHECK(stem_args("stem_backward", n, cout, k, stride, C, H, W, F, &p));
+  REQUIRE(params && pix && act && dz && grad && B >= 1 && T >= 1 && rows >= 0 && rows <= INT32_MAX &&
+          lddz >= F,
+          "stem_backward: null pointer, B or T below 1, rows outside [0, 2^31) or lddz < F");
+  REQUIRE(rows <= B * T || pix_next, "stem_backward: rows beyond B*T need pix_next");
+  if (rows == 0) return SMI_OK;
+  const StemScratch sc = stem_scratch(p, rows);
+  REQUIRE(scratch && (reinterpret_cast<uintptr_t>(scratch) & 3) == 0 && scratch_bytes >= 4 * sc.total,
+          "stem_backward: scratch missing, misaligned or smaller than smi_stem_scratch_bytes");
+  float* s = static_cast<float*>(scratch);
+  const float* A[kStemMaxLayers] = {nullptr, nullptr, nullptr, nullptr};
+  float* dA[kStemMaxLayers] = {nullptr, nullptr, nullptr, nullptr};
+  for (int i = 0; i < p.n; ++i) {
+    A[i] = act + stem_act_off(p, rows, i);
+    if (sc.dA[i] >= 0) dA[i] = s + sc.dA[i];
+  }
+  const PixRows pr{pix, pix_next, B, T, p.img};
+  return stem_backward(p, params, pr, rows, A, dz, lddz, grad, dA, s + sc.part, SMI_STREAM(stream),
+                       skip);
+}
+
 int smi_ppo_rnn_phase(const smi_ppo_rnn_args* a, int phase, int epoch, void* stream) {
   REQUIRE(a, "ppo_rnn: null args");
   REQUIRE(a->rnn_layer >= 0 && a->rnn_layer <= 3 && (a->rnn_layer <= 1 || a->rnn_hidden > 0),
@@ -904,6 +1013,10 @@ int smi_ppo_rnn_phase(const smi_ppo_rnn_args* a, int phase, int epoch, void* str
           "ppo_rnn: obs_dim must be in [1, 128] ([0, 128] with a pixel stem)");
   REQUIRE(a->cnn_feat <= 0 || (a->pixels && a->pixels_next),
           "ppo_rnn: pixel stem needs pixels and pixels_next");
+  if (a->cnn_feat > 0) {
+    const int bad = stem_check(stem_spec_default(a->cnn_feat), a->pix_c, a->pix_h, a->pix_w);
+    if (bad) return stem_spec_error("ppo_rnn", bad);
+  }
   REQUIRE(!(a->use_zf && a->obs_dim == 0), "ppo_rnn: z-filter needs low-dim observations");
   REQUIRE(a->rnn_hidden >= 0 && a->rnn_hidden <= 256,
           "ppo_rnn: rnn_hidden must be in [0, 256] (0: MLP policy over the stem input)");

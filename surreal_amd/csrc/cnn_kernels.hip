@@ -32,13 +32,6 @@ __device__ __forceinline__ float u8f(unsigned u, int byte) {
   return (float)((u >> (8 * byte)) & 0xffu);
 }
 
-__device__ __forceinline__ const unsigned char* pix_of(const PixRows& pr, int64_t n) {
-  const int64_t t = n / pr.B, b = n - t * pr.B;
-  return t < pr.T ? pr.pix + (b * pr.T + t) * pr.img_bytes : pr.pix_next + b * pr.img_bytes;
-}
-
-__host__ __device__ inline int64_t lds_img_bytes(const CnnGeom& g) { return (g.img + 15) & ~(int64_t)15; }
-
 // ------------------------------------------------------------------ forward
 // One workgroup (4 waves) per image, grid-stride over images.
 //   conv1: implicit GEMM M = P1 pixels, N = 16 channels, K = 64*C; wave w owns
@@ -400,31 +393,15 @@ cnn_bwd_kernel(const float* __restrict__ prm, PixRows pr, int H, int W, int64_t 
 
 // ------------------------------------------------------------------- host
 static int cnn_check(const CnnGeom& g) {
-  if (g.C != 3 && g.C != 9)
-    return set_error(SMI_E_ARG, "cnn: 3 (one RGB frame) or 9 (three stacked RGB frames) channels");
-  if (g.H1 < 4 || g.W1 < 4 || g.H2 < 1 || g.W2 < 1)
-    return set_error(SMI_E_ARG, "cnn: image smaller than the two convolutions");
-  if ((g.P2 + 15) / 16 > 6)
-    return set_error(SMI_E_ARG, "cnn: conv-2 output larger than 96 pixels (84x84 gives 81)");
-  if (g.W % 4 != 0 || g.img % 16 != 0 || g.P1 % 4 != 0 || g.W1 % 2 != 0 || g.flat % 4 != 0)
-    return set_error(SMI_E_ARG, "cnn: need W % 4 == 0, C*H*W % 16 == 0, even conv-1 width, "
-                                "conv-1 pixels % 4 == 0 (84x84 qualifies)");
-  if (g.F < 1) return set_error(SMI_E_ARG, "cnn: feature dim must be >= 1");
-  return SMI_OK;
+  const char* why = cnn_check_msg(g);                  // smi_shapes.hpp
+  return why ? set_error(SMI_E_ARG, why) : SMI_OK;
 }
-
-static size_t cnn_fwd_lds(const CnnGeom& g) { return (size_t)lds_img_bytes(g) + (size_t)64 * g.P1; }
-static size_t cnn_bwd_lds(const CnnGeom& g) {
-  return (size_t)lds_img_bytes(g) + (size_t)64 * g.P1 + 4 * (size_t)round4(g.flat) + 4 * kWG +
-         4 * (size_t)(g.P1 + g.P2);
-}
-
 
 int cnn_forward(const float* prm, const PixRows& pr, int C, int H, int W, int F, int64_t rows,
                 float* A1, float* A2, float* feat, int64_t ldf, hipStream_t st, const int* skip) {
   const CnnGeom g = cnn_geom(C, H, W, F);
   RC_CHECK(cnn_check(g));
-  const size_t lds = cnn_fwd_lds(g);
+  const size_t lds = (size_t)cnn_fwd_lds(g);
   if (lds > (size_t)kCuLdsBytes)
     return set_error(SMI_E_ARG, "cnn: the frame's image and conv-1 activation exceed the LDS of a CU");
   if (rows < 1) return SMI_OK;
@@ -447,7 +424,7 @@ int cnn_backward(const float* prm, const PixRows& pr, int C, int H, int W, int F
                  float* dA2, float* part, hipStream_t st, const int* skip) {
   const CnnGeom g = cnn_geom(C, H, W, F);
   RC_CHECK(cnn_check(g));
-  const size_t lds = cnn_bwd_lds(g);
+  const size_t lds = (size_t)cnn_bwd_lds(g);
   if (lds > (size_t)kCuLdsBytes)
     return set_error(SMI_E_ARG, "cnn: the frame's backward staging exceeds the LDS of a CU");
   if (rows < 1) return SMI_OK;

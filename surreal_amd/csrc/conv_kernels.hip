@@ -91,10 +91,17 @@ __device__ __forceinline__ void kpos_step4(KPos& q, int ny, int nx) {
 // staging maps: A (weights) element j of thread tid: VW ? row (tid >> 3) + 32 (j >> 2),
 // z 4 (tid & 7) + (j & 3) : row (tid >> 5) + 8 j, z tid & 31;  B (patches): row
 // tid & 63 (the thread's output pixel), z (tid >> 6) + 4 j (uniform in a wave)
-template <typename T, bool VW>
+//
+// ROWS (uint8 input only): image nn is not at x + nn cin h w but where the
+// learners' time-major row map puts it (pix_of: pix[b][t] | pix_next[b], 64-bit
+// bases, element alignment); the base is all that changes.
+// skip: device stop flag, read once per workgroup before any other load.
+template <typename T, bool VW, bool ROWS>
 __global__ void __launch_bounds__(kWG)
 conv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wgt, const float* __restrict__ bias,
-                float* __restrict__ y, ConvGeom g, int64_t n, int act, int div255) {
+                float* __restrict__ y, ConvGeom g, int64_t n, int act, int div255, PixRows pr,
+                const int* skip) {
+  if (skip && skip[0] != 0) return;
   __shared__ __attribute__((aligned(16))) float As[kConvTile * LD];
   __shared__ __attribute__((aligned(16))) float Bs[kConvTile * LD];
   const int tid = threadIdx.x, l = tid & 63;
@@ -114,7 +121,9 @@ conv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wgt, const fl
     const int pp = qok ? (int)(q - nn * g.P) : 0;
     const int oy = pp / g.wo, ox = pp - oy * g.wo;
     const int iy0 = oy * g.s - g.p, ix0 = ox * g.s - g.p;
-    const T* xb = x + nn * (int64_t)g.cin * HW;
+    const T* xb;
+    if constexpr (ROWS) xb = pix_of(pr, nn);
+    else xb = x + nn * (int64_t)g.cin * HW;
     KPos kp;
     kp.c = w / kk2;
     kp.y = (w - kp.c * kk2) / g.k;
@@ -205,7 +214,9 @@ conv_fwd_kernel(const T* __restrict__ x, const float* __restrict__ wgt, const fl
 // of the class), z (tid >> 6) + 4 j = (co, ay, ax), uniform in a wave
 __global__ void __launch_bounds__(kWG)
 conv_dx_kernel(const float* __restrict__ dy, const float* __restrict__ wgt,
-               const float* __restrict__ mask, float* __restrict__ dx, ConvGeom g, int64_t n) {
+               const float* __restrict__ mask, float* __restrict__ dx, ConvGeom g, int64_t n,
+               const int* skip) {
+  if (skip && skip[0] != 0) return;
   __shared__ __attribute__((aligned(16))) float As[kConvTile * LD];
   __shared__ __attribute__((aligned(16))) float Bs[kConvTile * LD];
   const int tid = threadIdx.x, l = tid & 63;
@@ -302,10 +313,12 @@ conv_dx_kernel(const float* __restrict__ dy, const float* __restrict__ wgt,
 // blockIdx.x = tile of dW [cout][K] (row tile fastest), blockIdx.y = split.
 // Staging maps: both operands row (tid >> 5) + 8 j, pixel (z) tid & 31: the
 // thread's 8 patch columns are fixed for the whole kernel, its pixel moves.
-template <typename T>
+// ROWS, skip: as in conv_fwd_kernel.
+template <typename T, bool ROWS>
 __global__ void __launch_bounds__(kWG)
 conv_dw_kernel(const float* __restrict__ dy, const T* __restrict__ x, float* __restrict__ part,
-               ConvGeom g, int64_t n, ConvDwPlan pl) {
+               ConvGeom g, int64_t n, ConvDwPlan pl, PixRows pr, const int* skip) {
+  if (skip && skip[0] != 0) return;
   __shared__ __attribute__((aligned(16))) float As[kConvTile * LD];
   __shared__ __attribute__((aligned(16))) float Bs[kConvTile * LD];
   const int tid = threadIdx.x, l = tid & 63;
@@ -335,7 +348,9 @@ conv_dw_kernel(const float* __restrict__ dy, const T* __restrict__ x, float* __r
     const int oy = pp / g.wo, ox = pp - oy * g.wo;
     const int iy0 = oy * g.s - g.p, ix0 = ox * g.s - g.p;
     const float* dyb = dy + nn * (int64_t)g.cout * g.P + pp;
-    const T* xb = x + nn * (int64_t)g.cin * HW + iy0 * g.w + ix0;
+    const T* xb;
+    if constexpr (ROWS) xb = pix_of(pr, nn) + iy0 * g.w + ix0;
+    else xb = x + nn * (int64_t)g.cin * HW + iy0 * g.w + ix0;
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       const int co = r0 + (tid >> 5) + 8 * j;
@@ -394,7 +409,8 @@ conv_dw_kernel(const float* __restrict__ dy, const T* __restrict__ x, float* __r
 // 256 partials), then the four wave sums are added 0 + 1 + 2 + 3.
 __global__ void __launch_bounds__(kWG)
 conv_dw_reduce(const float* __restrict__ part, int splits, int64_t slab, int64_t nw,
-               float* __restrict__ dw, float* __restrict__ db, int div255) {
+               float* __restrict__ dw, float* __restrict__ db, int div255, const int* skip) {
+  if (skip && skip[0] != 0) return;
   __shared__ float red[kNW][64];
   const int l = threadIdx.x & 63, w = threadIdx.x >> 6;
   for (int64_t i0 = (int64_t)blockIdx.x * 64; i0 < slab; i0 += (int64_t)gridDim.x * 64) {
@@ -414,56 +430,66 @@ conv_dw_reduce(const float* __restrict__ part, int splits, int64_t slab, int64_t
 }
 
 // ------------------------------------------------------------------- host
+// rows (non-null: x is ignored, the uint8 images are those of the row map) and
+// skip are the kernels' ROWS form and stop flag
 int conv2d_forward(const void* x, int x_u8, int div255, int64_t n, const ConvGeom& g,
-                   const float* wgt, const float* bias, int act, float* y, hipStream_t st) {
+                   const float* wgt, const float* bias, int act, float* y, hipStream_t st,
+                   const int* skip, const PixRows* rows) {
   if (n < 1) return SMI_OK;
   const bool vw = g.K % 4 == 0 && (reinterpret_cast<uintptr_t>(wgt) & 15) == 0;
   const int64_t tiles = conv_fwd_tiles(g, n);
   const double flops = 2.0 * (double)n * g.P * g.K * g.cout;
+  const PixRows pr = rows ? *rows : PixRows{nullptr, nullptr, 1, 1, 0};
   const int kt = ktime_begin(st);
-#define SMI_CONV_FWD(T, VW)                                                                      \
+#define SMI_CONV_FWD(T, VW, ROWS)                                                                \
   do {                                                                                           \
-    auto k = conv_fwd_kernel<T, VW>;                                                             \
+    auto k = conv_fwd_kernel<T, VW, ROWS>;                                                       \
     const int64_t rg = resident_grid(k, kWG, 0);                                                 \
     hipLaunchKernelGGL(k, dim3((unsigned)(tiles < rg ? tiles : rg)), dim3(kWG), 0, st,           \
-                       static_cast<const T*>(x), wgt, bias, y, g, n, act, div255);               \
+                       static_cast<const T*>(x), wgt, bias, y, g, n, act, div255, pr, skip);     \
   } while (0)
-  if (x_u8) { if (vw) SMI_CONV_FWD(unsigned char, true); else SMI_CONV_FWD(unsigned char, false); }
-  else { if (vw) SMI_CONV_FWD(float, true); else SMI_CONV_FWD(float, false); }
+  if (rows) { if (vw) SMI_CONV_FWD(unsigned char, true, true); else SMI_CONV_FWD(unsigned char, false, true); }
+  else if (x_u8) { if (vw) SMI_CONV_FWD(unsigned char, true, false); else SMI_CONV_FWD(unsigned char, false, false); }
+  else { if (vw) SMI_CONV_FWD(float, true, false); else SMI_CONV_FWD(float, false, false); }
 #undef SMI_CONV_FWD
   ktime_end(kt, KT_CNN_FWD, flops, st);
   return check_launch("conv_fwd_kernel");
 }
 
 int conv2d_backward_input(const float* dy, int64_t n, const ConvGeom& g, const float* wgt,
-                          const float* mask, float* dx, hipStream_t st) {
+                          const float* mask, float* dx, hipStream_t st, const int* skip) {
   if (n < 1) return SMI_OK;
   const int64_t tiles = conv_dx_max_tiles(g, n);
   const int64_t rg = resident_grid(conv_dx_kernel, kWG, 0);
   const int64_t per = (rg + g.s * g.s - 1) / (g.s * g.s);          // resident workgroups per class
   const int kt = ktime_begin(st);
   hipLaunchKernelGGL(conv_dx_kernel, dim3((unsigned)(tiles < per ? tiles : per), g.s * g.s), dim3(kWG),
-                     0, st, dy, wgt, mask, dx, g, n);
+                     0, st, dy, wgt, mask, dx, g, n, skip);
   ktime_end(kt, KT_CNN_BWD, 2.0 * (double)n * g.P * g.K * g.cout, st);
   return check_launch("conv_dx_kernel");
 }
 
 int conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
-                           const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st) {
+                           const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st,
+                           const int* skip, const PixRows* rows) {
   if (n < 1) return SMI_OK;
   const ConvDwPlan pl = conv_dw_plan(g, n);
+  const PixRows pr = rows ? *rows : PixRows{nullptr, nullptr, 1, 1, 0};
   const int kt = ktime_begin(st);
-  if (x_u8)
-    hipLaunchKernelGGL(conv_dw_kernel<unsigned char>, dim3(pl.tiles, pl.splits), dim3(kWG), 0, st, dy,
-                       static_cast<const unsigned char*>(x), part, g, n, pl);
+  if (rows)
+    hipLaunchKernelGGL((conv_dw_kernel<unsigned char, true>), dim3(pl.tiles, pl.splits), dim3(kWG), 0,
+                       st, dy, static_cast<const unsigned char*>(nullptr), part, g, n, pl, pr, skip);
+  else if (x_u8)
+    hipLaunchKernelGGL((conv_dw_kernel<unsigned char, false>), dim3(pl.tiles, pl.splits), dim3(kWG), 0,
+                       st, dy, static_cast<const unsigned char*>(x), part, g, n, pl, pr, skip);
   else
-    hipLaunchKernelGGL(conv_dw_kernel<float>, dim3(pl.tiles, pl.splits), dim3(kWG), 0, st, dy,
-                       static_cast<const float*>(x), part, g, n, pl);
+    hipLaunchKernelGGL((conv_dw_kernel<float, false>), dim3(pl.tiles, pl.splits), dim3(kWG), 0, st, dy,
+                       static_cast<const float*>(x), part, g, n, pl, pr, skip);
   ktime_end(kt, KT_CNN_BWD, 2.0 * (double)n * g.P * g.K * g.cout, st);
   RC_CHECK(check_launch("conv_dw_kernel"));
   const int64_t nb = (pl.slab + 63) / 64;
   hipLaunchKernelGGL(conv_dw_reduce, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(kWG), 0, st, part,
-                     pl.splits, pl.slab, (int64_t)g.cout * g.K, dw, db, div255);
+                     pl.splits, pl.slab, (int64_t)g.cout * g.K, dw, db, div255, skip);
   return check_launch("conv_dw_reduce");
 }
 

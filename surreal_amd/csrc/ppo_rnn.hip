@@ -218,15 +218,17 @@ static int cnn_features(const smi_ppo_rnn_args& a, const RnnDims& d, const float
                         float* X, float* A1, const RnnScratch& s, hipStream_t st,
                         const int* skip) {
   if (d.F == 0) return SMI_OK;
-  return cnn_forward(cnn, pix_rows(a, d), d.G.C, d.G.H, d.G.W, d.F, (int64_t)S * d.B, A1, s.A2,
-                     X + d.D, d.ldx, st, skip);
+  // (the general stem keeps A1 in memory whether or not a backward follows)
+  float* A[kStemMaxLayers] = {A1 || d.px_fused ? A1 : s.A1, s.A2, nullptr, nullptr};
+  return stem_forward(d.SP, cnn, pix_rows(a, d), (int64_t)S * d.B, A, X + d.D, d.ldx, st, skip);
 }
 
 // CNN backward from dF = dL/d(features) * relu'(features) in s.dF
 static int cnn_bwd_from_dF(const smi_ppo_rnn_args& a, const RnnDims& d, const float* cnn,
                            float* Gc, const RnnScratch& s, hipStream_t st, const int* skip) {
-  return cnn_backward(cnn, pix_rows(a, d), d.G.C, d.G.H, d.G.W, d.F, d.NE, s.A1, s.A2, s.dF, d.F,
-                      Gc, s.dA2, s.cpart, st, skip);
+  const float* A[kStemMaxLayers] = {s.A1, s.A2, nullptr, nullptr};
+  float* dA[kStemMaxLayers] = {s.dA1, s.dA2, nullptr, nullptr};
+  return stem_backward(d.SP, cnn, pix_rows(a, d), d.NE, A, s.dF, d.F, Gc, dA, s.cpart, st, skip);
 }
 
 // pixel-stem gradient (into Gc) from the LSTM gate gradients of the E steps:
@@ -517,6 +519,7 @@ static int phase_prep(const Ctx& c, const Rules& r) {
   // may have run its input transpose and recurrence (gae_prep_dual).
   RnnScratch sp = s;
   sp.xproj = s.xprojR; sp.hbuf = s.hbufR; sp.HA1 = s.HA1R; sp.HA2 = s.HA2R; sp.A2 = s.A2R;
+  sp.A1 = s.A1R;
   const float* X = s.Xr;
   if (!r.gae_prep_dual()) {   // (else the GAE phase ran this input and recurrence)
     RC_CHECK(launch_zf_tmajor(a.obs, a.obs_next, d.B, d.T, d.E, d.D, a.use_zf, a.rzf_sum,

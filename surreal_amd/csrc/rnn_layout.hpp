@@ -3,6 +3,7 @@
 // runtime calls, so tests/rnn_layout_main.cpp sweeps it on the CPU.
 #pragma once
 #include "smi_shapes.hpp"
+#include "stem_plan.hpp"
 
 namespace smi {
 
@@ -19,6 +20,11 @@ struct RnnDims {
   int64_t nA_head, nC_head, nL, nCnn, nS;   // parameter counts; stem = [lstm | cnn]
   MlpLayout LA, LC;
   CnnGeom G;
+  // the stem behind G (the reference's default layers, ppo_net.py:139 passes
+  // none) and the implementation it runs on this camera: the fused kernels, or
+  // the general layers (stem_plan.hpp); px_ok: a stem the library accepts
+  StemPlan SP;
+  bool px_ok, px_fused;
 };
 
 inline RnnDims rnn_dims(int B, int T, int Hz, int D, int H, int h1, int h2, int A, int c1, int c2,
@@ -28,6 +34,10 @@ inline RnnDims rnn_dims(int B, int T, int Hz, int D, int H, int h1, int h2, int 
   d.F = F > 0 ? F : 0; d.Din = D + d.F;
   d.G = cnn_geom(pc, ph, pw, d.F);
   d.nCnn = d.F > 0 ? d.G.total : 0;
+  d.SP = StemPlan{};
+  d.px_ok = d.F > 0 && stem_check(stem_spec_default(d.F), pc, ph, pw) == 0;
+  if (d.px_ok) d.SP = stem_plan(stem_spec_default(d.F), pc, ph, pw);
+  d.px_fused = d.px_ok && d.SP.fused;
   d.B = B; d.T = T; d.Hz = Hz; d.E = T - Hz + 1; d.S1 = T + 1; d.D = D; d.H = H; d.G4 = 4 * H;
   d.A = A; d.h1 = h1; d.h2 = h2; d.c1 = c1; d.c2 = c2;
   d.NE = (int64_t)d.E * B; d.NG = (int64_t)d.S1 * B;
@@ -61,6 +71,9 @@ struct RnnScratch {
   // ret_tm[n] the window return
   float *rowin, *ret_tm;
   float *A1, *A2, *dA2, *dF, *cpart;        // pixel stem (empty without one)
+  // the general stem's own regions (empty where the fused one runs): its
+  // forward keeps A1 in memory (the PREP phase's copy) and its backward dA1
+  float *A1R, *dA1;
   double *part, *gaepart;
   int* ci; float* cf;
   // the transposed image of LSTM layer 0's weights, [W_ihT [Din][4H] | W_hhT [H][4H]
@@ -122,13 +135,16 @@ inline RnnScratch rnn_scratch(const RnnDims& d, void* base) {
   s.ret_tm = take(d.NE);
   s.lvpart = take((int64_t)4096 * d.A);
   const bool px = d.F > 0;
-  s.A1 = take(px ? d.NE * 16 * d.G.P1 : 0);
+  // general stem: also the S1-step forward of the GAE pass writes A1
+  const bool gen = px && d.px_ok && !d.px_fused;
+  s.A1 = take(px ? (gen ? d.NG : d.NE) * 16 * d.G.P1 : 0);
   s.A2 = take(px ? d.NG * d.G.flat : 0);
   s.xprojR = take(d.NE * d.G4);
   s.hbufR = take((int64_t)d.L * (d.S1 + 1) * d.B * d.H);
   s.HA1R = take(d.NE * hmax1);
   s.HA2R = take(d.NE * hmax2);
   s.A2R = take(px ? d.NE * d.G.flat : 0);
+  s.A1R = take(gen ? d.NE * 16 * d.G.P1 : 0);
   {
     const int64_t wa = (int64_t)d.Hin * d.h1 + (int64_t)d.h1 * d.h2;
     const int64_t wc = (int64_t)d.Hin * d.c1 + (int64_t)d.c1 * d.c2;
@@ -136,7 +152,10 @@ inline RnnScratch rnn_scratch(const RnnDims& d, void* base) {
   }
   s.dA2 = take(px ? d.NE * d.G.flat : 0);
   s.dF = take(px ? d.NE * d.F : 0);
-  s.cpart = take(px ? (int64_t)cnn_bwd_grid(d.NE) * d.G.nconv : 0);
+  s.dA1 = take(gen ? d.NE * 16 * d.G.P1 : 0);
+  // conv weight-gradient partials: the fused backward's slabs, or the general
+  // layers' shared region (stem_part_floats)
+  s.cpart = take(px ? (gen ? stem_part_floats(d.SP, d.NE) : (int64_t)cnn_bwd_grid(d.NE) * d.G.nconv) : 0);
   s.part = reinterpret_cast<double*>(take(2 * part_doubles(d)));   // >= 65536 doubles
   s.gaepart = reinterpret_cast<double*>(take(2 * 2 * 2048));
   s.ci = reinterpret_cast<int*>(take(CI_COUNT));

@@ -94,6 +94,12 @@ constexpr int fault() { return SMI_FAULT_NONE; }
 // ---- pixel stem (CnnGeom, cnn_geom, cnn_bwd_grid: smi_shapes.hpp) ------------
 // image of activation row n = t*B + b: t < T -> pix[b][t], else pix_next[b]
 struct PixRows { const unsigned char* pix; const unsigned char* pix_next; int64_t B, T, img_bytes; };
+#ifdef __HIPCC__
+__device__ __forceinline__ const unsigned char* pix_of(const PixRows& pr, int64_t n) {
+  const int64_t t = n / pr.B, b = n - t * pr.B;
+  return t < pr.T ? pr.pix + (b * pr.T + t) * pr.img_bytes : pr.pix_next + b * pr.img_bytes;
+}
+#endif
 int cnn_forward(const float* prm, const PixRows& pr, int C, int H, int W, int F, int64_t rows,
                 float* A1, float* A2, float* feat, int64_t ldf, hipStream_t st, const int* skip);
 // dz: gradient at the Linear pre-activation (ReLU mask applied), rows x F

@@ -11,6 +11,8 @@ namespace smi {
 struct PolRowArgs;     // pol_rows.hpp
 struct LstmFwdArgs;    // lstm_cell.hpp
 struct ConvGeom;       // conv_plan.hpp
+struct PixRows;        // smi_internal.hpp
+struct StemPlan;       // stem_plan.hpp
 
 // ---- ops_kernels.hip
 int launch_zfilter_apply(const float* x, float* out, int64_t rows, int dim, const float* s,
@@ -75,13 +77,30 @@ int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
 int launch_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t vs, int64_t rows,
                       int A, int dueling, int32_t* out, hipStream_t st);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
+// skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
+// rows: the uint8 images come through the learners' time-major row map
+// (row n = t B + b: pix[b][t] | pix_next[b]) and x is ignored.
 int conv2d_forward(const void* x, int x_u8, int div255, int64_t n, const ConvGeom& g,
-                   const float* wgt, const float* bias, int act, float* y, hipStream_t st);
+                   const float* wgt, const float* bias, int act, float* y, hipStream_t st,
+                   const int* skip = nullptr, const PixRows* rows = nullptr);
 int conv2d_backward_input(const float* dy, int64_t n, const ConvGeom& g, const float* wgt,
-                          const float* mask, float* dx, hipStream_t st);
+                          const float* mask, float* dx, hipStream_t st, const int* skip = nullptr);
 // part: conv_scratch_bytes(g, n) of scratch, written before it is read
 int conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
-                           const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st);
+                           const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st,
+                           const int* skip = nullptr, const PixRows* rows = nullptr);
+// ---- stem.hip (the pixel stem of free shape: fused or general, stem_plan.hpp)
+// A[i]: activation of layer i, [rows][act[i]] (the fused form takes A[0] == NULL
+// when no backward follows); feat [rows][F] at ldf
+int stem_forward(const StemPlan& p, const float* prm, const PixRows& pr, int64_t rows,
+                 float* const* A, float* feat, int64_t ldf, hipStream_t st, const int* skip);
+// dz: gradient at the Linear pre-activation (ReLU mask applied), rows x F at
+// lddz; writes the whole gradient (not accumulated) into grad in the planner's
+// layout; dA[i] ([rows][act[i]]; the fused form reads dA[n - 1] alone) and part
+// (stem_part_floats) are scratch, written before they are read
+int stem_backward(const StemPlan& p, const float* prm, const PixRows& pr, int64_t rows,
+                  const float* const* A, const float* dz, int64_t lddz, float* grad,
+                  float* const* dA, float* part, hipStream_t st, const int* skip);
 // ---- linear_kernels.hip
 int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,

@@ -84,6 +84,26 @@ SMI_HD inline CnnGeom cnn_geom(int C, int H, int W, int F) {
 constexpr int kCnnPartials = 512;               // max workgroups (partial slabs) of the backward
 inline int cnn_bwd_grid(int64_t rows) { return (int)(rows < kCnnPartials ? rows : kCnnPartials); }
 constexpr int kCnnThreads = 256;                // threads of a stem workgroup (== kWG)
+// what the fused kernels (cnn_kernels.hip) ask of a frame: nullptr, or the
+// reason they refuse it
+inline const char* cnn_check_msg(const CnnGeom& g) {
+  if (g.C != 3 && g.C != 9) return "cnn: 3 (one RGB frame) or 9 (three stacked RGB frames) channels";
+  if (g.H1 < 4 || g.W1 < 4 || g.H2 < 1 || g.W2 < 1) return "cnn: image smaller than the two convolutions";
+  if ((g.P2 + 15) / 16 > 6) return "cnn: conv-2 output larger than 96 pixels (84x84 gives 81)";
+  if (g.W % 4 != 0 || g.img % 16 != 0 || g.P1 % 4 != 0 || g.W1 % 2 != 0 || g.flat % 4 != 0)
+    return "cnn: need W % 4 == 0, C*H*W % 16 == 0, even conv-1 width, "
+           "conv-1 pixels % 4 == 0 (84x84 qualifies)";
+  if (g.F < 1) return "cnn: feature dim must be >= 1";
+  return nullptr;
+}
+// dynamic LDS of the fused forward / backward: the 16-byte-aligned image and A1;
+// + dA2, the reduction space and the two pixel-offset tables
+SMI_HD inline int64_t lds_img_bytes(const CnnGeom& g) { return (g.img + 15) & ~(int64_t)15; }
+inline int64_t cnn_fwd_lds(const CnnGeom& g) { return lds_img_bytes(g) + (int64_t)64 * g.P1; }
+inline int64_t cnn_bwd_lds(const CnnGeom& g) {
+  return lds_img_bytes(g) + (int64_t)64 * g.P1 + 4 * (int64_t)round4(g.flat) + 4 * kCnnThreads +
+         4 * (int64_t)(g.P1 + g.P2);
+}
 // per-thread 16-byte chunk counts of an 84 x 84 frame's staging (image, A1,
 // dA2), register arrays of the forward's batched image loads and the
 // backward's next-image prefetch (larger frames: a tail loop / prefetch off)

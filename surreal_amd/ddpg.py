@@ -137,7 +137,9 @@ class DDPGModel(nn.Module):
             self.cnn_dim = int(conv_hidden_dim if conv_hidden_dim is not None else 200)
             self.perception = CNNStemNetwork(
                 obs_spec['pixel']['camera0'], self.cnn_dim,
-                conv_out_channels or (16, 32), conv_kernel_sizes or (8, 4), conv_strides or (4, 2),
+                (16, 32) if conv_out_channels is None else conv_out_channels,
+                (8, 4) if conv_kernel_sizes is None else conv_kernel_sizes,
+                (4, 2) if conv_strides is None else conv_strides,
                 device=self.device, generator=generator)
         # concatenated perception: [cnn features | low_dim] (ddpg_net.py:69-79)
         self.input_dim = self.cnn_dim + self.low_dim
@@ -210,20 +212,29 @@ class _Net(LaunchNet):
                p(self.bufs[tag + '_mu']), p(self.bufs[tag + '_rs']), p(ln.weight), rows, ln.n, 1,
                p(dx), dx.stride(0), p(dg), p(db), self.st)
 
+    def stem_scratch(self, cnn, rows):
+        """(bytes, buffer) of the stem's scratch (one size serves forward and
+        backward; every launch on this net's stream writes it before reading)"""
+        nb = int(L.lib().smi_stem_scratch_bytes(rows, *cnn.spec_args()))
+        if nb < 0:
+            L.check(-1, 'smi_stem_scratch_bytes')
+        return nb, self.buf('cnn_scratch', (max((nb + 3) // 4, 1),))
+
     def perception_fwd(self, model, pix, low, rows, store, keep=False):
         """[cnn(pix / 255) | low] (ddpg_net.py:69-79) into buffer store_P; keep:
-        the conv activations stay for a backward (store_A1 / store_A2)"""
+        every layer's activation stays for a backward (store_A)"""
         cnn = model.perception
-        C, H, W = cnn.D_obs
         F, D = model.cnn_dim, model.low_dim
         pre = store or 'ptmp'
         P = self.buf(pre + '_P', (rows, F + D))
-        A1 = self.buf(pre + '_A1', (rows, 16 * ((H - 8) // 4 + 1) * ((W - 8) // 4 + 1))) if keep else None
-        A2 = self.buf(pre + '_A2', (rows, cnn.flat_dim))
         if pix.dtype != torch.uint8:
             raise TypeError('DDPG camera observations must be uint8 (scaled by 1/255 in the kernel)')
-        L.call('smi_cnn_forward', p(cnn.flat), p(pix), None, rows, 1, rows, C, H, W, F,
-               p(A1) if A1 is not None else None, p(A2), p(P), F + D, self.st)
+        spec = cnn.spec_args()
+        # every layer's activation for a backward; else the intermediates in scratch
+        A = self.buf(pre + '_A', (rows * sum(cnn.act_dims),)) if keep else None
+        nb, scratch = self.stem_scratch(cnn, rows)
+        L.call('smi_stem_forward', p(cnn.flat), p(pix), None, rows, 1, rows, *spec,
+               p(A) if A is not None else None, p(scratch), nb, p(P), F + D, None, self.st)
         if D:
             L.call('smi_copy_cols', p(low), low.stride(0), rows, D, p(P[:, F:]), F + D, self.st)
         return P
@@ -232,17 +243,14 @@ class _Net(LaunchNet):
         """the critic's first-layer input gradient over the cnn columns, masked by
         the FC ReLU, back through the CNN stem into grad (its flat layout)"""
         cnn = model.perception
-        C, H, W = cnn.D_obs
         F, D = model.cnn_dim, model.low_dim
         P = self.bufs[store + '_P']
         dF = self.buf(store + '_dF', (rows, F))
         L.call('smi_linear_backward_input', p(dH1), c1, rows, c1, p(wo), ldwo, F, p(P), F + D,
                p(dF), F, self.st)
-        nb = int(L.lib().smi_cnn_scratch_bytes(rows, C, H, W, F))
-        scratch = self.buf('cnn_scratch', ((nb + 3) // 4,))
-        L.call('smi_cnn_backward', p(cnn.flat), p(pix), None, rows, 1, rows, C, H, W, F,
-               p(self.bufs[store + '_A1']), p(self.bufs[store + '_A2']), p(dF), F, p(grad),
-               p(scratch), nb, self.st)
+        nb, scratch = self.stem_scratch(cnn, rows)
+        L.call('smi_stem_backward', p(cnn.flat), p(pix), None, rows, 1, rows, *cnn.spec_args(),
+               p(self.bufs[store + '_A']), p(dF), F, p(grad), p(scratch), nb, None, self.st)
 
     def actor_fwd(self, obs, rows, store='a', actor=None):
         actor = actor if actor is not None else self.m.actor

@@ -256,39 +256,105 @@ class _ParamView(_FlatViews):
                 p.copy_(torch.empty(p.shape).uniform_(-bound, bound, generator=generator))
 
 
+STEM_MAX_LAYERS = 4
+
+
+def stem_layer_shapes(D_obs, conv_channels, kernel_sizes, strides):
+    """[(cin, h, w, cout, k, stride, ho, wo)] of the stem's conv layers on a
+    (C, H, W) camera, checked on the host against what smi_stem_* accepts (the
+    ranges of the general layer, include/surreal_mi.h); ConfigError names the
+    layer that is out of range or larger than the frame it receives."""
+    from .config import ConfigError
+    try:
+        C, H, W = (int(v) for v in D_obs)
+    except (TypeError, ValueError):
+        raise ConfigError('pixel stem: the camera shape must be (C, H, W), got {!r}'.format(D_obs))
+    lists = [list(conv_channels), list(kernel_sizes), list(strides)]
+    if len({len(v) for v in lists}) != 1:
+        raise ConfigError('pixel stem: conv_spec out_channels, kernel_sizes and strides must have '
+                          'one length, got {}, {} and {}'.format(*[len(v) for v in lists]))
+    n = len(lists[0])
+    if not 1 <= n <= STEM_MAX_LAYERS:
+        raise ConfigError('pixel stem: conv_spec must hold 1 to {} layers, got {}'.format(
+            STEM_MAX_LAYERS, n))
+    if not (1 <= C <= 128 and 1 <= H <= 16384 and 1 <= W <= 16384):
+        raise ConfigError('pixel stem: layer 1 takes 1 to 128 channels of at most 16384 x 16384 '
+                          'pixels, got camera {}'.format((C, H, W)))
+    out = []
+    c, h, w = C, H, W
+    for i, (co, k, s) in enumerate(zip(*lists)):
+        if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in (co, k, s)):
+            raise ConfigError('pixel stem: layer {} of conv_spec must be integers, got {!r}'.format(
+                i + 1, (co, k, s)))
+        co, k, s = int(co), int(k), int(s)
+        if not (1 <= co <= 128 and 1 <= k <= 8 and 1 <= s <= min(k, 4)):
+            raise ConfigError('pixel stem: layer {} ({}@{}s{}) is outside 1 <= out_channels <= 128, '
+                              '1 <= kernel_size <= 8, 1 <= stride <= min(kernel_size, 4)'.format(
+                                  i + 1, co, k, s))
+        if h < k or w < k:
+            raise ConfigError('pixel stem: layer {} ({}@{}s{}) cannot cover the {} x {} frame it '
+                              'receives (camera {})'.format(i + 1, co, k, s, h, w, (C, H, W)))
+        ho, wo = (h - k) // s + 1, (w - k) // s + 1
+        if c * h * w > 2 ** 31 - 1 or co * ho * wo > 2 ** 31 - 1:
+            raise ConfigError('pixel stem: layer {} ({}@{}s{}): one image of its input or output '
+                              'has 2^31 elements or more'.format(i + 1, co, k, s))
+        out.append((c, h, w, co, k, s, ho, wo))
+        c, h, w = co, ho, wo
+    return out
+
+
 class CNNStemNetwork(nn.Module):
-    """builders.py:8-33: conv 8x8/4 (C->16) -> ReLU -> conv 4x4/2 (16->32) -> ReLU
-    -> Flatten -> Linear(D_out) -> ReLU, over ONE flat device buffer in the C-ABI
-    CNN layout (include/surreal_mi.h, smi_cnn_*).  State-dict keys follow the
-    Sequential positions: model.0 (conv), model.2 (conv), model.5 (linear).
+    """builders.py:8-33: n x [Conv2d(cout_i, k_i, stride_i) -> ReLU] -> Flatten ->
+    Linear(D_out) -> ReLU (the reference default: 16@8s4 -> 32@4s2), over ONE flat
+    device buffer in the C-ABI stem layout (include/surreal_mi.h, smi_stem_*; for
+    the default spec the layout of smi_cnn_*).  Any spec and camera smi_stem_*
+    accepts (1 to 4 unpadded layers inside the general layer's ranges); anything
+    else is a ConfigError naming the layer, raised before a device is touched.
+    State-dict keys follow the Sequential positions: conv i at model.{2i}, the
+    Linear at model.{2n+1} (default: model.0, model.2, model.5).
 
     forward() takes the raw uint8 camera tensor, (N, C, H, W) or (B, S, C, H, W)
-    — the obs/255 of ppo_net.py:368-375 is fused into the conv kernel (bit-equal
-    to torch's uint8 / 255.0).  Inference only; the learner's phases run the
-    backward (smi_ppo_rnn_phase)."""
+    — the obs/255 of ppo_net.py:368-375 is fused into the first conv kernel.
+    Inference only; the learners run the backward (smi_ppo_rnn_phase,
+    smi_stem_backward)."""
 
     def __init__(self, D_obs, D_out, conv_channels=(16, 32), kernel_sizes=(8, 4), strides=(4, 2),
                  device=None, generator=None, flat=None):
         super().__init__()
-        if list(conv_channels) != [16, 32] or list(kernel_sizes) != [8, 4] or list(strides) != [4, 2]:
-            raise NotImplementedError('surreal_amd: CNN stem is built for the reference defaults '
-                                      '(16@8s4, 32@4s2; builders.py:9)')
+        from .config import ConfigError
+        shapes = stem_layer_shapes(D_obs, conv_channels, kernel_sizes, strides)
+        if int(D_out) < 1:
+            raise ConfigError('pixel stem: hidden_output_dim must be >= 1, got {}'.format(D_out))
         C, H, W = (int(v) for v in D_obs)
         self.D_obs, self.D_out = (C, H, W), int(D_out)
-        n = int(L.lib().smi_cnn_param_count(C, H, W, self.D_out))
+        self.conv_channels = tuple(sh[3] for sh in shapes)
+        self.kernel_sizes = tuple(sh[4] for sh in shapes)
+        self.strides = tuple(sh[5] for sh in shapes)
+        # floats of one row of each layer's activation, and the Linear's input width
+        self.act_dims = tuple(sh[3] * sh[6] * sh[7] for sh in shapes)
+        self.flat_dim = self.act_dims[-1]
+        n = sum(sh[3] * sh[0] * sh[4] * sh[4] + sh[3] for sh in shapes) + \
+            self.D_out * self.flat_dim + self.D_out
         if flat is None:
             flat = torch.zeros(n, dtype=torch.float32, device=device)
         assert flat.numel() == n
-        H1, W1 = (H - 8) // 4 + 1, (W - 8) // 4 + 1
-        H2, W2 = (H1 - 4) // 2 + 1, (W1 - 4) // 2 + 1
-        self.flat_dim = 32 * H2 * W2
-        c1 = _ParamView(flat, 0, (16, C, 8, 8), 16)
-        c2 = _ParamView(flat, c1.end, (32, 16, 4, 4), 32)
-        fc = _ParamView(flat, c2.end, (self.D_out, self.flat_dim), self.D_out)
-        self.model = nn.Sequential(c1, nn.ReLU(), c2, nn.ReLU(), nn.Flatten(), fc, nn.ReLU())
-        for m in (c1, c2, fc):
+        mods, views, off = [], [], 0
+        for cin, _, _, co, k, _, _, _ in shapes:
+            conv = _ParamView(flat, off, (co, cin, k, k), co)
+            off = conv.end
+            views.append(conv)
+            mods += [conv, nn.ReLU()]
+        fc = _ParamView(flat, off, (self.D_out, self.flat_dim), self.D_out)
+        views.append(fc)
+        self.model = nn.Sequential(*(mods + [nn.Flatten(), fc, nn.ReLU()]))
+        for m in views:
             m.reset_parameters(generator)
         self.__dict__['flat'] = flat
+
+    def spec_args(self):
+        """(n, cout, k, stride, C, H, W, F): the spec and frame arguments of smi_stem_*"""
+        return L.stem_spec(self.conv_channels, self.kernel_sizes, self.strides) + self.D_obs + \
+            (self.D_out,)
 
     def forward(self, obs):
         if obs.dtype != torch.uint8:
@@ -298,11 +364,13 @@ class CNNStemNetwork(nn.Module):
         x = obs.reshape(-1, *self.D_obs).contiguous()
         rows = x.shape[0]
         dev = self.flat.device
-        a2 = torch.empty(rows, self.flat_dim, dtype=torch.float32, device=dev)
+        spec = self.spec_args()
+        assert int(L.lib().smi_stem_param_count(*spec)) == self.flat.numel()
+        nb = int(L.lib().smi_stem_scratch_bytes(rows, *spec))
+        scratch = torch.empty(max(nb // 4, 1), dtype=torch.float32, device=dev)
         out = torch.empty(rows, self.D_out, dtype=torch.float32, device=dev)
-        C, H, W = self.D_obs
-        L.call('smi_cnn_forward', L.ptr(self.flat), L.ptr(x), None, max(rows, 1), 1, rows,
-               C, H, W, self.D_out, None, L.ptr(a2), L.ptr(out), self.D_out, L.stream(dev))
+        L.call('smi_stem_forward', L.ptr(self.flat), L.ptr(x), None, max(rows, 1), 1, rows, *spec,
+               None, L.ptr(scratch), nb, L.ptr(out), self.D_out, None, L.stream(dev))
         return out.reshape(*lead, self.D_out)
 
 
