@@ -580,35 +580,81 @@ lstm_fwd_r4_kernel(LstmFwdArgs a) {
   }
 }
 
-// KW: k range per wave (4H / waves-per-unit-group) rounded up to 8
+// One cell's BPTT step inputs (activated gates, c_t, c_{t-1}, dL/dh_t from the
+// heads) and the factors of the cell backward that depend on the stored gates
+// and c_t alone.  Written as one expression per gate, the cell backward
+// compiled 1 - tc^2 and 1 - cg^2 into FMAs and dc into fma(1 - tc^2, dh og,
+// dc_{t+1}); every other product and difference was a rounding of its own
+// (the VALU forms still are that code).  Both helpers state exactly those
+// operations with contraction off, so that computing the factors a phase
+// early (lstm_bwd_r4_kernel) cannot change a rounding.
+struct BpttIn { float ig, fg, cg, og, c, cp, dh; };
+struct BpttFac { float tc, omt, fo, fi, fgg, ff; };
+
+__device__ __forceinline__ BpttFac bptt_factors(const BpttIn& s) {
+#pragma clang fp contract(off)
+  BpttFac f;
+  f.tc = ftanh(s.c);
+  f.omt = fmaf(-f.tc, f.tc, 1.f);
+  f.fo = s.og * (1.f - s.og);
+  f.fi = s.ig * (1.f - s.ig);
+  f.fgg = fmaf(-s.cg, s.cg, 1.f);
+  f.ff = s.fg * (1.f - s.fg);
+  return f;
+}
+
+// d = (d_i, d_f, d_g, d_o) and dc_t fg (the caller masks it) from dh_rec
+__device__ __forceinline__ float bptt_cell(const BpttIn& s, const BpttFac& f, float dhr, float dcreg,
+                                           float d[4]) {
+#pragma clang fp contract(off)
+  const float dh = s.dh + dhr;
+  const float dc = fmaf(dh * s.og, f.omt, dcreg);
+  d[3] = (dh * f.tc) * f.fo;
+  d[0] = (dc * s.cg) * f.fi;
+  d[2] = (dc * s.ig) * f.fgg;
+  d[1] = (dc * s.cp) * f.ff;
+  return dc * s.fg;
+}
+
+// KW: k range per wave (4H / waves-per-unit-group) rounded up to 8.  The
+// launcher picks KW = 32 exactly when H <= 64 (one unit group, 8 waves over K)
+// and 104 / 128 beyond (two groups, 4 waves each), so KW fixes the split.
+//
+// What sits between a step's two barriers on the cell threads is one LDS trip
+// for the WPG partial sums, dh = dh_t + dh_rec, six dependent multiplies and
+// the four LDS writes.  Everything else rides in the MFMA phase's shadow: the
+// dgates stores of step t, the loads of step t-2 (two register sets, sa / sb,
+// alternated by step parity in a loop unrolled by two, so every loaded
+// register has one role for its whole life) and, after the wave's MFMAs are
+// issued, the gate-only factors of step t-1.  The loads are issued by
+// every thread from clamped addresses and consumed (pinned) by every thread a
+// whole step later: with no branch around either, the one vmcnt wait of the
+// loop is a counted one.  (The earlier form fetched t-1 under if (cell) / if (t > 0)
+// after the cell's stores and waited for it before the first barrier.)
+__device__ float g_lstm_zero_row[128];            // a W_hh row of zeros (H <= 128)
+// (KW = 32 keeps two workgroups per CU, 128 registers, as before)
 template <int KW>
-__global__ void __launch_bounds__(kWG8)
+__global__ void __launch_bounds__(kWG8, KW <= 32 ? 4 : 2)
 lstm_bwd_r4_kernel(LstmBwdArgs a) {
   if (a.skip && a.skip[0] != 0) return;
   LSTM_T0();
   constexpr int G4P = 4 * 128 + KW;               // dG row stride (reads run up to KW past 4H)
+  constexpr int WPG = KW <= 32 ? 8 : 4;           // waves per unit group of 64 lanes
   __shared__ __attribute__((aligned(16))) float dG[LR4 * G4P];
   __shared__ float red[8][LR4][64];
   const int H = a.H, B = a.B, G4 = 4 * H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);      // in scalar registers
   const int r0 = blockIdx.x * LR4;
-  const int64_t BH = (int64_t)B * H;
-  const int NU = (H + 63) >> 6;                   // unit groups of 64 lanes
-  const int WPG = 8 / NU;                         // waves per group (NU <= 2)
+  const int64_t BH = (int64_t)B * H, BG4 = (int64_t)B * G4;
   const int kw = (G4 + WPG - 1) / WPG;
   const int ug = wave / WPG, kp = wave - ug * WPG;
   const int k0 = kp * kw;
   const int unit = ug * 64 + lane;
   const int uc = unit < H ? unit : H - 1;
   for (int e = tid; e < LR4 * G4P; e += kWG8) dG[e] = 0.f;
-  float w[KW];                                    // W_hh[k0 + j][unit]
-#pragma unroll
-  for (int j = 0; j < KW; ++j) {
-    const int k = k0 + j;
-    const bool ok = j < kw && k < G4 && unit < H;
-    const float x = a.w_hh[(int64_t)(k < G4 ? k : G4 - 1) * H + uc];
-    w[j] = ok ? x : 0.f;
-  }
+  // zero partial sums: the first step's dh_rec is 0 + 0 + .. = +0 without a branch
+  for (int e = tid; e < 8 * LR4 * 64; e += kWG8) (&red[0][0][0])[e] = 0.f;
   const bool cell = tid < LR4 * H;
   const int crow = cell ? tid / H : 0;
   const int cunit = cell ? tid - crow * H : 0;
@@ -616,75 +662,132 @@ lstm_bwd_r4_kernel(LstmBwdArgs a) {
   const bool cok = cell && cgr < B;
   const int64_t grc = cgr < B ? cgr : B - 1;
   const int cug = cunit >> 6, cl = cunit & 63;
-  float pg[4], pc = 0.f, pcp = 0.f, pdh = 0.f;
-  auto fetch = [&](int t) {
-    const float* gp = a.gates + ((int64_t)t * B + grc) * G4 + cunit;
-    pg[0] = gp[0]; pg[1] = gp[H]; pg[2] = gp[2 * H]; pg[3] = gp[3 * H];
-    pc = a.cbuf[(int64_t)(t + 1) * BH + grc * H + cunit];
-    pcp = a.cbuf[(int64_t)t * BH + grc * H + cunit];
-    pdh = a.dh[(int64_t)t * BH + grc * H + cunit];
+  const int64_t goff = grc * G4 + cunit, hoff = grc * H + cunit;
+  auto fetch = [&](int t, BpttIn& s) {
+    const float* gp = a.gates + ((int64_t)t * BG4 + goff);
+    s.ig = gp[0]; s.fg = gp[H]; s.cg = gp[2 * H]; s.og = gp[3 * H];
+    const int64_t o = (int64_t)t * BH + hoff;
+    s.c = a.cbuf[o + BH];
+    s.cp = a.cbuf[o];
+    s.dh = a.dh[o];
   };
-  if (cell && a.S > 0) fetch(a.S - 1);
+  BpttIn sa, sb;                                  // steps S-1, S-3, .. / S-2, S-4, ..
+  fetch(a.S - 1, sa);
+  fetch(a.S > 1 ? a.S - 2 : 0, sb);
+  // W_hh[k0 + j][unit] in registers.  Rows past the wave's k range are zeros by
+  // address, as in load_col: a select on the loaded value is free to sink
+  // below the barrier, where the KW wave-uniform conditions it left behind
+  // spilled.  Lanes of units >= H hold unit H-1's column: their sums land in
+  // red[][][lane >= H], which no cell reads (the earlier form zeroed them).
+  float w[KW];
+  const int jn = min(kw, G4 - k0);                  // the wave's rows: k0 + j, j < jn
+#pragma unroll
+  for (int j = 0; j < KW; ++j) {
+    const bool in = j < jn;                           // wave-uniform
+    const float* base = in ? a.w_hh : g_lstm_zero_row;
+    const uint32_t ro = in ? (uint32_t)((k0 + j) * H) : 0u;
+    w[j] = base[ro + (uint32_t)uc];
+  }
+  // (pinned here as in the loop: the loop's waits are then counted from the
+  // loop's own loads on both ways into it)
+  asm volatile("" : "+v"(sa.ig), "+v"(sa.fg), "+v"(sa.cg), "+v"(sa.og), "+v"(sa.c), "+v"(sa.cp),
+               "+v"(sa.dh));
+  asm volatile("" : "+v"(sb.ig), "+v"(sb.fg), "+v"(sb.cg), "+v"(sb.og), "+v"(sb.c), "+v"(sb.cp),
+               "+v"(sb.dh));
+  BpttFac f = bptt_factors(sa);
   float dcreg = 0.f;
+  // the weights land here (vmcnt(0); nothing selects on them, so their waits
+  // would otherwise sit at their first MFMAs, inside the loop)
+  __builtin_amdgcn_s_waitcnt(0x0F70);
   __syncthreads();
-  LSTM_TICK(7);                                  // prologue (W_hh, first step inputs)
-  for (int t = a.S - 1; t >= 0; --t) {
+  LSTM_TICK(7);                                  // prologue (W_hh, first steps' inputs)
+  // cell phase of step t from its inputs x, up to the barrier: d = its dgates
+  auto cells = [&](const BpttIn& x, float d[4]) __attribute__((always_inline)) {
     if (cell) {
+      // the partial sums in one LDS round trip, added in the order p = 0, 1, ..
+      float r[WPG];
+#pragma unroll
+      for (int p = 0; p < WPG; ++p) r[p] = red[cug * WPG + p][crow][cl];
       float dhr = 0.f;
-      if (t < a.S - 1) {
-        for (int p = 0; p < WPG; ++p) dhr += red[cug * WPG + p][crow][cl];
-      }
-      const float ig = pg[0], fg = pg[1], cg = pg[2], og = pg[3];
-      const float dh = pdh + dhr;
-      const float tc = ftanh(pc);
-      const float dc = dh * og * (1.f - tc * tc) + dcreg;
-      const float d_o = (dh * tc) * (og * (1.f - og));
-      const float d_i = (dc * cg) * (ig * (1.f - ig));
-      const float d_g = (dc * ig) * (1.f - cg * cg);
-      const float d_f = (dc * pcp) * (fg * (1.f - fg));
-      dcreg = cok ? dc * fg : 0.f;
+#pragma unroll
+      for (int p = 0; p < WPG; ++p) dhr += r[p];
+      const float dcf = bptt_cell(x, f, dhr, dcreg, d);
+      dcreg = cok ? dcf : 0.f;
       float* l = dG + crow * G4P + cunit;
-      l[0] = cok ? d_i : 0.f; l[H] = cok ? d_f : 0.f;
-      l[2 * H] = cok ? d_g : 0.f; l[3 * H] = cok ? d_o : 0.f;
-      if (cok) {
-        float* o = a.dgates + ((int64_t)t * B + cgr) * G4 + cunit;
-        o[0] = d_i; o[H] = d_f; o[2 * H] = d_g; o[3 * H] = d_o;
-      }
-      if (t > 0) fetch(t - 1);
+      l[0] = cok ? d[0] : 0.f; l[H] = cok ? d[1] : 0.f;
+      l[2 * H] = cok ? d[2] : 0.f; l[3 * H] = cok ? d[3] : 0.f;
     }
     LSTM_TICK(3);
     __syncthreads();
     LSTM_TICK(4);
-    if (t == 0) break;
-    if (wave < NU * WPG) {
-      f32x4 acc[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-      // dgates operand reads LQ float4 ahead (as in the forward's h loop)
-      constexpr int NQ = KW / 4, LQ = 4;
-      const float4* dr = reinterpret_cast<const float4*>(dG + (lane & 3) * G4P + k0);
-      float4 q[LQ];
-#pragma unroll
-      for (int j = 0; j < LQ && j < NQ; ++j) q[j] = dr[j];
-#pragma unroll
-      for (int j = 0; j < NQ; ++j) {
-        const float4 u = q[j % LQ];
-        if (j + LQ < NQ) q[j % LQ] = dr[j + LQ];
-        const int a0 = (j & 1) * 4;
-        acc[a0 + 0] = mfma4x64(u.x, w[4 * j + 0], acc[a0 + 0]);
-        acc[a0 + 1] = mfma4x64(u.y, w[4 * j + 1], acc[a0 + 1]);
-        acc[a0 + 2] = mfma4x64(u.z, w[4 * j + 2], acc[a0 + 2]);
-        acc[a0 + 3] = mfma4x64(u.w, w[4 * j + 3], acc[a0 + 3]);
-        __builtin_amdgcn_sched_barrier(0);
-      }
-      const f32x4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) +
-                        ((acc[4] + acc[5]) + (acc[6] + acc[7]));
-#pragma unroll
-      for (int i = 0; i < 4; ++i) red[wave][i][lane] = sum[i];
+  };
+  auto store = [&](int t, const float d[4]) __attribute__((always_inline)) {
+    if (cok) {
+      float* o = a.dgates + ((int64_t)t * BG4 + (int64_t)cgr * G4 + cunit);
+      o[0] = d[0]; o[H] = d[1]; o[2 * H] = d[2]; o[3 * H] = d[3];
     }
+  };
+  // a step t > 0: x holds its inputs, y those of step t-1 (in flight)
+  auto step = [&](int t, BpttIn& x, BpttIn& y) __attribute__((always_inline)) {
+    float d[4] = {0.f, 0.f, 0.f, 0.f};
+    cells(x, d);
+    f32x4 acc[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) acc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // dgates operand reads LQ float4 ahead (as in the forward's h loop)
+    constexpr int NQ = KW / 4, LQ = 4;
+    const float4* dr = reinterpret_cast<const float4*>(dG + (lane & 3) * G4P + k0);
+    float4 q[LQ];
+#pragma unroll
+    for (int j = 0; j < LQ && j < NQ; ++j) q[j] = dr[j];
+#pragma unroll
+    for (int j = 0; j < NQ; ++j) {
+      const float4 u = q[j % LQ];
+      if (j + LQ < NQ) q[j % LQ] = dr[j + LQ];
+      const int a0 = (j & 1) * 4;
+      acc[a0 + 0] = mfma4x64(u.x, w[4 * j + 0], acc[a0 + 0]);
+      acc[a0 + 1] = mfma4x64(u.y, w[4 * j + 1], acc[a0 + 1]);
+      acc[a0 + 2] = mfma4x64(u.z, w[4 * j + 2], acc[a0 + 2]);
+      acc[a0 + 3] = mfma4x64(u.w, w[4 * j + 3], acc[a0 + 3]);
+      // once the matrix pipe has work: step t's dgates stores, and step t-2's
+      // inputs into x, whose values of step t are spent
+      if (j == 1) {
+        store(t, d);
+        fetch(t > 1 ? t - 2 : 0, x);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    // step t-1's inputs, loaded a step ago: the loop's one (counted) vmcnt wait,
+    // here for all seven, so that the cell phase meets none
+    asm volatile("" : "+v"(y.ig), "+v"(y.fg), "+v"(y.cg), "+v"(y.og), "+v"(y.c), "+v"(y.cp),
+                 "+v"(y.dh));
+    // under the MFMAs just issued (pinned: their one use is in the next cell
+    // phase, where the compiler would otherwise compute them)
+    f = bptt_factors(y);
+    asm volatile("" : "+v"(f.tc), "+v"(f.omt), "+v"(f.fo), "+v"(f.fi), "+v"(f.fgg), "+v"(f.ff));
+    const f32x4 sum = ((acc[0] + acc[1]) + (acc[2] + acc[3])) +
+                      ((acc[4] + acc[5]) + (acc[6] + acc[7]));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) red[wave][i][lane] = sum[i];
     LSTM_TICK(5);
     __syncthreads();
+  };
+  // steps S-1 .. 1 in pairs (one way out of the loop: a second one led back to
+  // the loop head in the structured flow and, with x's loads in flight on it,
+  // turned the cell phase's waits into vmcnt(0)), then the odd one and step 0
+  int t = a.S - 1;
+  for (int i = t >> 1; i > 0; --i, t -= 2) {
+    step(t, sa, sb);
+    step(t - 1, sb, sa);
   }
+  float d[4] = {0.f, 0.f, 0.f, 0.f};
+  if (t == 1) {
+    step(1, sa, sb);
+    cells(sb, d);
+  } else {
+    cells(sa, d);
+  }
+  store(0, d);
 }
 
 static int device_cus() {
