@@ -837,6 +837,21 @@ int smi_mse_grad(const float* q, int64_t q_stride, const float* y, int64_t n, fl
  * td_out == NULL: not written; both NULL: smi_mse_grad's own kernel. */
 int smi_mse_grad_weighted(const float* q, int64_t q_stride, const float* y, const float* w,
                           int64_t n, float* dq, float* loss, float* td_out, void* stream);
+/* One rank's shard of smi_mse_grad_weighted over a global draw (data-parallel
+ * DDPG with a prioritized replay): the n rows given are rows [row0, row0 + n) of
+ * a draw of n_global rows.  dq [n], loss and their divisor n are bit for bit
+ * smi_mse_grad_weighted's on the same rows (the same kernel; smi_mse_grad_weighted
+ * is n_global = n, row0 = 0): the ranks' gradients are averaged by the caller.
+ *   td_all [n_global]: td_all[row0 + i] = Q_i - y_i, and every other entry is
+ *     written +0.0f by the same launch.  A SUM all-reduce of the ranks' td_all is
+ *     then an exact all-gather (x + 0 + ... + 0 = x in IEEE arithmetic), except
+ *     that a td of -0.0 arrives as +0.0, which priorities (|td|) do not see.
+ * w and loss may be NULL; td_all is required.
+ * SMI_E_ARG: NULL q, y, dq or td_all, n < 1, n_global < n, row0 < 0,
+ * row0 + n > n_global. */
+int smi_mse_grad_weighted_shard(const float* q, int64_t q_stride, const float* y, const float* w,
+                                int64_t n, int64_t n_global, int64_t row0, float* dq, float* loss,
+                                float* td_all, void* stream);
 /* actor loss -Q(s, mu(s)).mean() (ddpg.py:325-329): loss, dQ = -1/n */
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream);

@@ -168,6 +168,7 @@ _SIGS = {
                                            c_int, P]),
     'smi_mse_grad': (c_int, [P, c_i64, P, c_i64, P, P, P]),
     'smi_mse_grad_weighted': (c_int, [P, c_i64, P, P, c_i64, P, P, P, P]),
+    'smi_mse_grad_weighted_shard': (c_int, [P, c_i64, P, P, c_i64, c_i64, c_i64, P, P, P, P]),
     'smi_dqn_td': (c_int, [P, c_i64] * 9 + [P, c_i64, c_int, c_f32, c_int, c_int, P, c_i64, P, P, P,
                                             P, P]),
     'smi_dqn_td_shard': (c_int, [P, c_i64] * 9 + [P, c_i64, c_i64, c_i64, c_int, c_f32, c_int, c_int,

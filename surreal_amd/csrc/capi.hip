@@ -455,7 +455,20 @@ int smi_mse_grad(const float* q, int64_t q_stride, const float* y, int64_t n, fl
 int smi_mse_grad_weighted(const float* q, int64_t q_stride, const float* y, const float* w,
                           int64_t n, float* dq, float* loss, float* td_out, void* stream) {
   REQUIRE(q && y && dq && n > 0, "mse_grad_weighted: bad args");
-  return launch_mse_grad_weighted(q, q_stride, y, w, n, dq, loss, td_out, SMI_STREAM(stream));
+  return launch_mse_grad_weighted(q, q_stride, y, w, n, n, 0, dq, loss, td_out,
+                                  SMI_STREAM(stream));
+}
+
+int smi_mse_grad_weighted_shard(const float* q, int64_t q_stride, const float* y, const float* w,
+                                int64_t n, int64_t n_global, int64_t row0, float* dq, float* loss,
+                                float* td_all, void* stream) {
+  REQUIRE(q && y && dq && td_all, "mse_grad_weighted_shard: null pointer");
+  REQUIRE(n >= 1, "mse_grad_weighted_shard: n < 1");
+  REQUIRE(n_global >= n, "mse_grad_weighted_shard: n_global < n");
+  REQUIRE(row0 >= 0, "mse_grad_weighted_shard: row0 < 0");
+  REQUIRE(row0 <= n_global - n, "mse_grad_weighted_shard: row0 + n > n_global");
+  return launch_mse_grad_weighted(q, q_stride, y, w, n, n_global, row0, dq, loss, td_all,
+                                  SMI_STREAM(stream));
 }
 
 int smi_dqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,

@@ -5,7 +5,9 @@
 //   mse_grad        critic loss nn.MSELoss()(Q, y): loss, dQ = 2 (Q - y) / n
 //   mse_grad_weighted  the prioritized replay's critic loss mean(w (Q - y)^2):
 //                   dQ = (2 (Q - y) / n) * w (this order: w = 1 gives mse_grad's
-//                   bits), and the TD error Q - y for the priorities
+//                   bits), and the TD error Q - y for the priorities; its shard
+//                   form (smi_mse_grad_weighted_shard, the SAME kernel) writes
+//                   the TD errors at the rank's rows of the whole draw
 //   neg_mean_grad   actor loss -Q(s, mu(s)).mean(): loss, dQ = -1 / n
 //   tanh_backward   d/dz tanh(z) = 1 - tanh(z)^2 (actor output layer)
 //   copy_cols       write the action block of the critic's concat input
@@ -36,13 +38,22 @@ mse_grad_kernel(const float* __restrict__ q, int64_t qs, const float* __restrict
   if (threadIdx.x == 0 && loss) loss[0] = (float)(a / (double)n);
 }
 
+// The n rows given are rows [row0, row0 + n) of a draw of n_global rows (whole
+// batch: n_global = n, row0 = 0).  dq, the loss sum and its divisor n are the
+// shard's own; td (when given) spans the draw: td[row0 + i] = d_i and every other
+// entry of td[0, n_global) is written +0.0f, so a SUM over the ranks' images is
+// an exact gather (dqn_td_kernel's protocol).
 __global__ void __launch_bounds__(kWG)
 mse_grad_weighted_kernel(const float* __restrict__ q, int64_t qs, const float* __restrict__ y,
-                         const float* __restrict__ w, int64_t n, float* __restrict__ dq,
-                         float* loss, float* __restrict__ td) {
+                         const float* __restrict__ w, int64_t n, int64_t n_global, int64_t row0,
+                         float* __restrict__ dq, float* loss, float* __restrict__ td) {
   __shared__ double scr[kNW];
   const float inv = 1.f / (float)n;
   double a = 0.0;
+  // the other ranks' entries of td (none for the whole batch): disjoint from the
+  // rows written below
+  if (td)
+    for (int64_t i = threadIdx.x; i < n_global - n; i += kWG) td[i < row0 ? i : i + n] = 0.f;
   for (int64_t i = threadIdx.x; i < n; i += kWG) {
     const float d = q[i * qs] - y[i];
     const float g = inv * (2.f * d);
@@ -55,7 +66,7 @@ mse_grad_weighted_kernel(const float* __restrict__ q, int64_t qs, const float* _
       dq[i] = g;
       a += (double)d2;
     }
-    if (td) td[i] = d;
+    if (td) td[row0 + i] = d;
   }
   a = block_sum_d(a, scr);
   if (threadIdx.x == 0 && loss) loss[0] = (float)(a / (double)n);
@@ -285,10 +296,11 @@ int launch_mse_grad(const float* q, int64_t qs, const float* y, int64_t n, float
   return check_launch("mse_grad_kernel");
 }
 int launch_mse_grad_weighted(const float* q, int64_t qs, const float* y, const float* w, int64_t n,
-                             float* dq, float* loss, float* td, hipStream_t st) {
+                             int64_t n_global, int64_t row0, float* dq, float* loss, float* td,
+                             hipStream_t st) {
   if (!w && !td) return launch_mse_grad(q, qs, y, n, dq, loss, st);
-  hipLaunchKernelGGL(mse_grad_weighted_kernel, dim3(1), dim3(kWG), 0, st, q, qs, y, w, n, dq, loss,
-                     td);
+  hipLaunchKernelGGL(mse_grad_weighted_kernel, dim3(1), dim3(kWG), 0, st, q, qs, y, w, n, n_global,
+                     row0, dq, loss, td);
   return check_launch("mse_grad_weighted_kernel");
 }
 int launch_neg_mean_grad(const float* q, int64_t qs, int64_t n, float* dq, float* loss,

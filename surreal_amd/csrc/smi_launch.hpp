@@ -41,7 +41,8 @@ int launch_ddpg_target(const float* r, const float* d, const float* q, const flo
 int launch_mse_grad(const float* q, int64_t qs, const float* y, int64_t n, float* dq, float* loss,
                     hipStream_t st);
 int launch_mse_grad_weighted(const float* q, int64_t qs, const float* y, const float* w, int64_t n,
-                             float* dq, float* loss, float* td, hipStream_t st);
+                             int64_t n_global, int64_t row0, float* dq, float* loss, float* td,
+                             hipStream_t st);
 int launch_neg_mean_grad(const float* q, int64_t qs, int64_t n, float* dq, float* loss,
                          hipStream_t st);
 int launch_tanh_backward(const float* dy, int64_t ldg, const float* y, int64_t ldy, int64_t rows,

@@ -306,7 +306,12 @@ class DDPGLearner(DeviceLearner):
     layernorm, TD3 options).  A batch with a 'weights' entry (float32 [B, 1],
     replay.PrioritizedReplay.sample_batch) weights both critics' loss; after
     every learn() `td_error` is a device view [B] of the first critic's Q - y
-    before its Adam step (PrioritizedReplay.update_priorities_from_td)."""
+    before its Adam step (PrioritizedReplay.update_priorities_from_td).  With
+    dp, `td_error` is [B_global = replay.batch_size * world]: the TD errors of
+    the WHOLE draw, in draw order, on every rank (replay.sample_shard's idx_all
+    names their slots).  Each rank's smi_mse_grad_weighted_shard writes its rows
+    of it and +0.0 elsewhere, and it rides behind the critic gradients in the
+    first of the two exchanges, so the SUM gathers it exactly."""
 
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  device=None, seed=0, use_graph=False, dp=None, checkpoint_full_state=False,
@@ -318,7 +323,12 @@ class DDPGLearner(DeviceLearner):
         the ranks before clip + Adam, which equals the reference's mean loss on
         the concatenated global batch (equal shards).  Initial weights are
         broadcast from rank 0 (learner.replicate_from_rank0), so parameters stay
-        replicated whatever seed each rank passes.
+        replicated whatever seed each rank passes.  A learn() is two all-reduces
+        ([critic gradients | td_all], then [actor gradient | statistics]); a
+        batch of another row count raises ValueError; with replicated
+        PrioritizedReplays every rank passes sample_shard's batch and feeds
+        update_priorities_from_td(idx_all, learner.td_error).  use_graph with
+        world > 1 runs eagerly.
         metrics / checkpoint: as PPOLearner's (session.py): learn() reports the
         statistics and calls periodic_checkpoint(global_steps=
         current_iteration) as ddpg.py:371-376 does."""
@@ -395,15 +405,24 @@ class DDPGLearner(DeviceLearner):
                 groups.append(('critic2_cnn', self.model2.perception.flat, net.lr_critic,
                                net.critic_regularization))
         # gradient buffers packed for the data-parallel exchange: [critic | cnn |
-        # critic2 | cnn2] (independent, one all-reduce) and [actor | 12 statistics]
+        # critic2 | cnn2] (independent, one all-reduce) and [actor | 12 statistics];
+        # with dp the first carries, behind a pad to a multiple of 4 floats, the TD
+        # errors of the whole draw (td_error: summed, not averaged)
         nc = self.model.critic.flat.numel()
         nq = self.model.perception.flat.numel() if self.is_pixel_input else 0
         na = self.model.actor.flat.numel()
-        self._critic_pack = torch.zeros((nc + nq) * (2 if self.use_double_critic else 1), device=dev)
+        ng = (nc + nq) * (2 if self.use_double_critic else 1)
+        if self.dp is None:
+            self._critic_pack = torch.zeros(ng, device=dev)
+        else:
+            ng4, Bg = (ng + 3) // 4 * 4, self.batch_size * self.dp.world_size
+            self._critic_pack = torch.zeros(ng4 + Bg, device=dev)
+            self.td_error = self._critic_pack[ng4:]
+        self._critic_grads = self._critic_pack[:ng]
         self._actor_pack = torch.zeros(na + 12, device=dev)
         packs = {'critic': self._critic_pack[:nc], 'critic_cnn': self._critic_pack[nc:nc + nq],
                  'critic2': self._critic_pack[nc + nq:2 * nc + nq],
-                 'critic2_cnn': self._critic_pack[2 * nc + nq:], 'actor': self._actor_pack[:na]}
+                 'critic2_cnn': self._critic_pack[2 * nc + nq:ng], 'actor': self._actor_pack[:na]}
         for name, flat, lr, wd in groups:
             self.opt[name] = self.adam_state(flat, lr, packs[name], wd)
         self.stats_buf = self._actor_pack[na:]
@@ -430,12 +449,6 @@ class DDPGLearner(DeviceLearner):
         with torch.no_grad():
             for t, s_ in self._target_pairs(perception):
                 t.copy_(s_)
-
-    def _dp_mean_(self, t):
-        """Average a per-rank gradient / statistics buffer over the ranks."""
-        if self.dp is not None:
-            self.dp.allreduce_(t)
-            t.mul_(1.0 / self.dp.world_size)
 
     def _adam(self, name, flat, clip_value, st):
         self.adam_step(self.opt[name], flat, 1e-8, 0.0, clip_value, st)
@@ -466,13 +479,26 @@ class DDPGLearner(DeviceLearner):
         return Config(out)
 
     # --------------------------------------------------------- _optimize
-    def _optimize(self, obs, actions, rewards, obs_next, done,           # ddpg.py:244-352
-                  weights=None, target_update=True):
-        """weights (float32 [B] or [B, 1], contiguous; a prioritized replay's
+    def _optimize(self, obs, actions, rewards, obs_next, done, weights=None, target_update=True):
+        """One update, the exchanges included (eager and captured paths)."""
+        for buf in self._update(obs, actions, rewards, obs_next, done, weights, target_update):
+            self.dp.allreduce_(buf)
+
+    def _update(self, obs, actions, rewards, obs_next, done,             # ddpg.py:244-352
+                weights=None, target_update=True):
+        """The update's launch sequence, as a generator of the buffers a
+        data-parallel learner must all-reduce (SUM) between its launches: the
+        critic image [gradients | pad | td_all], then [actor gradient | 12
+        statistics]; the 1 / world scale follows each (the gradients and the
+        statistics only: td_all is the plain sum).  Without dp it yields nothing.
+        weights (float32 [B] or [B, 1], contiguous; a prioritized replay's
         importance-sampling weights): both critics' loss becomes mean(w (Q -
         y)^2); the actor loss stays unweighted.  The first critic's Q - y
         before its Adam step is left in self.td_error either way."""
         B = actions.shape[0]
+        if self.dp is not None and B != self.batch_size:
+            raise ValueError(f'data parallel: a rank\'s batch is replay.batch_size = '
+                             f'{self.batch_size} rows (td_error spans batch_size * world), got {B}')
         if weights is not None and (weights.numel() != B or not weights.is_contiguous()
                                     or weights.dtype != torch.float32):
             raise ValueError(f'weights: expected contiguous float32 [{B}] or [{B}, 1], got '
@@ -527,9 +553,14 @@ class DDPGLearner(DeviceLearner):
         crit = self.model.critic
         q = net.critic_fwd(crit, obs, actions, B, store='c')
         dq = net.buf('dq', (B, 1))
-        self.td_error = net.buf('td', (B,))
-        L.call('smi_mse_grad_weighted', p(q), 1, p(y), p(weights), B, p(dq),
-               p(self.stats_buf[1:2]), p(self.td_error), st)
+        if self.dp is None:
+            self.td_error = net.buf('td', (B,))
+            L.call('smi_mse_grad_weighted', p(q), 1, p(y), p(weights), B, p(dq),
+                   p(self.stats_buf[1:2]), p(self.td_error), st)
+        else:       # this rank's rows of the whole draw's TD errors, +0.0 in the others'
+            L.call('smi_mse_grad_weighted_shard', p(q), 1, p(y), p(weights), B,
+                   B * self.dp.world_size, self.dp.rank * B, p(dq), p(self.stats_buf[1:2]),
+                   p(self.td_error), st)
         g = self.opt['critic']['g']
         cnn = (self.model, pix, 'cp', self.opt['critic_cnn']['g']) if self.is_pixel_input else None
         with L.dw_group(st):
@@ -552,7 +583,10 @@ class DDPGLearner(DeviceLearner):
             L.call('smi_ddpg_stats', p(actions), actions.stride(0), self.action_dim, p(rewards),
                    rewards.stride(0) if rewards.dim() == 2 else 1, p(y), p(q_2), 1, B,
                    p(self.stats_buf[8:12]), st)         # [.., .., .., Q_policy2]
-        self._dp_mean_(self._critic_pack)
+        if self.dp is not None:
+            yield self._critic_pack
+            self._ctx.make_current()      # whatever ran on this thread meanwhile
+            self._critic_grads.mul_(1.0 / self.dp.world_size)
         self._adam('critic', crit.flat, cclip, st)
         if self.is_pixel_input:         # the perception: critic optimizer, no value clip
             self._adam('critic_cnn', self.model.perception.flat, 0.0, st)
@@ -573,7 +607,10 @@ class DDPGLearner(DeviceLearner):
         # the actor gradient (one exchange)
         L.call('smi_ddpg_stats', p(actions), actions.stride(0), A, p(rewards), rs, p(y), p(q), 1,
                B, p(self.stats_buf[2:6]), st)
-        self._dp_mean_(self._actor_pack)
+        if self.dp is not None:
+            yield self._actor_pack
+            self._ctx.make_current()
+            self._actor_pack.mul_(1.0 / self.dp.world_size)
         self._adam('actor', act.flat,
                    self.actor_gradient_clip_value if self.clip_actor_gradient else 0.0, st)
         if target_update:
@@ -672,12 +709,37 @@ class DDPGLearner(DeviceLearner):
                 self._hard_update()
 
     # ------------------------------------------------------- reference API
-    def _learn_device(self, batch):                                      # ddpg.py:354-376
+    def _learn_phases(self, batch):
+        """learn() as a generator of the buffers a data-parallel learner must
+        all-reduce (SUM) between its launches (_update: the critic image, then
+        the actor image).  Without dp it yields nothing."""
+        self.current_iteration += 1
+        self._ctx.make_current()
+        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
+            batch = self.preprocess(batch)
+        if self.dp is None:
+            self._learn_device(batch)
+        else:
+            yield from self._update(*self._inputs(batch), weights=batch.get('weights'))
+        self._report_metrics(self.current_iteration)
+        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
+
+    def learn(self, batch):
+        if self.dp is None:           # the one-GPU frame the off-policy learners share
+            return super().learn(batch)
+        for buf in self._learn_phases(batch):
+            self.dp.allreduce_(buf)
+
+    def _inputs(self, batch):
+        """(obs, actions, rewards, obs_next, dones) of a device batch"""
         obs, obs_next = batch['obs'], batch['obs_next']
         if not self.is_pixel_input:
             obs = obs['low_dim']['flat_inputs'] if isinstance(obs, dict) else obs
             obs_next = obs_next['low_dim']['flat_inputs'] if isinstance(obs_next, dict) else obs_next
-        ins = (obs, batch['actions'], batch['rewards'], obs_next, batch['dones'])
+        return (obs, batch['actions'], batch['rewards'], obs_next, batch['dones'])
+
+    def _learn_device(self, batch):                                      # ddpg.py:354-376
+        ins = self._inputs(batch)
         weights = batch.get('weights')
         if self.is_pixel_input or not self.use_graph:
             self._optimize(*ins, weights=weights)

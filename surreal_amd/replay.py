@@ -397,8 +397,8 @@ class UniformReplay(object):
 
     def sample_shard(self, batch_size, rank, world):
         """Returns (idx_all, batch) for one rank of a data-parallel learner
-        (DQNLearner(dp=...)): idx_all is the WHOLE draw, int64 [batch_size] on
-        the device (overwritten by the next draw), and batch is sample_batch's
+        (DQNLearner / DDPGLearner(dp=...)): idx_all is the WHOLE draw, int64
+        [batch_size] on the device (overwritten by the next draw), and batch is sample_batch's
         dict for rows [rank * n, (rank + 1) * n) of it, n = batch_size / world,
         gathered by the same kernels over the index slice.  Every replica draws
         all batch_size indices from the one CPython-exact stream, so replicas
@@ -453,8 +453,8 @@ class PrioritizedReplay(UniformReplay):
     alpha is read from learner_config.replay.alpha, as the reference does.
     Data parallel: every rank keeps a replicated replay (same seed, same
     inserts) and calls sample_shard(), which draws the whole global batch on
-    every rank and gathers the rank's rows; after DQNLearner(dp=...).learn()
-    every rank applies update_priorities_from_td(idx_all, learner.td_error),
+    every rank and gathers the rank's rows; after DQNLearner / DDPGLearner
+    (dp=...).learn() every rank applies update_priorities_from_td(idx_all, learner.td_error),
     the TD errors of the whole draw in draw order, so the trees stay
     bit-identical.  sample() and sample_batch() are the one-rank calls:
     world != 1 raises ValueError there."""
