@@ -30,7 +30,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .config import Config, ConfigError
-from .device_learner import DeviceLearner, LaunchNet, p
+from .device_learner import DeviceLearner, LaunchNet, exchange_image, p
 from .model import CNNStemNetwork, _FlatViews, _LinearView
 
 RELU, TANH, NONE = 1, 2, 0
@@ -334,7 +334,6 @@ class DDPGLearner(DeviceLearner):
         current_iteration) as ddpg.py:371-376 does."""
         lc, ec = self._init_device(learner_config, env_config, session_config, metrics, checkpoint,
                                    device, checkpoint_full_state)
-        self.dp = dp if dp is not None and dp.world_size > 1 else None
         self.batch_size = lc.replay.batch_size
         self.discount_factor = lc.algo.gamma
         self.n_step = lc.algo.n_step
@@ -374,7 +373,6 @@ class DDPGLearner(DeviceLearner):
             self.model2 = mk2()
             self.model_target2 = mk2()
         self.is_pixel_input = self.model.is_pixel_input
-        from .learner import replicate_from_rank0
         flats = [self.model.actor.flat, self.model.critic.flat]
         if self.use_double_critic:
             flats.append(self.model2.critic.flat)
@@ -386,7 +384,7 @@ class DDPGLearner(DeviceLearner):
             flats.append(self.model_target.perception.flat)
             if self.use_double_critic:
                 flats.append(self.model_target2.perception.flat)
-        replicate_from_rank0(self.dp, flats)
+        self.dp = self._dp_group(dp, flats)
         # ddpg.py:174-178: the constructor hard-syncs the target actor and
         # critic(s) only; a target perception keeps its own random init until
         # the first target update
@@ -413,12 +411,10 @@ class DDPGLearner(DeviceLearner):
         na = self.model.actor.flat.numel()
         ng = (nc + nq) * (2 if self.use_double_critic else 1)
         if self.dp is None:
-            self._critic_pack = torch.zeros(ng, device=dev)
+            self._critic_pack = self._critic_grads = torch.zeros(ng, device=dev)
         else:
-            ng4, Bg = (ng + 3) // 4 * 4, self.batch_size * self.dp.world_size
-            self._critic_pack = torch.zeros(ng4 + Bg, device=dev)
-            self.td_error = self._critic_pack[ng4:]
-        self._critic_grads = self._critic_pack[:ng]
+            self._critic_pack, self._critic_grads, (self.td_error,) = exchange_image(
+                dev, ng, (self.batch_size * self.dp.world_size,))
         self._actor_pack = torch.zeros(na + 12, device=dev)
         packs = {'critic': self._critic_pack[:nc], 'critic_cnn': self._critic_pack[nc:nc + nq],
                  'critic2': self._critic_pack[nc + nq:2 * nc + nq],
@@ -709,26 +705,9 @@ class DDPGLearner(DeviceLearner):
                 self._hard_update()
 
     # ------------------------------------------------------- reference API
-    def _learn_phases(self, batch):
-        """learn() as a generator of the buffers a data-parallel learner must
-        all-reduce (SUM) between its launches (_update: the critic image, then
-        the actor image).  Without dp it yields nothing."""
-        self.current_iteration += 1
-        self._ctx.make_current()
-        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
-            batch = self.preprocess(batch)
-        if self.dp is None:
-            self._learn_device(batch)
-        else:
-            yield from self._update(*self._inputs(batch), weights=batch.get('weights'))
-        self._report_metrics(self.current_iteration)
-        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
-
-    def learn(self, batch):
-        if self.dp is None:           # the one-GPU frame the off-policy learners share
-            return super().learn(batch)
-        for buf in self._learn_phases(batch):
-            self.dp.allreduce_(buf)
+    def _update_phases(self, batch):
+        """the data-parallel update: _update's critic image, then its actor image"""
+        yield from self._update(*self._inputs(batch), weights=batch.get('weights'))
 
     def _inputs(self, batch):
         """(obs, actions, rewards, obs_next, dones) of a device batch"""

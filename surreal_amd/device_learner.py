@@ -1,6 +1,7 @@
 """What the learners share on the host side of their launches: config
 coercion, named scratch buffers, the dense-layer launch helpers (LaunchNet)
-and, for the off-policy learners, the learn() frame, the Adam state and the
+and, for the off-policy learners, the learn() frame with and without a
+data-parallel group, the layout of an exchange image, the Adam state and the
 one hipGraph capture-and-replay routine (DeviceLearner)."""
 import torch
 
@@ -22,6 +23,19 @@ def named_buf(bufs, device, name, shape, dtype=torch.float32):
         t = torch.zeros(shape, dtype=dtype, device=device)
         bufs[name] = t
     return t
+
+
+def exchange_image(device, n_grad, tails):
+    """What one all-reduce of a data-parallel learn() carries: the zero-filled
+    buffer [gradient (n_grad) | pad to a multiple of 4 floats | tails...], its
+    gradient view and the views of the tails (their lengths in `tails`)"""
+    off = (n_grad + 3) // 4 * 4
+    buf = torch.zeros(off + sum(tails), dtype=torch.float32, device=device)
+    views = []
+    for n in tails:
+        views.append(buf[off:off + n])
+        off += n
+    return buf, buf[:n_grad], views
 
 
 class LaunchNet(object):
@@ -51,7 +65,12 @@ class LaunchNet(object):
 class DeviceLearner(LearnerHooks):
     """An off-policy learner whose update is one launch sequence on one stream.
     The host class provides preprocess(host batch), _learn_device(device batch)
-    and _stats_dict; use_graph routes the update through _graph_step."""
+    and _stats_dict; use_graph routes the update through _graph_step.  A
+    data-parallel learner (self.dp: a group exposing world_size, rank and
+    allreduce_, see _dp_group) also provides _update_phases(device batch): the
+    update as a generator of the buffers to all-reduce (SUM) between its
+    launches."""
+    dp = None                     # one GPU, unless the constructor sets a group
 
     def _init_device(self, learner_config, env_config, session_config, metrics, checkpoint,
                      device, checkpoint_full_state):
@@ -71,6 +90,15 @@ class DeviceLearner(LearnerHooks):
         self._graph = None
         self._gin = None
         return self.learner_config, self.env_config
+
+    @staticmethod
+    def _dp_group(dp, tensors):
+        """a constructor's data-parallel group: None for one rank (dp=None or a
+        group of world 1); the tensors start as rank 0's on every rank"""
+        from .learner import replicate_from_rank0
+        dp = dp if dp is not None and dp.world_size > 1 else None
+        replicate_from_rank0(dp, tensors)
+        return dp
 
     # ---------------------------------------------------------------- Adam
     @staticmethod
@@ -93,11 +121,30 @@ class DeviceLearner(LearnerHooks):
 
     # ------------------------------------------------------- reference API
     def learn(self, batch):                               # ddpg.py:354-376, dqn.py:75-92
-        self.current_iteration += 1
+        if self.dp is not None:
+            for buf in self._learn_phases(batch):
+                self.dp.allreduce_(buf)
+            return
+        self.current_iteration += 1           # one GPU: the frame without a generator
         self._ctx.make_current()
         if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
             batch = self.preprocess(batch)
         self._learn_device(batch)
+        self._report_metrics(self.current_iteration)
+        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
+
+    def _learn_phases(self, batch):
+        """learn() as a generator of the buffers a data-parallel learner must
+        all-reduce (SUM) between its launches (_update_phases); a caller that
+        is not learn() sums them itself.  Without dp it yields nothing."""
+        self.current_iteration += 1
+        self._ctx.make_current()
+        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
+            batch = self.preprocess(batch)
+        if self.dp is None:
+            self._learn_device(batch)
+        else:
+            yield from self._update_phases(batch)
         self._report_metrics(self.current_iteration)
         self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
 

@@ -60,9 +60,10 @@ input), more than 4 conv layers or a layer outside the kernel's ranges
 (1 <= k <= 8, 1 <= stride <= min(k, 4), 1 <= channels <= 128), a non-discrete
 action spec.
 
-Data parallel (DQNLearner(dp=...), the protocol of DDPGLearner's dp): N ranks
-each learn on B / N rows of one global draw (replay.sample_shard) and end with
-the parameters, statistics, TD errors and, through
+Data parallel (DQNLearner(dp=...); DeviceLearner owns the learn() frame and the
+layout of the exchange image): N ranks each learn on B / N rows of one global
+draw (replay.sample_shard) and end with the parameters, statistics, TD errors
+and, through
 update_priorities_from_td(idx_all, learner.td_error), the priority trees that
 one learner on the B rows would have.  smi_dqn_td_shard divides by the global
 batch, so the SUM of the ranks' gradient images is the global-batch gradient;
@@ -78,7 +79,7 @@ import torch.nn as nn
 
 from . import _lib as L
 from .config import Config, ConfigError
-from .device_learner import DeviceLearner, LaunchNet, as_config, p
+from .device_learner import DeviceLearner, LaunchNet, as_config, exchange_image, p
 from .model import _LinearView
 
 RELU, NONE = 1, 0
@@ -475,20 +476,14 @@ class DQNLearner(DeviceLearner):
 
     def __init__(self, learner_config, env_config, session_config=None, metrics=None,
                  device=None, seed=0, use_graph=False, checkpoint=None,
-                 checkpoint_full_state=False, **parallel):
-        """The one keyword `parallel` takes is dp (keyword only; anything else is
-        a TypeError, as for a named parameter).
-        dp: None (one GPU) or a data-parallel group exposing `world_size`,
-        `rank` and `allreduce_(tensor)` (in-place SUM, stream-ordered), e.g.
+                 checkpoint_full_state=False, *, dp=None):
+        """dp (keyword only): None (one GPU) or a data-parallel group exposing
+        `world_size`, `rank` and `allreduce_(tensor)` (in-place SUM, stream-ordered), e.g.
         learner.TorchDistAllReduce().  Each rank passes its own
         replay.batch_size = B_global / world rows of one global draw
         (sample_shard); initial weights are broadcast from rank 0.  A group of
         world 1 is dp=None.  use_graph with world > 1 runs eagerly (the
         collective is not captured)."""
-        dp = parallel.pop('dp', None)
-        if parallel:
-            raise TypeError('DQNLearner() got an unexpected keyword argument {!r}'.format(
-                sorted(parallel)[0]))
         lc, ec = as_config(learner_config), as_config(env_config)
         D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)      # host checks come first
         self.algo = algo = lc.algo
@@ -502,10 +497,7 @@ class DQNLearner(DeviceLearner):
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
         self.pixel = bool(conv_kw)
         self.q_target = self.q_func.clone()                   # dqn.py:17
-        self.dp = dp if dp is not None and dp.world_size > 1 else None
-        if self.dp is not None:
-            from .learner import replicate_from_rank0
-            replicate_from_rank0(self.dp, [self.q_func.flat, self.q_target.flat])
+        self.dp = self._dp_group(dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
         self.stats_buf = torch.zeros(2, dtype=torch.float32, device=self.device)
         self.td_error = None
@@ -554,19 +546,6 @@ class DQNLearner(DeviceLearner):
                 self.device, non_blocking=True)
         return Config(out)
 
-    def _exchange_image(self, B_global):
-        """[ gradient image (P floats, padded to a multiple of 4) | td_all
-        (B_global) | stats (2) ]: what one all-reduce per learn() carries.  The
-        optimizer's gradient, td_error and stats_buf are views of it."""
-        P = self.q_func.flat.numel()
-        P4 = (P + 3) // 4 * 4
-        if self._xbuf is None or self._xbuf.numel() != P4 + B_global + 2:
-            self._xbuf = x = torch.zeros(P4 + B_global + 2, dtype=torch.float32, device=self.device)
-            self.opt['g'] = x[:P]
-            self.td_error = x[P4:P4 + B_global]
-            self.stats_buf = x[P4 + B_global:]
-        return self._xbuf
-
     # --------------------------------------------------------- _optimize
     def _optimize(self, obs, actions, rewards, obs_next, dones, weights=None):   # dqn.py:42-73
         self._gradient(obs, actions, rewards, obs_next, dones, weights)
@@ -605,7 +584,11 @@ class DQNLearner(DeviceLearner):
                    p(self.td_error), None, p(self.stats_buf), st)
         else:
             world = self.dp.world_size
-            self._exchange_image(B * world)
+            if self._xbuf is None or self.td_error.numel() != B * world:
+                # what the one all-reduce per learn() carries: [gradient | pad |
+                # td_all (B_global) | stats (2)], the three as views of it
+                self._xbuf, self.opt['g'], (self.td_error, self.stats_buf) = exchange_image(
+                    self.device, self.q_func.flat.numel(), (B * world, 2))
             L.call('smi_dqn_td_shard', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
                    p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, B * world,
                    self.dp.rank * B, A, float(self.algo.gamma), int(dueling), int(self.double_q),
@@ -614,35 +597,19 @@ class DQNLearner(DeviceLearner):
             net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'])
 
     # ------------------------------------------------------- reference API
-    def _learn_phases(self, batch):
-        """learn() as a generator of the buffers a data-parallel learner must
-        all-reduce (SUM) between its launches: the exchange image, once, after
-        the backward and before smi_adam_clip.  Without dp it yields nothing."""
-        self.current_iteration += 1
-        self._ctx.make_current()
-        if not isinstance(batch['actions'], torch.Tensor) or not batch['actions'].is_cuda:
-            batch = self.preprocess(batch)
-        if self.dp is None:
-            self._learn_device(batch)
-        else:
-            ins = self._inputs(batch)
-            self._gradient(*ins, weights=batch.get('weights'))
-            yield self._xbuf
-            self._ctx.make_current()      # whatever ran on this thread meanwhile
-            self._apply()
-            # samples of the GLOBAL batch: every rank copies the target on the
-            # step the single learner would
-            if self.target_update_tracker.track_increment(
-                    int(ins[0].shape[0]) * self.dp.world_size):
-                self._update_target()
-        self._report_metrics(self.current_iteration)
-        self.periodic_checkpoint(global_steps=self.current_iteration, score=None)
-
-    def learn(self, batch):
-        if self.dp is None:           # the one-GPU frame the off-policy learners share
-            return super().learn(batch)
-        for buf in self._learn_phases(batch):
-            self.dp.allreduce_(buf)
+    def _update_phases(self, batch):
+        """the data-parallel update: the exchange image is all-reduced once,
+        after the backward and before smi_adam_clip"""
+        ins = self._inputs(batch)
+        self._gradient(*ins, weights=batch.get('weights'))
+        yield self._xbuf
+        self._ctx.make_current()      # whatever ran on this thread meanwhile
+        self._apply()
+        # samples of the GLOBAL batch: every rank copies the target on the
+        # step the single learner would
+        if self.target_update_tracker.track_increment(
+                int(ins[0].shape[0]) * self.dp.world_size):
+            self._update_target()
 
     def _inputs(self, batch):
         """(obs, actions, rewards, obs_next, dones) of a device batch"""

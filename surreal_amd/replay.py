@@ -71,28 +71,33 @@ def _low_dim(obs):
     return np.concatenate([np.ravel(v) for v in obs['low_dim'].values()])
 
 
-def pack_pixel_exps(exps, obs_dim, act_dim, camera_shape):
-    """SSAR experience dicts {'obs': [o0, o1], 'action', 'reward', 'done'} with
-    camera observations -> (rows float32 [n, W], pix uint8 [n, C, H, W],
-    pix_next uint8 [n, C, H, W]) on the host; W = 2 * obs_dim + act_dim + 2 and
-    the row layout is UniformReplay's (obs_dim 0: [action | reward | done])."""
+def pack_rows(exps, obs_dim, act_dim):
+    """SSAR experience dicts {'obs': [o0, o1], 'action', 'reward', 'done'} ->
+    rows float32 [n, W] on the host, W = 2 * obs_dim + act_dim + 2, in
+    UniformReplay's layout [obs | action | reward | obs_next | done] (obs_dim
+    0, a pixel-only spec: [action | reward | done])."""
     D, A = int(obs_dim), int(act_dim)
-    shape = tuple(int(c) for c in camera_shape)
-    n = len(exps)
-    rows = np.zeros((n, 2 * D + A + 2), dtype=np.float32)
-    pix = np.zeros((n,) + shape, dtype=np.uint8)
-    pix_next = np.zeros((n,) + shape, dtype=np.uint8)
+    rows = np.zeros((len(exps), 2 * D + A + 2), dtype=np.float32)
     for i, e in enumerate(exps):
-        o0, o1 = e['obs']
         if D:
-            rows[i, :D] = _low_dim(o0)
-            rows[i, D + A + 1:2 * D + A + 1] = _low_dim(o1)
+            rows[i, :D] = _low_dim(e['obs'][0])
+            rows[i, D + A + 1:2 * D + A + 1] = _low_dim(e['obs'][1])
         rows[i, D:D + A] = e['action']
         rows[i, D + A] = e['reward']
         rows[i, 2 * D + A + 1] = float(e['done'])
-        pix[i] = _camera_u8(o0['pixel']['camera0'], shape)
-        pix_next[i] = _camera_u8(o1['pixel']['camera0'], shape)
-    return rows, pix, pix_next
+    return rows
+
+
+def pack_pixel_exps(exps, obs_dim, act_dim, camera_shape):
+    """SSAR experience dicts with camera observations -> (pack_rows' rows, pix
+    uint8 [n, C, H, W], pix_next uint8 [n, C, H, W]) on the host."""
+    shape = tuple(int(c) for c in camera_shape)
+    pix = np.zeros((len(exps),) + shape, dtype=np.uint8)
+    pix_next = np.zeros((len(exps),) + shape, dtype=np.uint8)
+    for i, e in enumerate(exps):
+        pix[i] = _camera_u8(e['obs'][0]['pixel']['camera0'], shape)
+        pix_next[i] = _camera_u8(e['obs'][1]['pixel']['camera0'], shape)
+    return pack_rows(exps, obs_dim, act_dim), pix, pix_next
 
 
 class UniformReplay(object):
@@ -201,17 +206,7 @@ class UniformReplay(object):
             return self._pack_shared(exps)
         if self.is_pixel:
             return pack_pixel_exps(exps, self.obs_dim, self.act_dim, self.camera_shape)
-        D, A = self.obs_dim, self.act_dim
-        out = np.zeros((len(exps), self.width), dtype=np.float32)
-        for i, e in enumerate(exps):
-            o0 = np.concatenate([np.ravel(v) for v in e['obs'][0]['low_dim'].values()])
-            o1 = np.concatenate([np.ravel(v) for v in e['obs'][1]['low_dim'].values()])
-            out[i, :D] = o0
-            out[i, D:D + A] = e['action']
-            out[i, D + A] = e['reward']
-            out[i, D + A + 1:2 * D + A + 1] = o1
-            out[i, 2 * D + A + 1] = float(e['done'])
-        return out
+        return pack_rows(exps, self.obs_dim, self.act_dim)
 
     def _pack_shared(self, exps):
         """pack() of the frame-shared mode: (rows, frames of obs, frames of
@@ -219,45 +214,51 @@ class UniformReplay(object):
         camera0 may be a list of S frames or one (C, H, W) array; an object
         that several experiences share comes back as the same arrays, so
         insert_rows digests it once."""
-        D, A, S = self.obs_dim, self.act_dim, self.frame_stacks
-        rows = np.zeros((len(exps), self.width), dtype=np.float32)
+        S = self.frame_stacks
         pix, pix_next, cache = [], [], {}
-        for i, e in enumerate(exps):
+        for e in exps:
             o0, o1 = e['obs']
-            if D:
-                rows[i, :D] = _low_dim(o0)
-                rows[i, D + A + 1:2 * D + A + 1] = _low_dim(o1)
-            rows[i, D:D + A] = e['action']
-            rows[i, D + A] = e['reward']
-            rows[i, 2 * D + A + 1] = float(e['done'])
             pix.append(split_camera(o0['pixel']['camera0'], S, self.frame_shape, cache))
             pix_next.append(split_camera(o1['pixel']['camera0'], S, self.frame_shape, cache))
-        return rows, pix, pix_next
+        return pack_rows(exps, self.obs_dim, self.act_dim), pix, pix_next
 
-    def _side_frames(self, name, pix, n):
-        """one side of insert_rows -> n lists of S contiguous uint8 frames"""
+    def _check_insert(self, rows, pix, pix_next):
+        """insert_rows of a pixel replay: rows [n, W] come with pix and pix_next,
+        each uint8 (n, C, H, W) (returned as tensors) or, frame-shared, a list
+        of n lists of S frames (returned as given)"""
+        n = rows.shape[0]
+        if pix is None or pix_next is None:
+            raise ValueError('a pixel replay inserts rows together with pix and pix_next')
+        sides = []
+        for name, f in (('pix', pix), ('pix_next', pix_next)):
+            if self.share_frames and isinstance(f, (list, tuple)) and (
+                    not len(f) or isinstance(f[0], (list, tuple))):
+                if len(f) != n:
+                    raise ValueError(f'{name} holds {len(f)} observations for {n} rows')
+            else:
+                f = torch.as_tensor(f)
+                if f.dtype != torch.uint8 or tuple(f.shape) != (n,) + self.camera_shape:
+                    raise ValueError(f'{name} must be uint8 {(n,) + self.camera_shape}, got '
+                                     f'{f.dtype} {tuple(f.shape)}')
+            sides.append(f)
+        if tuple(rows.shape) != (n, self.width):
+            raise ValueError(f'rows must be ({n}, {self.width}), got {tuple(rows.shape)}')
+        return sides
+
+    def _side_frames(self, pix, n):
+        """one checked side of insert_rows -> n lists of S contiguous uint8 frames"""
         S = self.frame_stacks
-        if isinstance(pix, (list, tuple)) and (not len(pix) or isinstance(pix[0], (list, tuple))):
-            if len(pix) != n:
-                raise ValueError(f'{name} holds {len(pix)} observations for {n} rows')
+        if not isinstance(pix, torch.Tensor):
             return [split_camera(f, S, self.frame_shape) for f in pix]
-        t = torch.as_tensor(pix)
-        if t.dtype != torch.uint8 or tuple(t.shape) != (n,) + self.camera_shape:
-            raise ValueError(f'{name} must be uint8 {(n,) + self.camera_shape}, got '
-                             f'{t.dtype} {tuple(t.shape)}')
-        a = np.ascontiguousarray(t.cpu().numpy()).reshape((n, S) + self.frame_shape)
+        a = np.ascontiguousarray(pix.cpu().numpy()).reshape((n, S) + self.frame_shape)
         return [[a[i, k] for k in range(S)] for i in range(n)]
 
     def _insert_shared(self, rows, pix, pix_next):
         rows = np.ascontiguousarray(torch.as_tensor(rows, dtype=torch.float32).cpu().numpy())
         n = rows.shape[0]
-        if pix is None or pix_next is None:
-            raise ValueError('a pixel replay inserts rows together with pix and pix_next')
-        if tuple(rows.shape) != (n, self.width):
-            raise ValueError(f'rows must be ({n}, {self.width}), got {tuple(rows.shape)}')
+        pix, pix_next = self._check_insert(rows, pix, pix_next)
         skip = max(0, n - self.memory_size)
-        sides = list(zip(self._side_frames('pix', pix, n)[skip:],
-                         self._side_frames('pix_next', pix_next, n)[skip:]))
+        sides = list(zip(self._side_frames(pix, n)[skip:], self._side_frames(pix_next, n)[skip:]))
         # raises RuntimeError, with nothing changed, when the store is full
         first, ids, fslots, new = self._alloc.insert(sides, skipped=skip)
         cnt, m, fb = n - skip, len(new), self.fbytes
@@ -308,15 +309,7 @@ class UniformReplay(object):
         rows = torch.as_tensor(rows, dtype=torch.float32)
         n = rows.shape[0]
         if self.is_pixel:
-            if pix is None or pix_next is None:
-                raise ValueError('a pixel replay inserts rows together with pix and pix_next')
-            pix, pix_next = torch.as_tensor(pix), torch.as_tensor(pix_next)
-            for name, t in (('pix', pix), ('pix_next', pix_next)):
-                if t.dtype != torch.uint8 or tuple(t.shape) != (n,) + self.camera_shape:
-                    raise ValueError(f'{name} must be uint8 {(n,) + self.camera_shape}, got '
-                                     f'{t.dtype} {tuple(t.shape)}')
-            if tuple(rows.shape) != (n, self.width):
-                raise ValueError(f'rows must be ({n}, {self.width}), got {tuple(rows.shape)}')
+            pix, pix_next = self._check_insert(rows, pix, pix_next)
         elif pix is not None or pix_next is not None:
             raise ValueError('this replay has no pixel observations (no "pixel" in the obs spec)')
         # more rows than slots: only the last memory_size survive a sequence of
@@ -339,7 +332,30 @@ class UniformReplay(object):
             self._idx = torch.empty(batch_size, dtype=torch.int64, device=self.device)
         return self.rng.randint_device(len(self), batch_size, self._idx)
 
-    def sample(self, batch_size, out=None, rank=0, world=1):
+    def _draw_indices(self, batch_size, rank, world, **draw):
+        """(idx_all, this rank's slice of it, n = batch_size / world): the whole
+        draw of sample_indices(batch_size, **draw), which every rank makes.
+        ValueError, before anything is drawn, unless batch_size % world == 0
+        and 0 <= rank < world."""
+        if world < 1 or not 0 <= rank < world or batch_size % world:
+            raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
+        idx = self.sample_indices(batch_size, **draw)
+        n = batch_size // world
+        return idx, idx[rank * n:(rank + 1) * n], n
+
+    def _draw(self, batch_size, rank, world, **draw):
+        """The one draw path of sample_batch and sample_shard: (idx_all, mine,
+        batch), the batch gathered for this rank's n slots into buffers that
+        are allocated once per n and overwritten by the next call."""
+        idx, mine, n = self._draw_indices(batch_size, rank, world, **draw)
+        if self._out is None or self._out[0].shape[0] != n:
+            self._out = (torch.empty(n, self.width, dtype=torch.float32, device=self.device),)
+            if self.is_pixel:
+                self._out += tuple(torch.empty((n,) + self.camera_shape, dtype=torch.uint8,
+                                               device=self.device) for _ in range(2))
+        return idx, mine, self._gather_batch(mine, n)
+
+    def sample(self, batch_size, out=None, rank=0, world=1, **draw):
         """Returns (indices, rows[batch, W]) on device; rows gathered by kernel.
 
         Data parallel (world > 1, SURVEY §8(e) DDPG row): every rank holds the
@@ -352,11 +368,7 @@ class UniformReplay(object):
         if self.is_pixel:
             raise ValueError('a pixel replay samples rows together with their frames: '
                              'use sample_batch()')
-        if world < 1 or not 0 <= rank < world or batch_size % world:
-            raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
-        idx = self.sample_indices(batch_size)
-        n = batch_size // world
-        mine = idx[rank * n:(rank + 1) * n]
+        _, mine, n = self._draw_indices(batch_size, rank, world, **draw)
         if out is None:
             out = torch.empty(n, self.width, dtype=torch.float32, device=self.device)
         if tuple(out.shape) != (n, self.width) or not out.is_contiguous():
@@ -365,7 +377,7 @@ class UniformReplay(object):
                L.stream(self.device))
         return mine, out
 
-    def sample_batch(self, batch_size, rank=0, world=1):
+    def sample_batch(self, batch_size, rank=0, world=1, **draw):
         """Returns (indices, batch): the draw of sample() (same CPython-exact
         stream, same rank slicing) gathered into the batch DDPGLearner.learn()
         takes.  Low-dim: split(rows), one smi_gather_rows.  Pixel: one
@@ -375,37 +387,19 @@ class UniformReplay(object):
         {'flat_inputs': [n, D]}}, 'obs_next': likewise, 'actions', 'rewards',
         'dones'} ('low_dim' omitted when D == 0).  The output buffers are
         allocated once per n and overwritten by the next call."""
-        idx_all, batch = self._draw_shard(batch_size, rank, world)
-        n = batch_size // world
-        return idx_all[rank * n:(rank + 1) * n], batch
+        _, mine, batch = self._draw(batch_size, rank, world, **draw)
+        return mine, batch
 
-    def _draw_shard(self, batch_size, rank, world):
-        """sample_shard without a subclass's additions (sample_batch's body)"""
-        if world < 1 or not 0 <= rank < world or batch_size % world:
-            raise ValueError(f'batch_size {batch_size} must split evenly over {world} ranks')
-        n = batch_size // world
-        if self._out is None or self._out[0].shape[0] != n:
-            rows = torch.empty(n, self.width, dtype=torch.float32, device=self.device)
-            self._out = (rows,)
-            if self.is_pixel:
-                self._out = (rows,
-                             torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device),
-                             torch.empty((n,) + self.camera_shape, dtype=torch.uint8, device=self.device))
-        idx = self.sample_indices(batch_size)
-        mine = idx[rank * n:(rank + 1) * n]
-        return idx, self._gather_batch(mine, n)
-
-    def sample_shard(self, batch_size, rank, world):
+    def sample_shard(self, batch_size, rank, world, **draw):
         """Returns (idx_all, batch) for one rank of a data-parallel learner
         (DQNLearner / DDPGLearner(dp=...)): idx_all is the WHOLE draw, int64
-        [batch_size] on the device (overwritten by the next draw), and batch is sample_batch's
-        dict for rows [rank * n, (rank + 1) * n) of it, n = batch_size / world,
-        gathered by the same kernels over the index slice.  Every replica draws
-        all batch_size indices from the one CPython-exact stream, so replicas
-        seeded and fed alike keep identical generators.  ValueError (before
-        anything is drawn) unless batch_size % world == 0 and
-        0 <= rank < world."""
-        return self._draw_shard(batch_size, rank, world)
+        [batch_size] on the device (overwritten by the next draw), and batch is
+        sample_batch's dict for rows [rank * n, (rank + 1) * n) of it, n =
+        batch_size / world, gathered by the same kernels over the index slice.
+        Every replica draws all batch_size indices from the one CPython-exact
+        stream, so replicas seeded and fed alike keep identical generators."""
+        idx_all, _, batch = self._draw(batch_size, rank, world, **draw)
+        return idx_all, batch
 
     def _gather_batch(self, mine, n):
         """sample_batch's dict for the n drawn slots `mine`, into self._out"""
@@ -472,7 +466,6 @@ class PrioritizedReplay(UniformReplay):
                                 dtype=torch.float64, device=self.device)
         L.call('smi_per_init', L.ptr(self.tree), self.capacity, L.stream(self.device))
         self.weights = None
-        self._beta = None
 
     @property
     def max_priority(self):
@@ -489,8 +482,6 @@ class PrioritizedReplay(UniformReplay):
 
     def sample_indices(self, batch_size, beta=0):
         """batch_size proportional draws; their weights are kept in self.weights"""
-        if self._beta is not None:                 # sample() / sample_batch() in progress
-            beta, self._beta = self._beta, None
         if self._idx is None or self._idx.numel() != batch_size:
             self._idx = torch.empty(batch_size, dtype=torch.int64, device=self.device)
             self.weights = torch.empty(batch_size, dtype=torch.float32, device=self.device)
@@ -506,51 +497,28 @@ class PrioritizedReplay(UniformReplay):
                              'a data-parallel rank calls sample_shard(batch_size, rank, world), '
                              'which keeps the replicated trees identical')
 
+    def _draw(self, batch_size, rank, world, beta=0):
+        """UniformReplay._draw over the proportional draw: smi_per_sample draws
+        the whole batch on every rank, and batch['weights'] is this rank's
+        slice, float32 [n, 1], where the learners read it (the weights are
+        normalised by the tree minimum, not by the batch, so they do not depend
+        on the shard).  After learn(), every rank of sample_shard() calls
+        update_priorities_from_td(idx_all, learner.td_error)."""
+        idx_all, mine, batch = super()._draw(batch_size, rank, world, beta=beta)
+        n = batch_size // world
+        batch['weights'] = self.weights[rank * n:(rank + 1) * n].view(-1, 1)
+        return idx_all, mine, batch
+
     def sample(self, batch_size, out=None, rank=0, world=1, beta=0):
         """(indices, rows, weights [batch] float32) on the device"""
         self._one_rank(world)
-        self._beta = beta
-        try:
-            idx, rows = super().sample(batch_size, out=out)
-        finally:
-            self._beta = None
+        idx, rows = super().sample(batch_size, out=out, beta=beta)
         return idx, rows, self.weights
 
     def sample_batch(self, batch_size, rank=0, world=1, beta=0):
-        """UniformReplay.sample_batch over the prioritized draw; the weights go
-        under batch['weights'] as float32 [n, 1], where DDPGLearner.learn()
-        reads them.  Pixel mode gathers through smi_replay_gather unchanged."""
+        """UniformReplay.sample_batch over the prioritized draw, for one rank"""
         self._one_rank(world)
-        if not self.is_pixel:
-            if self._out is None or self._out[0].shape[0] != batch_size:
-                self._out = (torch.empty(batch_size, self.width, dtype=torch.float32,
-                                         device=self.device),)
-            idx, rows, _ = self.sample(batch_size, out=self._out[0], beta=beta)
-            batch = self.split(rows)
-        else:
-            self._beta = beta
-            try:
-                idx, batch = super().sample_batch(batch_size)
-            finally:
-                self._beta = None
-        batch['weights'] = self.weights.view(-1, 1)
-        return idx, batch
-
-    def sample_shard(self, batch_size, rank, world, beta=0):
-        """UniformReplay.sample_shard over the proportional draw: smi_per_sample
-        draws the whole batch on every rank, and batch['weights'] is this
-        rank's slice, float32 [n, 1] (the weights are normalised by the tree
-        minimum, not by the batch, so they do not depend on the shard).  After
-        learn(), every rank calls update_priorities_from_td(idx_all,
-        learner.td_error)."""
-        self._beta = beta
-        try:
-            idx_all, batch = super().sample_shard(batch_size, rank, world)
-        finally:
-            self._beta = None
-        n = batch_size // world
-        batch['weights'] = self.weights[rank * n:(rank + 1) * n].view(-1, 1)
-        return idx_all, batch
+        return super().sample_batch(batch_size, beta=beta)
 
     def _indices(self, indices):
         if isinstance(indices, torch.Tensor):

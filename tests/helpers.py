@@ -4,7 +4,8 @@ import copy
 import numpy as np
 import torch
 
-from surreal_amd.config import PPO_DEFAULT_LEARNER_CONFIG, Config, gym_env_config
+from surreal_amd.config import (DDPG_DEFAULT_LEARNER_CONFIG, PPO_DEFAULT_LEARNER_CONFIG, Config,
+                                gym_env_config)
 
 
 def ppo_config(B=64, T=50, mode='clip', use_z_filter=True, hidden=(64, 64), lam=0.95,
@@ -41,6 +42,38 @@ def ppo_config(B=64, T=50, mode='clip', use_z_filter=True, hidden=(64, 64), lam=
 
 def env_config(D=17, A=6):
     return gym_env_config(D, A)
+
+
+def ddpg_config(B=512, target='hard', clip_critic=False, layernorm=False):
+    lc = copy.deepcopy(DDPG_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = B
+    lc.model.use_layernorm = layernorm
+    lc.algo.network.clip_critic_gradient = clip_critic
+    if target == 'soft':
+        lc.algo.network.target_update = {'type': 'soft', 'tau': 1e-3}
+    else:
+        lc.algo.network.target_update = {'type': 'hard', 'interval': 2}
+    return lc
+
+
+def per_cfg(B=64, memory_size=200, double=False, action_reg=False):
+    """ddpg_config for a learner fed by a PrioritizedReplay"""
+    lc = ddpg_config(B, 'hard')
+    lc.replay.memory_size = memory_size
+    lc.replay.sampling_start_size = 10
+    lc.replay.alpha = 0.6
+    lc.algo.network.use_double_critic = double
+    lc.algo.network.use_action_regularization = action_reg
+    return lc
+
+
+def replay_rows(n, D, A, seed):
+    """n packed replay rows [obs | action | reward | obs_next | done] on the host"""
+    g = torch.Generator().manual_seed(seed)
+    rows = torch.randn(n, 2 * D + A + 2, generator=g)
+    rows[:, D:D + A] = torch.tanh(rows[:, D:D + A])
+    rows[:, 2 * D + A + 1] = (torch.rand(n, generator=g) < 0.1).float()
+    return rows
 
 
 def copy_weights_to_oracle(learner, ref):

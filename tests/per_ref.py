@@ -179,3 +179,23 @@ def seed_stream(advanced):
         for _ in range(m):
             random.randint(0, n - 1)
     return mt_state()
+
+
+def ref_from_device(tree, cap):
+    """per_ref tree rebuilt from the device's own leaves (every ancestor
+    recomputed in Python) and max_priority"""
+    t = tree.cpu().numpy()
+    return PerRef.from_leaves(cap, t[2 * cap::2], max_priority=float(t[0])), t
+
+
+def check_drawn_leaves(tree, cap, want, td):
+    """the leaves of the drawn slots are (|td| + 1e-6) ** 0.6 (a repeated slot
+    keeps its last) to 2 ulp = 2^-51 relative: the device's fp64 pow against
+    the host's (test_gpu_dqn.py::test_prioritized_replay_loop)"""
+    leaves = tree.cpu().numpy()[2 * cap::2]
+    last = {s: (abs(float(v)) + 1e-6) ** 0.6 for s, v in zip(want, td)}
+    slots = np.array(sorted(last))
+    exp = np.array([last[s] for s in slots])
+    rel = np.abs(leaves[slots] - exp) / exp
+    print('leaf max relative difference from the host pow:', rel.max())
+    assert (rel <= 2.0 ** -51).all()

@@ -20,7 +20,7 @@ import torch.multiprocessing as mp
 import torch.nn as nn
 
 from oracle import ddpg_ref as R
-from tests.test_cpu_dist import _free_port
+from tests.dp_harness import free_port as _free_port
 
 B_LOC, D, A, STEPS = 64, 17, 6, 3
 

@@ -12,8 +12,9 @@ import torch
 
 from oracle import ddpg_ref as R
 from surreal_amd import synthetic
+from tests.helpers import per_cfg as _per_cfg
 from tests.test_gpu_ddpg import _load_ddpg
-from tests.test_gpu_per import WeightedRef, _per_cfg
+from tests.test_gpu_per import WeightedRef
 
 E_ARG = -1
 

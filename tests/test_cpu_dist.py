@@ -5,7 +5,6 @@ segments, weights per-row gradients by 1/B_global, SUM-all-reduces gradients
 for early stopping / the adapt penalty, and the ZFilter column sums.  The
 result must equal the single-process oracle on the concatenated batch."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -14,14 +13,7 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 from oracle import ppo_ref as R
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
+from tests.dp_harness import free_port as _free_port
 
 
 def _dp_learn(ref, group, obs, obs_next, actions, rewards, dones, pds, B_g):

@@ -151,7 +151,8 @@ def test_learner_and_agent_raise_before_touching_a_device():
     from surreal_amd.agent import QAgentBatch
     from surreal_amd.dqn import DQNLearner
     lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
-    assert 'dp' not in inspect.signature(DQNLearner.__init__).parameters
+    dp = inspect.signature(DQNLearner.__init__).parameters['dp']
+    assert dp.kind is inspect.Parameter.KEYWORD_ONLY and dp.default is None
     with pytest.raises(ConfigError, match='discrete'):
         DQNLearner(lc, gym_env_config(5, 3))
     bad = copy.deepcopy(lc)

@@ -1,7 +1,6 @@
 """DDPG learner step (ddpg.py:244-428) on the MFMA GEMM layers vs the CPU
 oracle, plus the uniform replay (CPython-exact indices) feeding it.  Tolerance
 as test_gpu_ppo.py (1e-5 relative, scale floor, Adam sign-flip budget)."""
-import copy
 import random
 
 import numpy as np
@@ -11,22 +10,11 @@ import torch
 from oracle import ddpg_ref as R
 from surreal_amd import _lib as L
 from surreal_amd import synthetic
-from surreal_amd.config import DDPG_DEFAULT_LEARNER_CONFIG, gym_env_config
+from surreal_amd.config import gym_env_config
 from surreal_amd.ddpg import DDPGLearner
+from tests.helpers import ddpg_config as _cfg
 
 pytestmark = pytest.mark.gpu
-
-
-def _cfg(B=512, target='hard', clip_critic=False, layernorm=False):
-    lc = copy.deepcopy(DDPG_DEFAULT_LEARNER_CONFIG)
-    lc.replay.batch_size = B
-    lc.model.use_layernorm = layernorm
-    lc.algo.network.clip_critic_gradient = clip_critic
-    if target == 'soft':
-        lc.algo.network.target_update = {'type': 'soft', 'tau': 1e-3}
-    else:
-        lc.algo.network.target_update = {'type': 'hard', 'interval': 2}
-    return lc
 
 
 def _sync_weights(learner, ref):

@@ -16,16 +16,13 @@ indices per step on the device and gathers its 256-row slice
     fp64 oracle's single-learner step on the 512 sampled rows
     (tests/test_gpu_ddpg.py ddpg_envelope_check), including the TD3 smoothing
     noise, which every rank draws for the global batch and slices."""
-import os
 import random
-import tempfile
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-from tests.test_gpu_dp_procs import _free_port
+from tests.dp_harness import spawn_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -59,12 +56,7 @@ def _split(rows):
             'obs_next': rows[:, D + A + 1:2 * D + A + 1], 'dones': rows[:, 2 * D + A + 1:]}
 
 
-def _worker(rank, world, port, target, td3, clip, outdir):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def _worker(rank, world, target, td3, clip):
     from surreal_amd.config import gym_env_config
     from surreal_amd.ddpg import DDPGLearner
     from surreal_amd.learner import TorchDistAllReduce
@@ -82,8 +74,7 @@ def _worker(rank, world, port, target, td3, clip, outdir):
         np.random.seed(100 + it)
         learner.learn(rep.split(rows))
         res.append({'idx': idx.cpu(), 'state': _ddpg_state(learner), 'stats': learner.last_stats()})
-    torch.save({'init': init, 'res': res}, os.path.join(outdir, f'rank{rank}.pt'))
-    dist.destroy_process_group()
+    return {'init': init, 'res': res}
 
 
 @pytest.mark.timeout(600)
@@ -92,9 +83,7 @@ def _worker(rank, world, port, target, td3, clip, outdir):
 def test_two_process_ddpg_dp_matches_single_learner(target, td3, clip):
     from tests.test_gpu_ddpg import ddpg_envelope_check
     world = 2
-    with tempfile.TemporaryDirectory() as outdir:
-        mp.spawn(_worker, args=(world, _free_port(), target, td3, clip, outdir), nprocs=world, join=True)
-        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True) for r in range(world)]
+    out = spawn_ranks(_worker, world, target, td3, clip)
     # one learner's index stream (uniform_replay.py:43-47)
     random.seed(SEED)
     rows = _rows()

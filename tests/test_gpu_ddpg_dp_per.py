@@ -1,7 +1,7 @@
 """Data-parallel DDPGLearner with a prioritized replay: ranks are simulated in
 one process by driving each learner's _learn_phases in lockstep and summing the
-yielded exchange images, as the all-reduce does (tests/test_gpu_dp.py::
-_lockstep).  N ranks on 96 / N rows each must end bit-identical, hold the TD
+yielded exchange images, as the all-reduce does (tests/dp_harness.py
+lockstep).  N ranks on 96 / N rows each must end bit-identical, hold the TD
 errors of the whole draw in draw order, and land where one learner on the 96
 rows lands: rank 0 goes through the bar of tests/test_gpu_per.py::
 test_random_weights_on_the_envelope against the fp64 weighted oracle on the
@@ -19,20 +19,14 @@ from surreal_amd.replay import PrioritizedReplay
 from tests import parity as P
 from tests import per_ref as PR
 from tests import test_gpu_ddpg as T
-from tests.test_gpu_dp import _lockstep
-from tests.test_gpu_per import WeightedRef, _per_cfg
+from tests.dp_harness import Group as _Group, cut as _cut, lockstep as _lockstep, pad4
+from tests.dp_harness import to_dev as _dev
+from tests.helpers import per_cfg as _per_cfg, replay_rows as _rows
+from tests.test_gpu_per import WeightedRef
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 BG, D, A = 96, 17, 6
-
-
-class _Group(object):
-    def __init__(self, world, rank):
-        self.world_size, self.rank = world, rank
-
-    def allreduce_(self, t):
-        raise AssertionError('ranks are driven through _learn_phases in this test')
 
 
 class _Seeded(object):
@@ -50,10 +44,6 @@ class _Seeded(object):
 
 def _ranks(lc_of, ec, world, seed=2):
     return [DDPGLearner(lc_of(BG // world), ec, seed=seed, dp=_Group(world, r)) for r in range(world)]
-
-
-def _cut(d, r, n):
-    return {k: v[r * n:(r + 1) * n].contiguous() for k, v in d.items()}
 
 
 def _step(learners, shards, seed):
@@ -81,10 +71,6 @@ def _batch(it, B=BG):
     return {k: v.numpy() for k, v in synthetic.ddpg_batch(B, D, A, seed=it).items()}
 
 
-def _dev(b):
-    return {k: torch.as_tensor(x, dtype=torch.float32).to(DEV) for k, x in b.items()}
-
-
 # --------------------------------------------------------------- envelope
 @pytest.mark.parametrize('world', [2, 3, 4])
 @pytest.mark.parametrize('td3', [False, True], ids=['plain', 'td3'])
@@ -107,7 +93,7 @@ def test_dp_random_weights_on_the_envelope(td3, world):
         v.ref.weight_noise = v._noisy if v.kind == 'ulp' else None
     # the exchange image: [critic | critic2 | pad to 4 floats | td_all]
     ng = l0.model.critic.flat.numel() * (2 if td3 else 1)
-    ng4 = (ng + 3) // 4 * 4
+    ng4 = pad4(ng)
     report = {}
     for it, b in enumerate(batches):
         dev = _dev(b)
@@ -158,14 +144,6 @@ def test_dp_unit_weights_change_nothing():
 
 
 # ---------------------------------------------------------------- PER loop
-def _rows(n, D, A, seed):
-    g = torch.Generator().manual_seed(seed)
-    rows = torch.randn(n, 2 * D + A + 2, generator=g)
-    rows[:, D:D + A] = torch.tanh(rows[:, D:D + A])
-    rows[:, 2 * D + A + 1] = (torch.rand(n, generator=g) < 0.1).float()
-    return rows
-
-
 def _per_step(reps, learners, Bg, beta, seed, want=None):
     """sample_shard -> learn -> update_priorities_from_td on every replica"""
     world = len(reps)
@@ -202,19 +180,10 @@ def test_dp_prioritized_replay_loop():
     cap = reps[0].capacity
     random.seed(seed)
     for it in range(3):
-        t = reps[0].tree.cpu().numpy()
-        ref = PR.PerRef.from_leaves(cap, t[2 * cap::2], max_priority=float(t[0]))
-        want, _ = ref.sample(n, BG, 0.4)
+        want, _ = PR.ref_from_device(reps[0].tree, cap)[0].sample(n, BG, 0.4)
         _per_step(reps, learners, BG, 0.4, it, want)
         _assert_same(learners[0], learners[1], it)
-        td = learners[0].td_error.cpu().numpy()
-        leaves = reps[0].tree.cpu().numpy()[2 * cap::2]
-        last = {s: (abs(float(v)) + 1e-6) ** 0.6 for s, v in zip(want, td)}
-        slots = np.array(sorted(last))
-        exp = np.array([last[s] for s in slots])
-        rel = np.abs(leaves[slots] - exp) / exp
-        print('leaf max relative difference from the host pow:', rel.max())
-        assert (rel <= 2.0 ** -51).all()
+        PR.check_drawn_leaves(reps[0].tree, cap, want, learners[0].td_error.cpu().numpy())
 
 
 def test_dp_pixel_frame_shared_loop():

@@ -9,15 +9,12 @@ steps.  Required: the ranks end bit-identical (draws, weights, parameters,
 targets, statistics, TD errors and the priority trees), and rank 0's states are
 bit-equal to the one-process _lockstep simulation of the same case
 (tests/test_gpu_ddpg_dp_per.py), whose rank 0 that file holds to the envelope."""
-import os
-import tempfile
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-from tests.test_gpu_dp_procs import _free_port
+from tests.dp_harness import Group, spawn_ranks
+from tests.helpers import per_cfg, replay_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -25,16 +22,14 @@ BG, D, A, NROWS, SEED, STEPS, BETA, WORLD = 96, 17, 6, 150, 4321, 3, 0.4, 2
 
 
 def _cfg(B):
-    from tests.test_gpu_per import _per_cfg
-    return _per_cfg(B, 200, double=True, action_reg=True)
+    return per_cfg(B, 200, double=True, action_reg=True)
 
 
 def _replica():
     from surreal_amd.config import gym_env_config
     from surreal_amd.replay import PrioritizedReplay
-    from tests.test_gpu_ddpg_dp_per import _rows
     rep = PrioritizedReplay(_cfg(BG // WORLD), gym_env_config(D, A), seed=SEED, device='cuda:0')
-    rep.insert_rows(_rows(NROWS, D, A, 3))
+    rep.insert_rows(replay_rows(NROWS, D, A, 3))
     return rep
 
 
@@ -45,12 +40,7 @@ def _record(rep, idx_all, learner):
             'td': learner.td_error.cpu().clone(), 'tree': rep.tree.cpu().clone()}
 
 
-def _worker(rank, world, port, outdir):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def _worker(rank, world):
     from surreal_amd.config import gym_env_config
     from surreal_amd.ddpg import DDPGLearner
     from surreal_amd.learner import TorchDistAllReduce
@@ -65,18 +55,17 @@ def _worker(rank, world, port, outdir):
         learner.learn(batch)
         rep.update_priorities_from_td(idx_all, learner.td_error, eps=1e-6)
         res.append(_record(rep, idx_all, learner))
-    torch.save(res, os.path.join(outdir, f'rank{rank}.pt'))
-    dist.destroy_process_group()
+    return res
 
 
 def _simulate():
     """the same case with both ranks in this process (rank 0's constructor seed)"""
     from surreal_amd.config import gym_env_config
     from surreal_amd.ddpg import DDPGLearner
-    from tests.test_gpu_ddpg_dp_per import _Group, _step
+    from tests.test_gpu_ddpg_dp_per import _step
     reps = [_replica() for _ in range(WORLD)]
     learners = [DDPGLearner(_cfg(BG // WORLD), gym_env_config(D, A), seed=5, device='cuda:0',
-                            dp=_Group(WORLD, r)) for r in range(WORLD)]
+                            dp=Group(WORLD, r)) for r in range(WORLD)]
     res = []
     for it in range(STEPS):
         draws = [rep.sample_shard(BG, r, WORLD, beta=BETA) for r, rep in enumerate(reps)]
@@ -97,10 +86,7 @@ def _assert_records_equal(a, b, tag):
 
 @pytest.mark.timeout(600)
 def test_two_process_ddpg_dp_per_matches_the_lockstep_simulation():
-    with tempfile.TemporaryDirectory() as outdir:
-        mp.spawn(_worker, args=(WORLD, _free_port(), outdir), nprocs=WORLD, join=True)
-        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True)
-               for r in range(WORLD)]
+    out = spawn_ranks(_worker, WORLD)
     sim = _simulate()
     for it in range(STEPS):
         r0, r1 = out[0][it], out[1][it]

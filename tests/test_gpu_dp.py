@@ -11,50 +11,10 @@ import torch
 from oracle import ppo_ref as R
 from surreal_amd import synthetic
 from surreal_amd.learner import PPOLearner
+from tests.dp_harness import Group as _Group, cut, lockstep as _lockstep, spawn_ranks
 from tests.helpers import copy_weights_to_oracle, env_config, max_rel_err, oracle_batch, ppo_config
 
 pytestmark = pytest.mark.gpu
-
-
-class _Group(object):
-    def __init__(self, n):
-        self.world_size = n
-
-    def allreduce_(self, t):
-        raise AssertionError('ranks are driven through _learn_phases in this test')
-
-
-def _shard(batch, lo, hi):
-    def cut(x):
-        if x is None:
-            return None
-        if isinstance(x, dict):
-            return {k: cut(v) for k, v in x.items()}
-        if isinstance(x, list):
-            return [cut(v) for v in x]
-        return x[lo:hi].contiguous()
-    return cut(batch)
-
-
-def _lockstep(learners, shards):
-    gens = [l._learn_phases(s) for l, s in zip(learners, shards)]
-    nphase = 0
-    while True:
-        bufs, done = [], 0
-        for g in gens:
-            try:
-                bufs.append(next(g))
-            except StopIteration:
-                done += 1
-        if done:
-            assert done == len(gens)
-            return nphase
-        total = bufs[0].clone()
-        for b in bufs[1:]:
-            total += b
-        for b in bufs:
-            b.copy_(total)
-        nphase += 1
 
 
 @pytest.mark.parametrize('mode,world,B_loc,rf', [('clip', 2, 32, False), ('adapt', 2, 32, False),
@@ -83,7 +43,7 @@ def test_dp_equals_global_batch(mode, world, B_loc, rf):
     for it in range(2):
         batch = synthetic.ppo_batch(B_loc * world, T, D, A, seed=300 + it)
         dev = synthetic.to_device(batch, 'cuda')
-        shards = [_shard(dev, r * B_loc, (r + 1) * B_loc) for r in range(world)]
+        shards = [cut(dev, r, B_loc) for r in range(world)]
         nphase = _lockstep(learners, shards)
         assert nphase == int(rf) + 1 + max(11, 10) + 1   # [reward sums,] moments, epochs, z-filter
         rstats = ref.learn(oracle_batch(batch))
@@ -136,13 +96,7 @@ def test_dp_world1_matches_fused_path():
         assert max_rel_err(phased.model.critic.flat.cpu(), fused.model.critic.flat.cpu()) < 1e-4
 
 
-def _capture_worker(rank, port, outdir):
-    import os
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('nccl', rank=0, world_size=1)
+def _capture_worker(rank, world):
     from surreal_amd.learner import TorchDistAllReduce
     from tests.test_gpu_boundary import _same, _state
     dp = TorchDistAllReduce()
@@ -163,9 +117,7 @@ def _capture_worker(rank, port, outdir):
         ok = _same(_state(eager), _state(graph)) and eager.last_stats() == graph.last_stats()
         ok = ok and all(torch.equal(v, graph.optimizer_state()[k]) for k, v in eager.optimizer_state().items())
         same.append(bool(ok))
-    torch.save({'capturable': dp.capturable, 'captured': graph._graph is not None, 'same': same},
-               os.path.join(outdir, 'res.pt'))
-    dist.destroy_process_group()
+    return {'capturable': dp.capturable, 'captured': graph._graph is not None, 'same': same}
 
 
 @pytest.mark.timeout(300)
@@ -175,12 +127,6 @@ def test_dp_learn_captured_with_rccl_allreduce_bit_exact():
     its launches: bit-identical to the same data-parallel learner run eagerly,
     over several learns with a publish between them (a rank of a
     strong-scaled job issues ~400 launches and 33 collectives per learn)."""
-    import os
-    import tempfile
-    import torch.multiprocessing as mp
-    from tests.test_gpu_dp_procs import _free_port
-    with tempfile.TemporaryDirectory() as d:
-        mp.spawn(_capture_worker, args=(_free_port(), d), nprocs=1, join=True)
-        res = torch.load(os.path.join(d, 'res.pt'), weights_only=True)
+    res, = spawn_ranks(_capture_worker, 1, backend='nccl')
     assert res['capturable'] and res['captured'], res
     assert all(res['same']), res

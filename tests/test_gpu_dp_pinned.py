@@ -16,52 +16,26 @@ segments, adapt over two learns and clip; C5 (C3 + camera stem, FC 256) as
 the c3_adapt fixture as 4 x 256 and 8 x 128 segments (one process per rank, all
 on cuda:0: ranks share the GPU, the exchange is gloo over host memory).
 """
-import os
-import socket
-import tempfile
-
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from tests.dp_harness import cut, spawn_ranks
 
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
-
-
-def _worker(rank, world, port, case, outdir):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def _worker(rank, world, case):
     from surreal_amd import synthetic
     from surreal_amd.learner import TorchDistAllReduce
     from tests import parity as P
     from tests.test_gpu_parity_pinned import _used, fixture_learner
     meta, fx, c, st, learner = fixture_learner(case, dp=TorchDistAllReduce())
     B = learner.batch_size
-    lo, hi = rank * B, (rank + 1) * B
     res = []
     for it in range(len(c['batch_seeds'])):
         full = P.case_batch(case, it)
-
-        def cut(x):
-            if x is None:
-                return None
-            if isinstance(x, dict):
-                return {k: cut(v) for k, v in x.items()}
-            if isinstance(x, list):
-                return [cut(v) for v in x]
-            return x[lo:hi].contiguous()
-        cap = P.learn_capture(learner, synthetic.to_device(cut(full), 'cuda:0'))
+        cap = P.learn_capture(learner, synthetic.to_device(cut(full, rank, B), 'cuda:0'))
         adv, ret = _used(learner)
         r = {'stats': learner.last_stats(), 'adv': torch.from_numpy(adv), 'ret': torch.from_numpy(ret)}
         if rank == 0:
@@ -69,8 +43,7 @@ def _worker(rank, world, port, case, outdir):
         else:
             r['final'] = cap['final']
         res.append(r)
-    torch.save(res, os.path.join(outdir, f'rank{rank}.pt'))
-    dist.destroy_process_group()
+    return res
 
 
 @pytest.mark.timeout(900)
@@ -79,10 +52,7 @@ def _worker(rank, world, port, case, outdir):
 def test_dp_ranks_match_global_fixture(case, world):
     from tests import parity as P
     from tests.helpers import oracle_batch
-    with tempfile.TemporaryDirectory() as outdir:
-        mp.spawn(_worker, args=(world, _free_port(), case, outdir), nprocs=world, join=True)
-        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True)
-               for r in range(world)]
+    out = spawn_ranks(_worker, world, case)
     meta, fx = P.load_fixture(case)
     c = P.CASES[case]
     lc = c['cfg']()

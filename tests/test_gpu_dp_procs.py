@@ -8,27 +8,15 @@ parameters, equal to the CPU oracle's learn() on the concatenated global batch
 more epochs the CNN's ReLU masks (pre-activations within fp32 noise of 0) and
 Adam's sign-normalised first steps let any two fp32 implementations drift
 apart by ~lr per affected entry (tools/dbg_px.py measures it)."""
-import os
-import socket
-import tempfile
-
-import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
+
+from tests.dp_harness import cut, spawn_ranks
 
 pytestmark = pytest.mark.gpu
 
 B_LOC, T, D, A = 24, 10, 17, 6
 CAM = (3, 84, 84)
-
-
-def _free_port():
-    s = socket.socket()
-    s.bind(('127.0.0.1', 0))
-    p = s.getsockname()[1]
-    s.close()
-    return p
 
 
 def _cfg(mode, rnn):
@@ -40,12 +28,7 @@ def _cfg(mode, rnn):
     return ppo_config(B=B_LOC, T=T, mode=mode, use_z_filter=True)
 
 
-def _worker(rank, world, port, mode, outdir, rnn):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def _worker(rank, world, mode, rnn):
     from surreal_amd import synthetic
     from surreal_amd.learner import PPOLearner, TorchDistAllReduce
     from surreal_amd.config import pixel_env_config
@@ -64,17 +47,7 @@ def _worker(rank, world, port, mode, outdir, rnn):
                                    rnn_hidden=40 if rnn else None,
                                    pixel=CAM if rnn == 'pixel' else None)
         dev = synthetic.to_device(full, 'cuda:0')
-        lo, hi = rank * B_LOC, (rank + 1) * B_LOC
-
-        def cut(x):
-            if x is None:
-                return None
-            if isinstance(x, dict):
-                return {k: cut(v) for k, v in x.items()}
-            if isinstance(x, list):
-                return [cut(v) for v in x]
-            return x[lo:hi].contiguous()
-        learner.learn(cut(dev))
+        learner.learn(cut(dev, rank, B_LOC))
         st = learner.last_stats()
         r = {'actor': learner.model.actor.flat.cpu(), 'critic': learner.model.critic.flat.cpu(),
              'zsum': learner.model.z_filter.running_sum.cpu(), 'stats': st}
@@ -83,8 +56,7 @@ def _worker(rank, world, port, mode, outdir, rnn):
         if rnn == 'pixel':
             r['cnn'] = learner.model.cnn_stem.flat.cpu()
         res.append(r)
-    torch.save({'init': init, 'res': res}, os.path.join(outdir, f'rank{rank}.pt'))
-    dist.destroy_process_group()
+    return {'init': init, 'res': res}
 
 
 @pytest.mark.parametrize('mode,rnn', [('adapt', False), ('clip', False), ('adapt', True),
@@ -96,9 +68,7 @@ def test_two_process_dp_learn_matches_oracle(mode, rnn):
                                seq_flat)
     from tests.test_gpu_ppo import _compare_params
     world = 2
-    with tempfile.TemporaryDirectory() as outdir:
-        mp.spawn(_worker, args=(world, _free_port(), mode, outdir, rnn), nprocs=world, join=True)
-        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True) for r in range(world)]
+    out = spawn_ranks(_worker, world, mode, rnn)
     lc = _cfg(mode, rnn)
     lc.replay.batch_size = B_LOC * world
     ref = R.PPOLearnerRef(lc, D, A, pixel=CAM if rnn == 'pixel' else None)

@@ -193,22 +193,13 @@ def test_prioritized_replay_loop():
     random.seed(seed)
     top = 1.0
     for it in range(2):
-        t = rep.tree.cpu().numpy()          # the device's own leaves, every ancestor recomputed
-        ref = PR.PerRef.from_leaves(cap, t[2 * cap::2], max_priority=float(t[0]))
-        want, _ = ref.sample(n, B, 0.4)
+        want, _ = PR.ref_from_device(rep.tree, cap)[0].sample(n, B, 0.4)
         idx, batch = rep.sample_batch(B, beta=0.4)
         assert idx.cpu().tolist() == want, it
         learner.learn(batch)
         rep.update_priorities_from_td(idx, learner.td_error)
         td = learner.td_error.cpu().numpy()
-        tree = rep.tree.cpu().numpy()
-        leaves = tree[2 * cap::2]
-        last = {s: (abs(float(t)) + 1e-6) ** 0.6 for s, t in zip(want, td)}
-        slots = np.array(sorted(last))
-        exp = np.array([last[s] for s in slots])
-        rel = np.abs(leaves[slots] - exp) / exp
-        print('leaf max relative difference from the host pow:', rel.max())
-        assert (rel <= 2.0 ** -51).all()
+        PR.check_drawn_leaves(rep.tree, cap, want, td)
         top = max(top, float(np.abs(td.astype(np.float64)).max()) + 1e-6)
         assert rep.max_priority == top
 

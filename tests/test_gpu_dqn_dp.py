@@ -1,13 +1,12 @@
 """Data-parallel DQNLearner: ranks are simulated in one process by driving each
 learner's _learn_phases in lockstep and summing the yielded exchange images, as
-the all-reduce does (tests/test_gpu_dp.py::_lockstep).  N ranks on B / N rows
+the all-reduce does (tests/dp_harness.py lockstep).  N ranks on B / N rows
 each must land where one learner on the B rows lands: rank 0 goes through the
 single learner's own envelope check on the GLOBAL batches, unchanged, and the
 ranks must be bit-identical to each other, priority trees included."""
 import copy
 import random
 
-import numpy as np
 import pytest
 import torch
 
@@ -18,18 +17,10 @@ from tests import dqn_ref as R
 from tests import parity as P
 from tests import per_ref as PR
 from tests import qconv_ref as Q
-from tests.test_gpu_dp import _lockstep
+from tests.dp_harness import Group as _Group, cut as _cut, lockstep as _lockstep, pad4
+from tests.dp_harness import to_dev as _dev
 
 pytestmark = pytest.mark.gpu
-DEV = 'cuda'
-
-
-class _Group(object):
-    def __init__(self, world, rank):
-        self.world_size, self.rank = world, rank
-
-    def allreduce_(self, t):
-        raise AssertionError('ranks are driven through _learn_phases in this test')
 
 
 def _rank_config(lc, world):
@@ -47,15 +38,6 @@ def _load(learner, init):
 def _ranks(lc, ec, init, world):
     return [_load(DQNLearner(_rank_config(lc, world), ec, dp=_Group(world, r)), init)
             for r in range(world)]
-
-
-def _dev(b):
-    return {k: torch.as_tensor(v).to(DEV) if torch.as_tensor(v).dtype == torch.uint8
-            else torch.as_tensor(v, dtype=torch.float32).to(DEV) for k, v in b.items()}
-
-
-def _cut(d, r, n):
-    return {k: v[r * n:(r + 1) * n] for k, v in d.items()}
 
 
 def _state(learner):
@@ -78,7 +60,7 @@ def _run_lockstep(learners, batches, Bg):
         assert _lockstep(learners, [_cut(d, r, n) for r in range(world)]) == 1    # ONE exchange
         l0 = learners[0]
         assert tuple(l0.td_error.shape) == (Bg,)
-        P4 = (l0.q_func.flat.numel() + 3) // 4 * 4
+        P4 = pad4(l0.q_func.flat.numel())
         base = l0._xbuf.data_ptr()
         assert l0.opt['g'].data_ptr() == base and l0.td_error.data_ptr() == base + 4 * P4
         assert l0.stats_buf.data_ptr() == base + 4 * (P4 + Bg) and l0._xbuf.numel() == P4 + Bg + 2
@@ -162,9 +144,7 @@ def test_dp_prioritized_replay_loop(make):
     cap = reps[0].capacity
     random.seed(seed)
     for it in range(3):
-        t = reps[0].tree.cpu().numpy()
-        ref = PR.PerRef.from_leaves(cap, t[2 * cap::2], max_priority=float(t[0]))
-        want, _ = ref.sample(n, Bg, 0.4)
+        want, _ = PR.ref_from_device(reps[0].tree, cap)[0].sample(n, Bg, 0.4)
         shards, idxs = [], []
         for r, rep in enumerate(reps):
             idx_all, batch = rep.sample_shard(Bg, r, world, beta=0.4)
@@ -192,14 +172,7 @@ def test_dp_prioritized_replay_loop(make):
         assert torch.equal(reps[0].tree, reps[1].tree), it
         assert torch.equal(reps[0].rng.dev, reps[1].rng.dev), it
         assert reps[0].max_priority == reps[1].max_priority
-        td = learners[0].td_error.cpu().numpy()
-        leaves = reps[0].tree.cpu().numpy()[2 * cap::2]
-        last = {s: (abs(float(v)) + 1e-6) ** 0.6 for s, v in zip(want, td)}
-        slots = np.array(sorted(last))
-        exp = np.array([last[s] for s in slots])
-        rel = np.abs(leaves[slots] - exp) / exp
-        print('leaf max relative difference from the host pow:', rel.max())
-        assert (rel <= 2.0 ** -51).all()
+        PR.check_drawn_leaves(reps[0].tree, cap, want, learners[0].td_error.cpu().numpy())
 
 
 # ---------------------------------------------------------- unchanged paths

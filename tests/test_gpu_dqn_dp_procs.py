@@ -8,15 +8,12 @@ case.  Required: the ranks end bit-identical (parameters, target, statistics,
 TD errors, draws and the saved priority trees), and rank 0 lies on the single
 learner's envelope (tests/dqn_ref.py envelope_check) for the 96 drawn rows."""
 import copy
-import os
-import tempfile
 
 import numpy as np
 import pytest
 import torch
-import torch.multiprocessing as mp
 
-from tests.test_gpu_dp_procs import _free_port
+from tests.dp_harness import spawn_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -35,12 +32,7 @@ def _case():
     return lc, D, A, init, rows
 
 
-def _worker(rank, world, port, outdir):
-    os.environ['MASTER_ADDR'] = '127.0.0.1'
-    os.environ['MASTER_PORT'] = str(port)
-    import torch.distributed as dist
-    torch.cuda.set_device(0)
-    dist.init_process_group('gloo', rank=rank, world_size=world)
+def _worker(rank, world):
     from surreal_amd.config import discrete_env_config
     from surreal_amd.dqn import DQNLearner
     from surreal_amd.learner import TorchDistAllReduce
@@ -73,8 +65,7 @@ def _worker(rank, world, port, outdir):
                     'stats': learner.last_stats(), 'stats_buf': learner.stats_buf.cpu().clone(),
                     'td': learner.td_error.cpu().clone(), 'tree': rep.tree.cpu().clone(),
                     'tracker': learner.target_update_tracker.value})
-    torch.save({'replicated': replicated, 'res': res}, os.path.join(outdir, f'rank{rank}.pt'))
-    dist.destroy_process_group()
+    return {'replicated': replicated, 'res': res}
 
 
 @pytest.mark.timeout(600)
@@ -82,9 +73,7 @@ def test_two_process_dqn_dp_matches_single_learner():
     from tests import dqn_ref as R
     from tests import parity as P
     world = 2
-    with tempfile.TemporaryDirectory() as outdir:
-        mp.spawn(_worker, args=(world, _free_port(), outdir), nprocs=world, join=True)
-        out = [torch.load(os.path.join(outdir, f'rank{r}.pt'), weights_only=True) for r in range(world)]
+    out = spawn_ranks(_worker, world)
     lc, D, A, init, rows = _case()
     Bg = lc.replay.batch_size
     assert torch.equal(out[0]['replicated'], out[1]['replicated'])     # replicate_from_rank0

@@ -21,6 +21,8 @@ from surreal_amd.replay import PrioritizedReplay
 from tests import parity as P
 from tests import per_ref as PR
 from tests import test_gpu_ddpg as T
+from tests.per_ref import ref_from_device
+from tests.helpers import per_cfg as _per_cfg, replay_rows as _rows
 
 pytestmark = pytest.mark.gpu
 
@@ -57,13 +59,6 @@ def host_tree(cap, idx, leaves):
 
 def bits(a):
     return np.ascontiguousarray(a).view(np.int64)
-
-
-def ref_from_device(tree, cap):
-    """per_ref tree rebuilt from the device's own leaves (every ancestor
-    recomputed in Python) and max_priority"""
-    t = tree.cpu().numpy()
-    return PR.PerRef.from_leaves(cap, t[2 * cap::2], max_priority=float(t[0])), t
 
 
 # ------------------------------------------------------------------ trees
@@ -241,24 +236,6 @@ def test_mse_grad_weighted(n):
 
 
 # ------------------------------------------------ replay + learner, end to end
-def _per_cfg(B=64, memory_size=200, double=False, action_reg=False):
-    lc = T._cfg(B, 'hard')
-    lc.replay.memory_size = memory_size
-    lc.replay.sampling_start_size = 10
-    lc.replay.alpha = 0.6
-    lc.algo.network.use_double_critic = double
-    lc.algo.network.use_action_regularization = action_reg
-    return lc
-
-
-def _rows(n, D, A, seed):
-    g = torch.Generator().manual_seed(seed)
-    rows = torch.randn(n, 2 * D + A + 2, generator=g)
-    rows[:, D:D + A] = torch.tanh(rows[:, D:D + A])
-    rows[:, 2 * D + A + 1] = (torch.rand(n, generator=g) < 0.1).float()
-    return rows
-
-
 def test_prioritized_replay_feeds_learner():
     B, D, A, seed = 64, 17, 6, 4321
     lc, ec = _per_cfg(B, 200), gym_env_config(D, A)
