@@ -220,7 +220,11 @@ int smi_reward_filter_commit(const double* sums3, float* running_sum, float* run
  *   loglik[r] = -0.5*sum(((a-mu)/sd)^2) - 0.5*log(2pi)*A - sum(log sd)
  *   lik[r]    = max(exp(loglik[r]), 1e-5)
  *   kl[r]     = KL(prob0[r] || prob1[r])
- *   ent[r]    = 0.5*sum(log sd) + 0.5*log(2 pi e)*A            (of prob0) */
+ *   ent[r]    = 0.5*sum(log sd) + 0.5*log(2 pi e)*A            (of prob0)
+ * act_dim <= 8 with 16-byte aligned operands runs one thread per row; every
+ * other call stages tiles of 256 rows through LDS, of 192 / 128 / 64 rows
+ * where 256 do not fit (act_dim >= 32); SMI_E_NOFIT (nothing launched) where
+ * 64 rows do not fit (act_dim >= 128). */
 int smi_diag_gauss(const float* actions, const float* prob0, const float* prob1,
                    int64_t rows, int act_dim,
                    float* loglik, float* lik, float* kl, float* entropy, void* stream);

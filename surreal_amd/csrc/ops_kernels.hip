@@ -36,7 +36,7 @@ zfilter_apply_kernel(const float* __restrict__ x, float* __restrict__ out, int64
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const float y = (r[j] - zm[c]) / zs[c];
-      r[j] = fminf(fmaxf(y, -5.f), 5.f);
+      r[j] = clamp5(y);
       c = (c + 1 == dim) ? 0 : c + 1;
     }
     o4[i] = float4{r[0], r[1], r[2], r[3]};
@@ -44,7 +44,7 @@ zfilter_apply_kernel(const float* __restrict__ x, float* __restrict__ out, int64
   for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * kWG + threadIdx.x; i < n; i += stride) {
     const int c = (int)(i % dim);
     const float y = (x[i] - zm[c]) / zs[c];
-    out[i] = fminf(fmaxf(y, -5.f), 5.f);
+    out[i] = clamp5(y);
   }
 }
 
@@ -176,10 +176,10 @@ reward_filter_kernel(float* __restrict__ r, int64_t n, float scale, int mode,
   for (int64_t i = threadIdx.x; i < n; i += kWG) {
     const float x = r[i] * scale;
     a1 += (double)x;
-    a2 += (double)(x * x);
+    a2 += (double)x * (double)x;
     if (mode & 1) {
       const float y = (x - mean) / sd;
-      r[i] = fminf(fmaxf(y, -5.f), 5.f);
+      r[i] = clamp5(y);
     } else {
       r[i] = x;
     }
@@ -210,11 +210,24 @@ __global__ void reward_filter_commit_kernel(const double* __restrict__ s3, float
 }
 
 // ------------------------------------------------------------ DiagGauss ops
-// HBM-bound: a tile of DG_R rows of actions (A floats), prob0 and prob1 (2A
+// HBM-bound: a tile of R rows of actions (A floats), prob0 and prob1 (2A
 // floats each) is staged through LDS with 16-byte coalesced loads (the tile is
 // contiguous in each array), then one thread per row forms the sums from LDS
 // with odd row strides (bank-conflict free); outputs are written coalesced.
+// R (a launch argument, <= DG_R: one thread per row) is DG_R while the tile fits
+// the LDS of a CU and shrinks in steps of 64 rows for wider actions; a row's
+// sums do not depend on the tile it is staged in.
 constexpr int DG_R = kWG;
+constexpr size_t kDgLdsCap = 160 * 1024;
+
+// floats of LDS per staged row: actions | prob0 | prob1, odd strides
+static size_t diag_gauss_row_floats(int A) { return (size_t)(A | 1) + 2 * (size_t)((2 * A) | 1); }
+// rows per tile: the largest multiple of 64 up to DG_R that fits; 0 = none does
+static int diag_gauss_tile_rows(int A) {
+  int R = DG_R;
+  while (R > 0 && (size_t)R * diag_gauss_row_floats(A) * 4 > kDgLdsCap) R -= 64;
+  return R;
+}
 
 __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_t r0, int nrows,
                                            int w, float* __restrict__ dst, int ldd) {
@@ -239,19 +252,19 @@ __device__ __forceinline__ void stage_rows(const float* __restrict__ src, int64_
 
 __global__ void __launch_bounds__(kWG)
 diag_gauss_kernel(const float* __restrict__ a, const float* __restrict__ p0,
-                  const float* __restrict__ p1, int64_t rows, int A, float c_ll, float c_ent,
-                  float* loglik, float* lik, float* kl, float* ent) {
+                  const float* __restrict__ p1, int64_t rows, int A, int R, float c_ll,
+                  float c_ent, float* loglik, float* lik, float* kl, float* ent) {
   extern __shared__ __attribute__((aligned(16))) float sm[];
   const int lda = A | 1, ldp = (2 * A) | 1;
   const bool need_a = loglik || lik;
   const bool need_p1 = kl && p1;
   float* sa = sm;
-  float* s0 = sa + DG_R * lda;
-  float* s1 = s0 + DG_R * ldp;
-  const int64_t ntiles = (rows + DG_R - 1) / DG_R;
+  float* s0 = sa + R * lda;
+  float* s1 = s0 + R * ldp;
+  const int64_t ntiles = (rows + R - 1) / R;
   for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-    const int64_t r0 = tile * DG_R;
-    const int nr = (int)min((int64_t)DG_R, rows - r0);
+    const int64_t r0 = tile * R;
+    const int nr = (int)min((int64_t)R, rows - r0);
     __syncthreads();
     if (need_a) stage_rows(a, r0, nr, A, sa, lda);
     stage_rows(p0, r0, nr, 2 * A, s0, ldp);
@@ -691,11 +704,13 @@ int launch_diag_gauss(const float* a, const float* p0, const float* p1, int64_t 
 #undef SMI_DG_CASE
     return check_launch("diag_gauss_rows_kernel");
   }
-  const size_t lds = (size_t)DG_R * ((A | 1) + 2 * ((2 * A) | 1)) * 4;
-  if (lds > 160 * 1024) return set_error(SMI_E_NOFIT, "diag_gauss: act_dim too large");
+  const int R = diag_gauss_tile_rows(A);
+  if (R == 0) return set_error(SMI_E_NOFIT, "diag_gauss: act_dim too large");
+  const size_t lds = (size_t)R * diag_gauss_row_floats(A) * 4;
+  const int64_t ntiles = (rows + R - 1) / R;
   allow_lds(diag_gauss_kernel, lds);
-  hipLaunchKernelGGL(diag_gauss_kernel, dim3(grid_for(rows, 4096)), dim3(kWG), lds, st, a, p0, p1,
-                     rows, A, c_ll, c_ent, ll, lik, kl, ent);
+  hipLaunchKernelGGL(diag_gauss_kernel, dim3((int)(ntiles < 4096 ? ntiles : 4096)), dim3(kWG), lds,
+                     st, a, p0, p1, rows, A, R, c_ll, c_ent, ll, lik, kl, ent);
   return check_launch("diag_gauss_kernel");
 }
 

@@ -70,7 +70,7 @@ critic_gae_kernel(CriticGaeArgs a) {
           v = (t < a.T) ? a.obs[(b * a.T + t) * a.D + c] : a.obs_next[b * a.D + c];
           if (a.use_zf) {
             v = (v - zmean[c]) / zstd[c];
-            v = fminf(fmaxf(v, -5.f), 5.f);
+            v = clamp5(v);
           }
         }
         X0[e] = v;

@@ -63,8 +63,8 @@ zf_tmajor_kernel(const float* __restrict__ obs, const float* __restrict__ obs_ne
         if (!lv || row >= nrows) continue;
         float2 o = v[j];
         if (use_zf) {
-          o.x = fminf(fmaxf((o.x - zm2.x) / zd2.x, -5.f), 5.f);
-          o.y = fminf(fmaxf((o.y - zm2.y) / zd2.y, -5.f), 5.f);
+          o.x = clamp5((o.x - zm2.x) / zd2.x);
+          o.y = clamp5((o.y - zm2.y) / zd2.y);
         }
         *reinterpret_cast<float2*>(out + (int64_t)row * ldo + cc) = o;
       }
@@ -91,12 +91,12 @@ zf_tmajor_kernel(const float* __restrict__ obs, const float* __restrict__ obs_ne
       float* dst = out + (int64_t)row * ldo;
       if (lane < D) {
         float v = v0[j];
-        if (use_zf) v = fminf(fmaxf((v - m0) / d0, -5.f), 5.f);
+        if (use_zf) v = clamp5((v - m0) / d0);
         dst[lane] = v;
       }
       if (lane + 64 < D) {
         float v = v1[j];
-        if (use_zf) v = fminf(fmaxf((v - m1) / d1, -5.f), 5.f);
+        if (use_zf) v = clamp5((v - m1) / d1);
         dst[lane + 64] = v;
       }
     }
@@ -166,8 +166,8 @@ zf_tile_kernel(const float* __restrict__ obs, const float* __restrict__ obs_next
   for (int t = 0; t < S; ++t) {
     float2 v = tp[t * D2];
     if (use_zf) {
-      v.x = fminf(fmaxf((v.x - m.x) / dd.x, -5.f), 5.f);
-      v.y = fminf(fmaxf((v.y - m.y) / dd.y, -5.f), 5.f);
+      v.x = clamp5((v.x - m.x) / dd.x);
+      v.y = clamp5((v.y - m.y) / dd.y);
     }
     *reinterpret_cast<float2*>(op + (int64_t)t * B * ldo) = v;
   }
@@ -247,7 +247,7 @@ zf_tile4_kernel(const float* __restrict__ obs, const float* __restrict__ obs_nex
       }
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        if (use_zf && c + j < D) v[j] = fminf(fmaxf((v[j] - zmv[j]) / zdv[j], -5.f), 5.f);
+        if (use_zf && c + j < D) v[j] = clamp5((v[j] - zmv[j]) / zdv[j]);
       *reinterpret_cast<float4*>(out + ((int64_t)t * B + b0 + bl) * ldo + c) =
           float4{v[0], v[1], v[2], v[3]};
     }
@@ -266,8 +266,8 @@ zf_tile4_kernel(const float* __restrict__ obs, const float* __restrict__ obs_nex
     for (int t = 0; t < S; ++t) {
       float2 v = t < T ? tp[t * D2] : reinterpret_cast<const float2*>(nxt + bl * D)[c2];
       if (use_zf) {
-        v.x = fminf(fmaxf((v.x - m.x) / dd.x, -5.f), 5.f);
-        v.y = fminf(fmaxf((v.y - m.y) / dd.y, -5.f), 5.f);
+        v.x = clamp5((v.x - m.x) / dd.x);
+        v.y = clamp5((v.y - m.y) / dd.y);
       }
       *reinterpret_cast<float2*>(op + (int64_t)t * B * ldo) = v;
     }
@@ -285,7 +285,7 @@ zf_tile4_kernel(const float* __restrict__ obs, const float* __restrict__ obs_nex
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       v[j] = j < w ? sp[j] : 0.f;
-      if (use_zf && j < w) v[j] = fminf(fmaxf((v[j] - zm[c + j]) / zd[c + j], -5.f), 5.f);
+      if (use_zf && j < w) v[j] = clamp5((v[j] - zm[c + j]) / zd[c + j]);
     }
     float* op = out + ((int64_t)t * B + b0 + bl) * ldo + c;
     if (w == 4) {
@@ -398,7 +398,7 @@ zf_pipe_kernel(const float* __restrict__ obs, const float* __restrict__ obs_next
         }
 #pragma unroll
         for (int j = 0; j < 4; ++j)
-          if (use_zf && c + j < D) v[j] = fminf(fmaxf((v[j] - zmv[j]) / zdv[j], -5.f), 5.f);
+          if (use_zf && c + j < D) v[j] = clamp5((v[j] - zmv[j]) / zdv[j]);
         *reinterpret_cast<float4*>(out + ((int64_t)t * B + b0 + bl) * ldo + c) =
             float4{v[0], v[1], v[2], v[3]};
       }

@@ -37,13 +37,23 @@ __host__ __device__ inline int pad_small(int k) { return round4(k) + 1; }
 
 template <int ACT>
 __device__ __forceinline__ float act_f(float x) {
-  if constexpr (ACT == ACT_RELU) return x > 0.f ? x : 0.f;
+  // torch.relu: a NaN stays NaN (x > 0 ? x : 0 would zero it); the bits of
+  // every other input are those of x > 0 ? x : 0 (-0.0 -> +0.0)
+  if constexpr (ACT == ACT_RELU) return x <= 0.f ? 0.f : x;
   else if constexpr (ACT == ACT_TANH) return tanhf(x);
   else return x;
 }
 
 __device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
+}
+
+// torch.clamp(y, -5, 5) of the filters (z_filter.py:79, reward_filter.py:56):
+// NaN propagates.  fminf / fmaxf alone have maxNum semantics (a NaN y would
+// come out as -5); every other input, -0.0 and +-inf included, keeps the bits
+// of fminf(fmaxf(y, -5), 5).
+__device__ __forceinline__ float clamp5(float y) {
+  return y != y ? y : fminf(fmaxf(y, -5.f), 5.f);
 }
 
 // ---------------------------------------------------------------- reductions
@@ -297,7 +307,7 @@ __device__ inline void load_obs_tile(const float* __restrict__ src, int64_t row_
       v = src[(int64_t)r * row_stride + c];
       if (zmean) {
         v = (v - zmean[c]) / zstd[c];
-        v = fminf(fmaxf(v, -5.f), 5.f);
+        v = clamp5(v);
       }
     }
     X[e] = v;
