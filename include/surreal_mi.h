@@ -968,6 +968,67 @@ int smi_dqn_td_shard(const float* adv, int64_t lda, const float* adv_next, int64
 int smi_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t val_stride,
                    int64_t rows, int A, int dueling, int32_t* out, void* stream);
 
+/* ------------------------------------------- categorical (C51) DQN pieces */
+/* The distributional head (Bellemare et al. 2017) of DQNLearner: smi_dqn_td
+ * for a distribution over N atoms per action (2 <= N <= 64), support
+ * z_i = v_min + i D, D = (v_max - v_min) / (N - 1).  adv / adv_next / adv_target
+ * [B][ld >= A N]: the action streams' logits, action major (column a N + i is
+ * atom i of action a); val / val_next / val_target [B][ld >= N]: the state
+ * streams' (read only with dueling).  The other inputs are smi_dqn_td's.  Per
+ * row, fp32 (the full operation order: dqn_dist_kernels.hip):
+ *   l[a,i] = (adv[a,i] - mean_a' adv[a',i]) + val[i] (dueling) | adv[a,i]
+ *   p[a,.] = softmax_i l[a,.];  Q[a] = sum_i z_i p[a,i]
+ *   a* = first arg-max of Q(s') of the online net (double_q) | the target net
+ *   Tz_j = clamp(r + gamma (1 - d) z_j, v_min, v_max);  b_j = (Tz_j - v_min) / D
+ *   m_i = sum_j p_target(s')[a*,j] max(0, 1 - |b_j - i|)     (j ascending: the
+ *         floor / ceil projection in gather form, no atomics, same bits anywhere)
+ *   loss = -sum_i m_i log_softmax(l[a_taken,.])_i;  g_i = (w (p[a_taken,i] - m_i)) / B
+ * Outputs: dadv [B][ldd >= A N] = g_i ([a' == a_taken] - 1/A) (dueling) | g_i at
+ * a_taken and 0 elsewhere, every entry of the A N columns written; dval
+ * [B][ldv >= N] = g_i (dueling only); td_out [B] = the row's loss (>= 0: the
+ * priority signal of a prioritized replay); m_out [B][N] and astar_out [B]
+ * (int32) may be NULL; stats[2] = { mean(w loss), mean(loss) }.  partials: a
+ * caller-owned device workspace of at least smi_dqn_c51_partials_bytes(B)
+ * bytes (8-byte aligned) for the workgroups' fp64 sums; a second launch of one
+ * wave adds them in a fixed order into stats.  SMI_E_ARG (nothing launched):
+ * NULL required pointer, B < 1, A < 1, N outside [2, 64], A N > 3072 (the LDS
+ * slabs of a workgroup), v_max <= v_min, a leading dimension too small,
+ * dueling without its pointers, too few partials bytes. */
+int smi_dqn_c51_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                   const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                   const float* val_next, int64_t ldval_next, const float* val_target,
+                   int64_t ldval_target, const float* actions, int64_t action_stride,
+                   const float* rewards, int64_t reward_stride, const float* dones,
+                   int64_t done_stride, const float* w, int64_t B, int A, int N, float v_min,
+                   float v_max, float gamma, int dueling, int double_q, float* dadv, int64_t ldd,
+                   float* dval, int64_t ldv, float* td_out, float* m_out, int32_t* astar_out,
+                   void* partials, int64_t partials_bytes, float* stats, void* stream);
+/* One rank's shard of smi_dqn_c51_td (the same kernel; smi_dqn_c51_td is
+ * B_global = B, row0 = 0), with exactly the three differences of
+ * smi_dqn_td_shard: g divides by (float)B_global; td_all [B_global] receives
+ * the shard's losses at row0 + i and +0.0f everywhere else; stats are the
+ * shard's sums / B_global.  dadv, dval, m_out, astar_out, w and partials
+ * (smi_dqn_c51_partials_bytes(B)) are the shard's own.  SMI_E_ARG: everything
+ * smi_dqn_c51_td rejects, B_global < B, row0 < 0, row0 + B > B_global. */
+int smi_dqn_c51_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                         const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                         const float* val_next, int64_t ldval_next, const float* val_target,
+                         int64_t ldval_target, const float* actions, int64_t action_stride,
+                         const float* rewards, int64_t reward_stride, const float* dones,
+                         int64_t done_stride, const float* w, int64_t B, int64_t B_global,
+                         int64_t row0, int A, int N, float v_min, float v_max, float gamma,
+                         int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                         int64_t ldv, float* td_all, float* m_out, int32_t* astar_out,
+                         void* partials, int64_t partials_bytes, float* stats, void* stream);
+/* q_out [rows][ldq >= A] = the expected values Q[a] of smi_dqn_c51_td over one
+ * pair of logit matrices; greedy_out [rows] (int32, may be NULL) = the first
+ * index of each row's maximum (FFQfunc.forward, QAgentBatch.act). */
+int smi_dqn_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
+                  int N, float v_min, float v_max, int dueling, float* q_out, int64_t ldq,
+                  int32_t* greedy_out, void* stream);
+/* bytes of smi_dqn_c51_td's partials workspace for B rows (host only) */
+int64_t smi_dqn_c51_partials_bytes(int64_t B);
+
 /* ------------------------------------------------------ DDPG n-step target */
 /* Replaces the target of DDPGLearner._optimize (surreal/learner/ddpg.py:279-283):
  *   y = r + gamma_n * q_next * (1 - done); with twin critics y = min(y, y2). */

@@ -341,7 +341,9 @@ class QAgentBatch(object):
     picks the greedy action, else `random.randrange(A)` is the action.  One
     forward over the N rows and one smi_dqn_greedy (first index of the
     maximum, as torch's max(1)[1] on the CPU) then serve the greedy agents,
-    and one D2H copy returns the N actions."""
+    and one D2H copy returns the N actions.  With algo.distributional.enabled
+    the model has categorical heads and smi_dqn_c51_q's greedy output (the
+    first maximum of the expected values) takes smi_dqn_greedy's place."""
 
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
         from .config import ConfigError
@@ -411,8 +413,12 @@ class QAgentBatch(object):
                 actions[i] = random.randrange(A)
         if greedy.any():
             xd = torch.from_numpy(x).to(self.device)
-            adv, val = _QNet(self.q_func, self._bufs).fwd(xd, self.n, 'act')
-            L.call('smi_dqn_greedy', L.ptr(adv), A, L.ptr(val), 1, self.n, A,
-                   int(self.q_func.dueling), L.ptr(self._greedy), L.stream(self.device))
+            net = _QNet(self.q_func, self._bufs)
+            adv, val = net.fwd(xd, self.n, 'act')
+            if self.q_func.atoms:      # categorical heads: arg-max of the expected values
+                net.expected_q(adv, val, self.n, 'act', greedy=self._greedy)
+            else:
+                L.call('smi_dqn_greedy', L.ptr(adv), A, L.ptr(val), 1, self.n, A,
+                       int(self.q_func.dueling), L.ptr(self._greedy), L.stream(self.device))
             actions[greedy] = self._greedy.cpu().numpy()[greedy]        # one D2H
         return actions

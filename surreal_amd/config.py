@@ -201,6 +201,8 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
             'beta_anneal_iters': None,
             'eps': 1e-6,
         },
+        # categorical heads (C51): atoms on the support [v_min, v_max]
+        'distributional': {'enabled': False, 'atoms': 51, 'v_min': -10.0, 'v_max': 10.0},
     },
     'eval': {'eps': 0.05},
     'replay': {'batch_size': 512, 'memory_size': int(1000000 / 3),

@@ -53,6 +53,7 @@
 // sum; the launch is latency bound.
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
+#include "dqn_rows.hpp"
 
 namespace smi {
 
@@ -97,11 +98,6 @@ __device__ __forceinline__ int dqn_argmax(const float* __restrict__ a, int A, fl
     if (q > qb) { qb = q; best = j; }
   }
   return best;
-}
-
-__device__ __forceinline__ int dqn_action_index(float af, int A) {
-  if (!(af >= 0.f)) return 0;                     // negative or NaN
-  return af < (float)A ? (int)af : A - 1;
 }
 
 template <bool DUELING, bool DOUBLE_Q>

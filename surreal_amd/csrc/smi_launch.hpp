@@ -77,6 +77,21 @@ int launch_dqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
                   hipStream_t st);
 int launch_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t vs, int64_t rows,
                       int A, int dueling, int32_t* out, hipStream_t st);
+// ---- dqn_dist_kernels.hip (categorical heads; shape and leading-dimension
+// checks are the launchers' own: SMI_E_ARG with a message, nothing launched)
+int launch_c51_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn,
+                  const float* adv_t, int64_t ldt, const float* val, int64_t ldv,
+                  const float* val_n, int64_t ldvn, const float* val_t, int64_t ldvt,
+                  const float* actions, int64_t as, const float* rewards, int64_t rs,
+                  const float* dones, int64_t ds, const float* w, int64_t B, int64_t B_global,
+                  int64_t row0, int A, int N, float v_min, float v_max, float gamma, int dueling,
+                  int double_q, float* dadv, int64_t ldd, float* dval, int64_t lddv, float* td_all,
+                  float* m_out, int32_t* astar_out, double* partials, int64_t partials_bytes,
+                  float* stats, hipStream_t st);
+int launch_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
+                 int N, float v_min, float v_max, int dueling, float* q, int64_t ldq,
+                 int32_t* greedy, hipStream_t st);
+int64_t c51_partials_bytes(int64_t B);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
 // skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
 // rows: the uint8 images come through the learners' time-major row map

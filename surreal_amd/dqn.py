@@ -72,6 +72,19 @@ the TD errors exactly; its statistics sum to the global means.  The three sit
 in ONE exchange image [gradient | td_all | stats] and one all-reduce per
 learn(), between the backward and smi_adam_clip, so the norm clip acts on the
 global-batch gradient.  Every rank then runs the same Adam on the same bits.
+
+Categorical heads (algo.distributional.enabled; C51, Bellemare et al. 2017;
+this build's own specification, dqn_dist_kernels.hip): the last layer of the
+action stream has A N outputs, action major (column a N + i is atom i of
+action a), the last layer of the state stream N; state_dict names are
+unchanged, only these two shapes grow.  forward() returns the expected values
+sum_i z_i softmax(l[a, .])_i over the support z_i = v_min + i (v_max - v_min) /
+(N - 1) (smi_dqn_c51_q), logits() the raw streams.  learn() runs the same three
+forwards, then smi_dqn_c51_td (smi_dqn_c51_td_shard under dp, inside the same
+exchange image) in place of smi_dqn_td and the same backward: the loss is the
+cross-entropy of the projected target distribution against the online net's
+log-softmax at the action taken, and `td_error` holds each row's loss (>= 0):
+the priority signal update_priorities_from_td reads.
 """
 import numpy as np
 import torch
@@ -199,15 +212,41 @@ def dqn_conv_specs(learner_config, env_config):
             bool(lc['model'].get('is_uint8', True)))
 
 
+C51_MAX_ATOMS = 64        # one lane per atom (dqn_dist_kernels.hip: kC51MaxAtoms)
+C51_MAX_SLAB = 3072       # A * atoms: the LDS slabs of a workgroup (kC51LdsBytes)
+
+
+def check_atoms(A, atoms, v_min, v_max):
+    """the ranges smi_dqn_c51_* serve, as (atoms, v_min, v_max)"""
+    atoms, v_min, v_max = int(atoms), float(v_min), float(v_max)
+    if not 2 <= atoms <= C51_MAX_ATOMS:
+        raise ConfigError('DQN algo.distributional.atoms must be in [2, {}], got {}'.format(
+            C51_MAX_ATOMS, atoms))
+    if not v_max > v_min:
+        raise ConfigError('DQN algo.distributional needs v_max > v_min, got [{}, {}]'.format(
+            v_min, v_max))
+    if A * atoms > C51_MAX_SLAB:
+        raise ConfigError('DQN algo.distributional: {} actions x {} atoms is over the kernel\'s '
+                          '{} logits per row'.format(A, atoms, C51_MAX_SLAB))
+    return atoms, v_min, v_max
+
+
 def dqn_model_kwargs(learner_config, env_config):
     """(D, A, hidden, dueling, FFQfunc keyword arguments): dqn_conv_specs for a
-    spec with pixels, dqn_specs otherwise.  Host only."""
+    spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
+    atoms, v_min and v_max.  Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
-        return D, A, hidden, dueling, {'convs': convs, 'input_shape': shape, 'is_uint8': u8}
-    D, A, hidden, dueling = dqn_specs(learner_config, env_config)
-    return D, A, hidden, dueling, {}
+        kw = {'convs': convs, 'input_shape': shape, 'is_uint8': u8}
+    else:
+        D, A, hidden, dueling = dqn_specs(learner_config, env_config)
+        kw = {}
+    dist = learner_config['algo'].get('distributional') or {}
+    if dist.get('enabled', False):
+        kw['atoms'], kw['v_min'], kw['v_max'] = check_atoms(
+            A, dist.get('atoms', 51), dist.get('v_min', -10.0), dist.get('v_max', 10.0))
+    return D, A, hidden, dueling, kw
 
 
 def ffq_param_names(n_convs, n_hidden, dueling):
@@ -233,11 +272,17 @@ class _ConvAt(_LinearView):
 class FFQfunc(nn.Module):
     """q_net.py:9-119 over ONE flat fp32 buffer (layout: module docstring).
     With convs ([[cout, k, stride]], input_shape (C, H, W)) the input is a
-    uint8 or float32 (rows, C, H, W) device tensor and D_in is ignored."""
+    uint8 or float32 (rows, C, H, W) device tensor and D_in is ignored.  With
+    atoms (categorical heads over the support [v_min, v_max]) the action
+    stream ends in A * atoms logits and the state stream in atoms."""
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
-                 convs=None, input_shape=None, is_uint8=False):
+                 convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None):
         super().__init__()
+        self.atoms, self.v_min, self.v_max = None, None, None
+        if atoms is not None:
+            self.atoms, self.v_min, self.v_max = check_atoms(int(action_dim), atoms, v_min, v_max)
+        N = self.atoms or 1
         hs = [int(h) for h in fc_hidden_sizes]
         if not 1 <= len(hs) <= 3:
             raise ConfigError('FFQfunc takes 1 to 3 hidden widths')
@@ -261,7 +306,7 @@ class FFQfunc(nn.Module):
         deep = lambda out: sum(hs[k] * hs[k - 1] + hs[k] for k in range(1, len(hs))) + \
             out * hs[-1] + out                                              # noqa: E731
         fc0 = sum(co * ci * k * k + co for ci, _, _, co, k, _, _ in self.conv_geoms)
-        n = fc0 + S * h1 * D + S * h1 + deep(A) + (deep(1) if dueling else 0)
+        n = fc0 + S * h1 * D + S * h1 + deep(A * N) + (deep(N) if dueling else 0)
         flat = torch.zeros(n, dtype=torch.float32, device=self.device)
         self.__dict__['flat'] = flat
         if self.convs:
@@ -278,7 +323,7 @@ class FFQfunc(nn.Module):
         self.__dict__['b1'] = flat[b1:b1 + S * h1]
         off = b1 + S * h1
         streams = []
-        for s, out in enumerate((A, 1)[:S]):
+        for s, out in enumerate((A * N, N)[:S]):
             layers = [_LinearAt(flat, fc0 + s * h1 * D, b1 + s * h1, D, h1)]
             for k in range(1, len(hs)):
                 layers.append(_LinearView(flat, off, hs[k - 1], hs[k]))
@@ -310,15 +355,24 @@ class FFQfunc(nn.Module):
     def clone(self):
         D, hs, A = self.dims
         c = FFQfunc(D, A, hs, self.dueling, self.device, convs=self.convs,
-                    input_shape=self.input_shape, is_uint8=self.is_uint8)
+                    input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
+                    v_min=self.v_min, v_max=self.v_max)
         c.copy_from(self)
         return c
 
+    def logits(self, x):
+        """the raw streams (adv [rows][A * atoms] action major, val [rows][atoms]
+        | None); for scalar heads (adv [rows][A], val [rows][1] | None)"""
+        x = x.contiguous() if self.convs else (x if x.stride(-1) == 1 else x.contiguous())
+        return _QNet(self, {}).fwd(x, x.shape[0], 'f')
+
     def forward(self, x):
         """q values [rows][A] (q_net.py:41-65,112-119) of a float32 device matrix
-        (with convs: of a uint8 or float32 (rows, C, H, W) device tensor)"""
-        x = x.contiguous() if self.convs else (x if x.stride(-1) == 1 else x.contiguous())
-        adv, val = _QNet(self, {}).fwd(x, x.shape[0], 'f')
+        (with convs: of a uint8 or float32 (rows, C, H, W) device tensor); with
+        atoms the expected values of the categorical heads (smi_dqn_c51_q)"""
+        adv, val = self.logits(x)
+        if self.atoms:
+            return _QNet(self, {}).expected_q(adv, val, adv.shape[0], 'f')
         if not self.dueling:
             return adv.clone()
         return (adv - adv.mean(dim=1, keepdim=True)) + val
@@ -376,8 +430,19 @@ class _QNet(LaunchNet):
                        pad, p(xi), p(dx), self.st)
                 dy = dx
 
+    def expected_q(self, adv, val, rows, pre, greedy=None):
+        """Q [rows][A] of a categorical model's logits (fwd's outputs); greedy
+        (int32 [rows], optional) receives each row's first arg-max"""
+        m = self.m
+        A = m.dims[2]
+        q = self.buf(pre + '_q', (rows, A))
+        L.call('smi_dqn_c51_q', p(adv), adv.stride(0), p(val), m.atoms, rows, A, m.atoms, m.v_min,
+               m.v_max, int(m.dueling), p(q), A, p(greedy), self.st)
+        return q
+
     def fwd(self, x, rows, pre):
-        """(ADV [rows][A], VAL [rows][1] | None); the hidden activations stay in
+        """(ADV [rows][A], VAL [rows][1] | None), with atoms (ADV [rows][A * atoms],
+        VAL [rows][atoms] | None); the hidden activations stay in
         the buffers pre_h1 ([rows][S h1], both streams) and pre_h{k}_{s}"""
         m = self.m
         D, hs, A = m.dims
@@ -469,7 +534,8 @@ class DQNLearner(DeviceLearner):
     """dqn.py:9-126 on MI355X (low-dimensional observations, or uint8 frames
     with model.convs; discrete actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
     replay.PrioritizedReplay.sample_batch) weights the Huber loss; after every
-    learn() `td_error` is a device view [B] of Q(s, a) - y
+    learn() `td_error` is a device view [B] of Q(s, a) - y, with categorical
+    heads of each row's cross-entropy (>= 0)
     (PrioritizedReplay.update_priorities_from_td).  With dp, `td_error` is
     [B_global]: the TD errors of the WHOLE draw, in draw order, on every rank
     (replay.sample_shard's idx_all names their slots)."""
@@ -495,7 +561,8 @@ class DQNLearner(DeviceLearner):
         self.max_norm = float(clip) if clip else 0.0          # None or 0: no clip (dqn.py:33-35)
         gen = torch.Generator().manual_seed(seed)
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
-        self.pixel = bool(conv_kw)
+        self.pixel = 'convs' in conv_kw
+        self.atoms = self.q_func.atoms
         self.q_target = self.q_func.clone()                   # dqn.py:17
         self.dp = self._dp_group(dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
@@ -574,9 +641,19 @@ class DQNLearner(DeviceLearner):
         adv_n = val_n = None
         if self.double_q:
             adv_n, val_n = net.fwd(obs_next, B, 'n')
-        dadv = net.buf('dadv', (B, A))
-        dval = net.buf('dval', (B, 1)) if dueling else None
-        if self.dp is None:
+        N = self.atoms or 1
+        dadv = net.buf('dadv', (B, A * N))
+        dval = net.buf('dval', (B, N)) if dueling else None
+        if self.dp is not None and (self._xbuf is None
+                                    or self.td_error.numel() != B * self.dp.world_size):
+            # what the one all-reduce per learn() carries: [gradient | pad |
+            # td_all (B_global) | stats (2)], the three as views of it
+            self._xbuf, self.opt['g'], (self.td_error, self.stats_buf) = exchange_image(
+                self.device, self.q_func.flat.numel(), (B * self.dp.world_size, 2))
+        if self.atoms:
+            self._gradient_c51(net, B, (adv, adv_n, adv_t), (val, val_n, val_t), (act, a_s),
+                               (rew, r_s), (don, d_s), weights, dadv, dval)
+        elif self.dp is None:
             self.td_error = net.buf('td', (B,))
             L.call('smi_dqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
                    p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, A,
@@ -584,17 +661,31 @@ class DQNLearner(DeviceLearner):
                    p(self.td_error), None, p(self.stats_buf), st)
         else:
             world = self.dp.world_size
-            if self._xbuf is None or self.td_error.numel() != B * world:
-                # what the one all-reduce per learn() carries: [gradient | pad |
-                # td_all (B_global) | stats (2)], the three as views of it
-                self._xbuf, self.opt['g'], (self.td_error, self.stats_buf) = exchange_image(
-                    self.device, self.q_func.flat.numel(), (B * world, 2))
             L.call('smi_dqn_td_shard', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
                    p(val_t), 1, p(act), a_s, p(rew), r_s, p(don), d_s, p(weights), B, B * world,
                    self.dp.rank * B, A, float(self.algo.gamma), int(dueling), int(self.double_q),
                    p(dadv), A, p(dval), p(self.td_error), None, p(self.stats_buf), st)
         with L.dw_group(st):
             net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'])
+
+    def _gradient_c51(self, net, B, advs, vals, act, rew, don, weights, dadv, dval):
+        """_gradient's TD step for categorical heads: smi_dqn_c51_td and its
+        statistics launch, or the shard form into the exchange image's views"""
+        A, N, q = self.action_dim, self.atoms, self.q_func
+        (adv, adv_n, adv_t), (val, val_n, val_t) = advs, vals
+        need = int(L.lib().smi_dqn_c51_partials_bytes(B))
+        part = net.buf('c51_partials', (need // 8,), torch.float64)
+        args = [p(adv), A * N, p(adv_n), A * N, p(adv_t), A * N, p(val), N, p(val_n), N, p(val_t), N,
+                p(act[0]), act[1], p(rew[0]), rew[1], p(don[0]), don[1], p(weights), B]
+        tail = [A, N, q.v_min, q.v_max, float(self.algo.gamma), int(q.dueling), int(self.double_q),
+                p(dadv), A * N, p(dval), N]
+        if self.dp is None:
+            self.td_error = net.buf('td', (B,))
+            L.call('smi_dqn_c51_td', *args, *tail, p(self.td_error), None, None, p(part), need,
+                   p(self.stats_buf), net.st)
+        else:
+            L.call('smi_dqn_c51_td_shard', *args, B * self.dp.world_size, self.dp.rank * B, *tail,
+                   p(self.td_error), None, None, p(part), need, p(self.stats_buf), net.st)
 
     # ------------------------------------------------------- reference API
     def _update_phases(self, batch):
@@ -631,7 +722,9 @@ class DQNLearner(DeviceLearner):
             self._update_target()
 
     def _stats_dict(self, v, host):
-        """'td_error' is the reference's scalar mean |td| (dqn.py:89-92)"""
+        """'td_error' is the reference's scalar mean |td| (dqn.py:89-92); with
+        categorical heads it is the mean cross-entropy of the rows (the
+        unweighted mean of what `td_error` holds per row)"""
         return {'loss': float(v[0]), 'td_error': float(v[1])}
 
     def module_dict(self):                                               # dqn.py:123-126

@@ -22,7 +22,15 @@ being sample_shard -> learn -> update_priorities_from_td at a global batch of
 512 (512 / N rows per rank).  Rank 0 prints the one JSON line.  With fewer than
 N (or fewer than two) GPUs visible it says so and starts nothing.
 
-Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel | --gpus N]
+--atoms N (2 <= N <= 64) times the categorical (C51) head instead: learn()
+with algo.distributional.enabled next to the scalar learner's, eager and as a
+graph replay, and at B = 512 and A in {6, 18} (dueling, double-Q, weights) one
+smi_dqn_c51_td call (the TD kernel and its statistics launch) next to the same
+math in eager torch on the same GPU tensors (log_softmax, index_add_
+projection, autograd to the three head outputs): what a user would otherwise
+write.  Each timed sample is --calls back-to-back calls between two events.
+
+Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel | --gpus N | --atoms N]
 """
 import argparse
 import copy
@@ -216,6 +224,75 @@ def dp_main(args):
     mp.spawn(dp_worker, args=(n, port, args.iters, args.warmup), nprocs=n, join=True)
 
 
+def torch_c51(adv, val, adv_n, val_n, adv_t, val_t, act, rew, done, w, A, N, v_min, v_max, gamma):
+    """the categorical TD step in eager torch: dueling logits, double-Q arg-max
+    of the expected values, floor / ceil projection, weighted cross-entropy and
+    its gradients at (adv, val)"""
+    B = adv.shape[0]
+    lg = lambda a, v: (lambda l: (l - l.mean(1, keepdim=True)) + v[:, None, :])(a.view(B, A, N))  # noqa: E731
+    delta = (v_max - v_min) / (N - 1)
+    z = v_min + torch.arange(N, device=adv.device, dtype=adv.dtype) * delta
+    rows = torch.arange(B, device=adv.device)
+    with torch.no_grad():
+        astar = (torch.softmax(lg(adv_n, val_n), 2) * z).sum(2).argmax(1)
+        pt = torch.softmax(lg(adv_t, val_t), 2)[rows, astar]
+        b = ((rew + gamma * ((1 - done) * z)).clamp(v_min, v_max) - v_min) / delta
+        lo, up = b.floor(), b.ceil()
+        off = (rows * N)[:, None]
+        m = torch.zeros(B * N, device=adv.device)
+        m.index_add_(0, (lo.long() + off).view(-1), (pt * ((up - b) + (lo == up).float())).view(-1))
+        m.index_add_(0, (up.long() + off).view(-1), (pt * (b - lo)).view(-1))
+    logp = torch.log_softmax(lg(adv, val), 2)[rows, act]
+    loss = -(m.view(B, N) * logp).sum(1)
+    return torch.autograd.grad((w * loss).mean(), (adv, val)), loss.detach()
+
+
+def atoms_main(args):
+    N, B, D, v_min, v_max, gamma = args.atoms, 512, 17, -10.0, 10.0, 0.99
+    p, st = L.ptr, L.stream()
+    for A in (6, 18):
+        g = torch.Generator().manual_seed(A)
+        adv, adv_n, adv_t = (torch.randn(B, A * N, generator=g).cuda() for _ in range(3))
+        val, val_n, val_t = (torch.randn(B, N, generator=g).cuda() for _ in range(3))
+        b = dqn_batch(B, D, A, 0)
+        act, rew, done, w = b['actions'], b['rewards'], b['dones'], b['weights']
+        dadv, dval, td = torch.zeros(B, A * N).cuda(), torch.zeros(B, N).cuda(), torch.zeros(B).cuda()
+        stats = torch.zeros(2).cuda()
+        need = int(L.lib().smi_dqn_c51_partials_bytes(B))
+        part = torch.zeros(need // 8, dtype=torch.float64).cuda()
+
+        def hip():
+            for _ in range(args.calls):
+                L.call('smi_dqn_c51_td', p(adv), A * N, p(adv_n), A * N, p(adv_t), A * N, p(val), N,
+                       p(val_n), N, p(val_t), N, p(act), 1, p(rew), 1, p(done), 1, p(w), B, A, N, v_min,
+                       v_max, gamma, 1, 1, p(dadv), A * N, p(dval), N, p(td), None, None, p(part),
+                       need, p(stats), st)
+        ga, gv = adv.clone().requires_grad_(), val.clone().requires_grad_()
+
+        def eager():
+            for _ in range(args.calls):
+                torch_c51(ga, gv, adv_n, val_n, adv_t, val_t, act.view(B).long(), rew, done,
+                          w.view(B), A, N, v_min, v_max, gamma)
+        for name, fn in (('c51_td_and_stats', hip), ('torch_eager_c51_td', eager)):
+            med, q1, q3 = (1e3 * t / args.calls for t in timed(fn, args.iters, args.warmup))
+            print(json.dumps({'measurement': name, 'B': B, 'A': A, 'atoms': N,
+                              'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                              'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
+                              'iters': args.iters}), flush=True)
+    A = 6
+    b = dqn_batch(B, D, A, 0)
+    for atoms in (None, N):
+        lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+        lc.replay.batch_size = B
+        lc.algo.distributional.enabled, lc.algo.distributional.atoms = atoms is not None, N
+        for graph in (False, True):
+            learner = DQNLearner(lc, discrete_env_config(D, A), seed=0, use_graph=graph)
+            med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
+            print(json.dumps({'measurement': 'dqn_learn_' + ('graph' if graph else 'eager'),
+                              'atoms': atoms, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                              'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
@@ -223,9 +300,15 @@ def main():
     ap.add_argument('--pixel', action='store_true')
     ap.add_argument('--gpus', type=int, default=1,
                     help='N >= 2: the data-parallel loop, one process per GPU')
+    ap.add_argument('--atoms', type=int, default=0,
+                    help='N: the categorical (C51) head with N atoms instead of scalar heads')
+    ap.add_argument('--calls', type=int, default=20,
+                    help='--atoms: back-to-back kernel calls per timed sample')
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
+    if args.atoms:
+        return atoms_main(args)
     if args.pixel:
         return pixel_main(args)
     B, D, A = 512, 17, 6
