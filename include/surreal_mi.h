@@ -990,9 +990,12 @@ int smi_dqn_greedy(const float* adv, int64_t lda, const float* val, int64_t val_
  * (int32) may be NULL; stats[2] = { mean(w loss), mean(loss) }.  partials: a
  * caller-owned device workspace of at least smi_dqn_c51_partials_bytes(B)
  * bytes (8-byte aligned) for the workgroups' fp64 sums; a second launch of one
- * wave adds them in a fixed order into stats.  SMI_E_ARG (nothing launched):
+ * wave adds them in a fixed order into stats.  The clamp is torch.clamp's: a
+ * NaN reward or done gives a NaN row of m_out, td_out, dadv and dval and NaN
+ * stats, never a finite loss; +-inf rewards go to the bounds.  SMI_E_ARG
+ * (nothing launched):
  * NULL required pointer, B < 1, A < 1, N outside [2, 64], A N > 3072 (the LDS
- * slabs of a workgroup), v_max <= v_min, a leading dimension too small,
+ * slabs of a workgroup), v_max <= v_min or NaN, a leading dimension too small,
  * dueling without its pointers, too few partials bytes. */
 int smi_dqn_c51_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
                    const float* adv_target, int64_t ldt, const float* val, int64_t ldval,

@@ -27,6 +27,7 @@
 //             of the online net with DOUBLE_Q, of the target net otherwise
 //   p'      = p_target(s')[a*, .]
 //   Tz_j    = clamp(r + gamma * ((1 - d) * z_j), v_min, v_max);  b_j = (Tz_j - v_min) / D
+//             (torch.clamp: +-inf go to the bounds, a NaN stays NaN)
 //   m_i     = sum_{j = 0..N-1} p'_j * max(0, 1 - |b_j - i|)      j ascending
 //             (the gather form of the textbook floor / ceil scatter, its l == u
 //             corner included: no atomics, continuous in b, the same bits on
@@ -38,6 +39,13 @@
 //   dadv[a',i] = g_i * ([a' == a_taken] - 1/A), dval[i] = g_i     (dueling)
 //   dadv[a_taken,i] = g_i, 0 for the other actions                (otherwise)
 //   stats = { mean(w loss), mean(loss) }, fixed-order fp64 sums
+// NaN: a NaN reward or done makes every Tz_j, b_j and with them the whole row
+// of m, its loss (td) and its gradients NaN, as the reference's torch.clamp
+// does (fminf(fmaxf()) alone would return v_min and hand the sum tree a finite
+// priority); a NaN weight reaches the row's gradients and stats[0] only; a NaN
+// logit of the action taken reaches td and that action's gradients.  A NaN
+// expected value never compares greater, so the arg-max scan steps over it
+// (and keeps it when it is action 0); what a* is then is not specified.
 // The action index is clamped as dqn_action_index does.  A shard differs in the
 // three places smi_dqn_td_shard documents: g divides by B_global, td goes to
 // td_all[row0 + i] with +0.0f written to every other entry of td_all, and the
@@ -46,10 +54,15 @@
 // Work split (reasoning from the code; measured figures: DESIGN.md §6): one
 // WAVE per row, one LANE per atom.  A workgroup of kWG threads holds 4 rows at
 // a time and owns a fixed contiguous block of rows (c51_rows_per_block: from B
-// and the CU count only).  Each wave stages one net's A N slab of its row in
-// its own LDS region (16-byte loads where base and leading dimension allow,
-// decided per launch on the host), reuses the region for the three nets in
-// turn, and reads it twice: the dueling mean over a, then the per-action
+// and the CU count only; one quad of rows up to B = 16 CUs, then 2, 3, ...).
+// Each wave stages one net's A N slab of its row in its own LDS region, reuses
+// the region for the three nets in turn, and reads it twice.  The staging form
+// is ONE decision per launch, made on the host: 16-byte loads (and dwords for
+// the last A N % 4 scores) when every score slab the form reads (adv,
+// adv_target, and adv_next with DOUBLE_Q) has a 16-byte aligned base and a
+// leading dimension that is a multiple of 4, dword loads for all of them
+// otherwise; val rows, outputs and an adv_next the form does not read have no
+// say.  The two reads: the dueling mean over a, then the per-action
 // softmax.  val rows, p', b and m live in one register per lane; the projection
 // is N steps of a wave-uniform lane broadcast (v_readlane) and 4-5 VALU ops.
 // Lanes i >= N carry -inf / 0 and never store.  Each workgroup writes
@@ -102,6 +115,13 @@ __device__ __forceinline__ float c51_wave_max(float v) {
 // lane j's value in every lane; j is wave uniform (a v_readlane)
 __device__ __forceinline__ float c51_lane(float v, int j) {
   return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
+}
+
+// torch.clamp(y, lo, hi): a NaN stays NaN (fmaxf / fminf return their other
+// operand); every other input has the bits of fminf(fmaxf(y, lo), hi)
+// (clamp5 of smi_device.hpp with the bounds as arguments)
+__device__ __forceinline__ float c51_clamp(float y, float lo, float hi) {
+  return y != y ? y : fminf(fmaxf(y, lo), hi);
 }
 
 // one row's A N scores into the wave's LDS region; the loads of a lane are
@@ -238,14 +258,16 @@ __global__ void __launch_bounds__(kWG) c51_td_kernel(C51TdArgs p) {
       // ---- projection onto the support, gather form
       const float r = p.rew[row * p.rs], d = p.done[row * p.ds];
       float tz = r + p.gamma * ((1.f - d) * z);
-      tz = fminf(fmaxf(tz, p.v_min), p.v_max);
+      tz = c51_clamp(tz, p.v_min, p.v_max);
       const float b = (tz - p.v_min) / delta;
       const float fi = (float)lane;
       float m = 0.f;
       for (int j = 0; j < N; ++j) {
         const float pj = c51_lane(pp, j), bj = c51_lane(b, j);
         const float wgt = 1.f - fabsf(bj - fi);
-        m = m + pj * (wgt > 0.f ? wgt : 0.f);
+        // a NaN b_j stays (as act_f's relu).  One wave-wide test of b after the
+        // loop with the old max here was measured and is no gain: DESIGN.md §6
+        m = m + pj * (wgt <= 0.f ? 0.f : wgt);
       }
       // ---- cross-entropy against the online net's log-softmax at the action taken
       c51_stage(p.adv + row * p.lda, AN, p.vec, slab, lane);
