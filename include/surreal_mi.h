@@ -1032,6 +1032,71 @@ int smi_dqn_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, 
 /* bytes of smi_dqn_c51_td's partials workspace for B rows (host only) */
 int64_t smi_dqn_c51_partials_bytes(int64_t B);
 
+/* --------------------------------------- quantile-regression (QR) DQN pieces */
+/* The quantile head (QR-DQN, Dabney et al. 2018) of DQNLearner: N quantile
+ * values per action, 1 <= N <= 256, A N <= 4096, no support.  The slabs have
+ * smi_dqn_c51_td's layout: adv / adv_next / adv_target [B][ld >= A N], action
+ * major (column a N + i is quantile i of action a); val / val_next /
+ * val_target [B][ld >= N] (read only with dueling).  Per row, fp32 (the full
+ * operation order, the sum orders included: dqn_quant_kernels.hip):
+ *   theta[a,i] = (adv[a,i] - mean_a' adv[a',i]) + val[i] (dueling) | adv[a,i]
+ *   Q[a] = (sum_i theta[a,i]) / N
+ *   a* = first arg-max of Q(s') of the online net (double_q) | the target net
+ *   T_j = r + gamma ((1 - d) theta_target(s')[a*,j]);  tau_i = (2 i + 1) / (2 N)
+ *   u_ij = T_j - theta(s)[a_taken,i];  c_ij = |tau_i - [u_ij < 0]|
+ *   kappa > 0:  S_i = (sum_j c_ij huber_kappa(u_ij)) / kappa,
+ *               G_i = (sum_j c_ij clamp(u_ij, -kappa, kappa)) / kappa
+ *   kappa == 0: S_i = sum_j c_ij |u_ij|,  G_i = sum_j c_ij sign(u_ij)   (pinball)
+ *   loss = (sum_i S_i) / N;  g_i = (w (-(G_i / N))) / B
+ * Outputs: dadv [B][ldd >= A N] = g_i ([a' == a_taken] - 1/A) (dueling) | g_i at
+ * a_taken and 0 elsewhere, every entry of the A N columns written; dval
+ * [B][ldv >= N] = g_i (dueling only); td_out [B] = the row's loss (>= 0: the
+ * priority signal of a prioritized replay); t_out [B][N] (the targets T) and
+ * astar_out [B] (int32) may be NULL; stats[2] = { mean(w loss), mean(loss) }.
+ * partials: a caller-owned device workspace of at least
+ * smi_dqn_qr_partials_bytes(B) bytes (8-byte aligned) for the workgroups' fp64
+ * sums; the one-wave statistics launch of smi_dqn_c51_td adds them in a fixed
+ * order.  N <= 64 runs one wave per row, N > 64 one workgroup per row.  A NaN
+ * reward or done gives a NaN row of t_out, td_out, dadv and dval and NaN
+ * stats, never a finite loss; an infinite reward gives td = +inf.  SMI_E_ARG
+ * (nothing launched): NULL required pointer, B < 1, A < 1, N outside [1, 256],
+ * A N > 4096, kappa < 0 or NaN, a leading dimension too small, dueling without
+ * its pointers, too few partials bytes. */
+int smi_dqn_qr_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                  const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                  const float* val_next, int64_t ldval_next, const float* val_target,
+                  int64_t ldval_target, const float* actions, int64_t action_stride,
+                  const float* rewards, int64_t reward_stride, const float* dones,
+                  int64_t done_stride, const float* w, int64_t B, int A, int N, float kappa,
+                  float gamma, int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                  int64_t ldv, float* td_out, float* t_out, int32_t* astar_out, void* partials,
+                  int64_t partials_bytes, float* stats, void* stream);
+/* One rank's shard of smi_dqn_qr_td (the same kernels; smi_dqn_qr_td is
+ * B_global = B, row0 = 0), with exactly the three differences of
+ * smi_dqn_td_shard: g divides by (float)B_global; td_all [B_global] receives
+ * the shard's losses at row0 + i and +0.0f everywhere else; stats are the
+ * shard's sums / B_global.  dadv, dval, t_out, astar_out, w and partials
+ * (smi_dqn_qr_partials_bytes(B)) are the shard's own.  SMI_E_ARG: everything
+ * smi_dqn_qr_td rejects, B_global < B, row0 < 0, row0 + B > B_global. */
+int smi_dqn_qr_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                        const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                        const float* val_next, int64_t ldval_next, const float* val_target,
+                        int64_t ldval_target, const float* actions, int64_t action_stride,
+                        const float* rewards, int64_t reward_stride, const float* dones,
+                        int64_t done_stride, const float* w, int64_t B, int64_t B_global,
+                        int64_t row0, int A, int N, float kappa, float gamma, int dueling,
+                        int double_q, float* dadv, int64_t ldd, float* dval, int64_t ldv,
+                        float* td_all, float* t_out, int32_t* astar_out, void* partials,
+                        int64_t partials_bytes, float* stats, void* stream);
+/* q_out [rows][ldq >= A] = the mean quantiles Q[a] of smi_dqn_qr_td over one
+ * pair of head matrices; greedy_out [rows] (int32, may be NULL) = the first
+ * index of each row's maximum (FFQfunc.forward, QAgentBatch.act).  kappa plays
+ * no part in Q, so the call has no such argument. */
+int smi_dqn_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
+                 int N, int dueling, float* q_out, int64_t ldq, int32_t* greedy_out, void* stream);
+/* bytes of smi_dqn_qr_td's partials workspace for B rows (host only) */
+int64_t smi_dqn_qr_partials_bytes(int64_t B);
+
 /* ------------------------------------------------------ DDPG n-step target */
 /* Replaces the target of DDPGLearner._optimize (surreal/learner/ddpg.py:279-283):
  *   y = r + gamma_n * q_next * (1 - done); with twin critics y = min(y, y2). */

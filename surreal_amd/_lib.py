@@ -182,6 +182,13 @@ _SIGS = {
     'smi_dqn_c51_q': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, c_int, c_f32, c_f32, c_int, P, c_i64,
                               P, P]),
     'smi_dqn_c51_partials_bytes': (c_i64, [c_i64]),
+    'smi_dqn_qr_td': (c_int, [P, c_i64] * 9 + [P, c_i64, c_int, c_int, c_f32, c_f32, c_int, c_int, P,
+                                               c_i64, P, c_i64, P, P, P, P, c_i64, P, P]),
+    'smi_dqn_qr_td_shard': (c_int, [P, c_i64] * 9 + [P, c_i64, c_i64, c_i64, c_int, c_int, c_f32,
+                                                     c_f32, c_int, c_int, P, c_i64, P, c_i64, P, P,
+                                                     P, P, c_i64, P, P]),
+    'smi_dqn_qr_q': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, c_int, c_int, P, c_i64, P, P]),
+    'smi_dqn_qr_partials_bytes': (c_i64, [c_i64]),
     'smi_neg_mean_grad': (c_int, [P, c_i64, c_i64, P, P, P]),
     'smi_tanh_backward': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, P, c_i64, P]),
     'smi_copy_cols': (c_int, [P, c_i64, c_i64, c_int, P, c_i64, P]),

@@ -343,7 +343,8 @@ class QAgentBatch(object):
     maximum, as torch's max(1)[1] on the CPU) then serve the greedy agents,
     and one D2H copy returns the N actions.  With algo.distributional.enabled
     the model has categorical heads and smi_dqn_c51_q's greedy output (the
-    first maximum of the expected values) takes smi_dqn_greedy's place."""
+    first maximum of the expected values) takes smi_dqn_greedy's place; with
+    kind 'quantile' smi_dqn_qr_q's (the first maximum of the mean quantiles)."""
 
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
         from .config import ConfigError
@@ -415,7 +416,7 @@ class QAgentBatch(object):
             xd = torch.from_numpy(x).to(self.device)
             net = _QNet(self.q_func, self._bufs)
             adv, val = net.fwd(xd, self.n, 'act')
-            if self.q_func.atoms:      # categorical heads: arg-max of the expected values
+            if self.q_func.atoms or self.q_func.quantiles:    # arg-max of the expected values
                 net.expected_q(adv, val, self.n, 'act', greedy=self._greedy)
             else:
                 L.call('smi_dqn_greedy', L.ptr(adv), A, L.ptr(val), 1, self.n, A,

@@ -201,8 +201,11 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
             'beta_anneal_iters': None,
             'eps': 1e-6,
         },
-        # categorical heads (C51): atoms on the support [v_min, v_max]
-        'distributional': {'enabled': False, 'atoms': 51, 'v_min': -10.0, 'v_max': 10.0},
+        # distributional heads.  kind 'categorical' (C51): atoms on the support
+        # [v_min, v_max]; kind 'quantile' (QR-DQN): atoms is the quantile count,
+        # kappa the Huber threshold (0: the pinball loss), v_min / v_max are not read
+        'distributional': {'enabled': False, 'kind': 'categorical', 'atoms': 51, 'v_min': -10.0,
+                           'v_max': 10.0, 'kappa': 1.0},
     },
     'eval': {'eps': 0.05},
     'replay': {'batch_size': 512, 'memory_size': int(1000000 / 3),

@@ -597,6 +597,69 @@ int smi_dqn_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, 
 
 int64_t smi_dqn_c51_partials_bytes(int64_t B) { return c51_partials_bytes(B); }
 
+int smi_dqn_qr_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                  const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                  const float* val_next, int64_t ldval_next, const float* val_target,
+                  int64_t ldval_target, const float* actions, int64_t action_stride,
+                  const float* rewards, int64_t reward_stride, const float* dones,
+                  int64_t done_stride, const float* w, int64_t B, int A, int N, float kappa,
+                  float gamma, int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                  int64_t ldv, float* td_out, float* t_out, int32_t* astar_out, void* partials,
+                  int64_t partials_bytes, float* stats, void* stream) {
+  REQUIRE(adv && adv_target && actions && rewards && dones && dadv && td_out && partials && stats,
+          "dqn_qr_td: null pointer");
+  REQUIRE(!double_q || adv_next,
+          "dqn_qr_td: double_q without the online quantiles at s' (null pointer)");
+  REQUIRE(B >= 1, "dqn_qr_td: B < 1");
+  REQUIRE(!dueling || (val && val_target && dval && (!double_q || val_next)),
+          "dqn_qr_td: dueling needs val, val_target, dval (and val_next with double_q)");
+  return launch_qr_td(adv, lda, adv_next, ldn, adv_target, ldt, val, ldval, val_next, ldval_next,
+                      val_target, ldval_target, actions, action_stride, rewards, reward_stride,
+                      dones, done_stride, w, B, B, 0, A, N, kappa, gamma, dueling, double_q, dadv,
+                      ldd, dval, ldv, td_out, t_out, astar_out, static_cast<double*>(partials),
+                      partials_bytes, stats, SMI_STREAM(stream));
+}
+
+int smi_dqn_qr_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                        const float* adv_target, int64_t ldt, const float* val, int64_t ldval,
+                        const float* val_next, int64_t ldval_next, const float* val_target,
+                        int64_t ldval_target, const float* actions, int64_t action_stride,
+                        const float* rewards, int64_t reward_stride, const float* dones,
+                        int64_t done_stride, const float* w, int64_t B, int64_t B_global,
+                        int64_t row0, int A, int N, float kappa, float gamma, int dueling,
+                        int double_q, float* dadv, int64_t ldd, float* dval, int64_t ldv,
+                        float* td_all, float* t_out, int32_t* astar_out, void* partials,
+                        int64_t partials_bytes, float* stats, void* stream) {
+  REQUIRE(adv && adv_target && actions && rewards && dones && dadv && td_all && partials && stats,
+          "dqn_qr_td_shard: null pointer");
+  REQUIRE(!double_q || adv_next,
+          "dqn_qr_td_shard: double_q without the online quantiles at s' (null pointer)");
+  REQUIRE(B >= 1, "dqn_qr_td_shard: B < 1");
+  REQUIRE(B_global >= B, "dqn_qr_td_shard: B_global < B");
+  REQUIRE(row0 >= 0, "dqn_qr_td_shard: row0 < 0");
+  REQUIRE(row0 <= B_global - B, "dqn_qr_td_shard: row0 + B > B_global");
+  REQUIRE(!dueling || (val && val_target && dval && (!double_q || val_next)),
+          "dqn_qr_td_shard: dueling needs val, val_target, dval (and val_next with double_q)");
+  return launch_qr_td(adv, lda, adv_next, ldn, adv_target, ldt, val, ldval, val_next, ldval_next,
+                      val_target, ldval_target, actions, action_stride, rewards, reward_stride,
+                      dones, done_stride, w, B, B_global, row0, A, N, kappa, gamma, dueling,
+                      double_q, dadv, ldd, dval, ldv, td_all, t_out, astar_out,
+                      static_cast<double*>(partials), partials_bytes, stats, SMI_STREAM(stream));
+}
+
+int smi_dqn_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
+                 int N, int dueling, float* q_out, int64_t ldq, int32_t* greedy_out,
+                 void* stream) {
+  REQUIRE(adv && q_out, "dqn_qr_q: null pointer");
+  REQUIRE(rows >= 0, "dqn_qr_q: rows < 0");
+  REQUIRE(!dueling || val, "dqn_qr_q: dueling needs val");
+  if (rows == 0) return SMI_OK;
+  return launch_qr_q(adv, lda, val, ldv, rows, A, N, dueling, q_out, ldq, greedy_out,
+                     SMI_STREAM(stream));
+}
+
+int64_t smi_dqn_qr_partials_bytes(int64_t B) { return qr_partials_bytes(B); }
+
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream) {
   REQUIRE(q && dq && n > 0, "neg_mean_grad: bad args");

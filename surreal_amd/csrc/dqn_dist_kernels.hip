@@ -53,7 +53,7 @@
 //
 // Work split (reasoning from the code; measured figures: DESIGN.md §6): one
 // WAVE per row, one LANE per atom.  A workgroup of kWG threads holds 4 rows at
-// a time and owns a fixed contiguous block of rows (c51_rows_per_block: from B
+// a time and owns a fixed contiguous block of rows (dqn_rows_per_block: from B
 // and the CU count only; one quad of rows up to B = 16 CUs, then 2, 3, ...).
 // Each wave stages one net's A N slab of its row in its own LDS region, reuses
 // the region for the three nets in turn, and reads it twice.  The staging form
@@ -78,7 +78,6 @@ namespace smi {
 
 constexpr int kC51MaxAtoms = 64;                 // one lane per atom
 constexpr int kC51LdsBytes = 48 * 1024;          // the kNW slabs of a workgroup: A N <= 3072
-constexpr int kC51BlocksPerCU = 4;               // row blocks aimed at per CU
 
 struct C51TdArgs {
   const float* adv; int64_t lda;
@@ -100,21 +99,10 @@ struct C51TdArgs {
   float* td; float* m_out; int32_t* astar; double* partials;
 };
 
-// LDS traffic between the lanes of ONE wave: order the wave's own accesses
-__device__ __forceinline__ void c51_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-}
-
 __device__ __forceinline__ float c51_wave_max(float v) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
-}
-
-// lane j's value in every lane; j is wave uniform (a v_readlane)
-__device__ __forceinline__ float c51_lane(float v, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
 }
 
 // torch.clamp(y, lo, hi): a NaN stays NaN (fmaxf / fminf return their other
@@ -124,56 +112,13 @@ __device__ __forceinline__ float c51_clamp(float y, float lo, float hi) {
   return y != y ? y : fminf(fmaxf(y, lo), hi);
 }
 
-// one row's A N scores into the wave's LDS region; the loads of a lane are
-// issued 4 at a time before their LDS stores
+// one row's A N scores into the wave's LDS region (dqn_copy_slab, ordered
+// against the wave's reads of the previous net)
 __device__ __forceinline__ void c51_stage(const float* __restrict__ src, int AN, int vec,
                                           float* __restrict__ slab, int lane) {
-  c51_wave_sync();                               // the previous net's reads are done
-  int done = 0;
-  if (vec) {
-    const int n4 = AN >> 2;
-    const float4* s4 = reinterpret_cast<const float4*>(src);
-    float4* d4 = reinterpret_cast<float4*>(slab);
-    for (int base = 0; base < n4; base += 4 * 64) {
-      float4 v[4];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = base + u * 64 + lane;
-        v[u] = e < n4 ? s4[e] : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int e = base + u * 64 + lane;
-        if (e < n4) d4[e] = v[u];
-      }
-    }
-    done = n4 << 2;                              // the last AN % 4 scores follow as dwords
-  }
-  for (int base = done; base < AN; base += 4 * 64) {
-    float v[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = base + u * 64 + lane;
-      v[u] = e < AN ? src[e] : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int e = base + u * 64 + lane;
-      if (e < AN) slab[e] = v[u];
-    }
-  }
-  c51_wave_sync();
-}
-
-// mean over the actions of atom `lane`, summed left to right (0 without dueling)
-template <bool DUELING>
-__device__ __forceinline__ float c51_atom_mean(const float* __restrict__ slab, int A, int N,
-                                               int lane) {
-#pragma clang fp contract(off)
-  if (!DUELING || lane >= N) return 0.f;
-  float s = slab[lane];
-  for (int a = 1; a < A; ++a) s = s + slab[a * N + lane];
-  return s / (float)A;
+  dqn_wave_sync();                               // the previous net's reads are done
+  dqn_copy_slab<64>(src, AN, vec, slab, lane);
+  dqn_wave_sync();
 }
 
 // l[a, lane]; -inf in the lanes past the last atom
@@ -245,13 +190,13 @@ __global__ void __launch_bounds__(kWG) c51_td_kernel(C51TdArgs p) {
       if (DOUBLE_Q) {
         c51_stage(p.adv_n + row * p.ldn, AN, p.vec, slab, lane);
         const float vn = DUELING && on ? p.val_n[row * p.ldvn + lane] : 0.f;
-        const float mn = c51_atom_mean<DUELING>(slab, A, N, lane);
+        const float mn = dqn_col_mean<DUELING>(slab, A, N, lane);
         astar = c51_first_argmax<DUELING>(slab, A, N, lane, mn, vn, z, nullptr);
       }
       // ---- p' = p_target(s')[a*, .]
       c51_stage(p.adv_t + row * p.ldt, AN, p.vec, slab, lane);
       const float vt = DUELING && on ? p.val_t[row * p.ldvt + lane] : 0.f;
-      const float mt = c51_atom_mean<DUELING>(slab, A, N, lane);
+      const float mt = dqn_col_mean<DUELING>(slab, A, N, lane);
       if (!DOUBLE_Q) astar = c51_first_argmax<DUELING>(slab, A, N, lane, mt, vt, z, nullptr);
       const C51Moments t = c51_moments(c51_logit<DUELING>(slab, astar, N, lane, mt, vt), z);
       const float pp = t.e / t.S;
@@ -263,7 +208,7 @@ __global__ void __launch_bounds__(kWG) c51_td_kernel(C51TdArgs p) {
       const float fi = (float)lane;
       float m = 0.f;
       for (int j = 0; j < N; ++j) {
-        const float pj = c51_lane(pp, j), bj = c51_lane(b, j);
+        const float pj = dqn_lane(pp, j), bj = dqn_lane(b, j);
         const float wgt = 1.f - fabsf(bj - fi);
         // a NaN b_j stays (as act_f's relu).  One wave-wide test of b after the
         // loop with the old max here was measured and is no gain: DESIGN.md §6
@@ -272,13 +217,13 @@ __global__ void __launch_bounds__(kWG) c51_td_kernel(C51TdArgs p) {
       // ---- cross-entropy against the online net's log-softmax at the action taken
       c51_stage(p.adv + row * p.lda, AN, p.vec, slab, lane);
       const float v = DUELING && on ? p.val[row * p.ldv + lane] : 0.f;
-      const float mean = c51_atom_mean<DUELING>(slab, A, N, lane);
+      const float mean = dqn_col_mean<DUELING>(slab, A, N, lane);
       const int ai = dqn_action_index(p.act[row * p.as], A);
       const float l = c51_logit<DUELING>(slab, ai, N, lane, mean, v);
       const C51Moments o = c51_moments(l, z);
       const float term = on ? m * ((l - o.mx) - logf(o.S)) : 0.f;
-      float s = c51_lane(term, 0);
-      for (int i = 1; i < N; ++i) s = s + c51_lane(term, i);
+      float s = dqn_lane(term, 0);
+      for (int i = 1; i < N; ++i) s = s + dqn_lane(term, i);
       const float loss = -s;
       const float wi = p.w ? p.w[row] : 1.f;
       if (on) {
@@ -343,34 +288,23 @@ c51_q_kernel(const float* __restrict__ adv, int64_t lda, const float* __restrict
        row += (int64_t)gridDim.x * kNW) {
     c51_stage(adv + row * lda, AN, vec, slab, lane);
     const float v = DUELING && lane < N ? val[row * ldv + lane] : 0.f;
-    const float mean = c51_atom_mean<DUELING>(slab, A, N, lane);
+    const float mean = dqn_col_mean<DUELING>(slab, A, N, lane);
     const int best = c51_first_argmax<DUELING>(slab, A, N, lane, mean, v, z, q + row * ldq);
     if (greedy && lane == 0) greedy[row] = best;
   }
 }
 
 // ------------------------------------------------------------------- host
-static int c51_cus() {
-  int dev = 0, cus = 256;
-  (void)hipGetDevice(&dev);
-  (void)hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev);
-  return cus < 1 ? 1 : cus;
-}
-
-// rows of one workgroup's block: the quads of kNW rows dealt evenly to
-// kC51BlocksPerCU blocks per CU
-static int64_t c51_rows_per_block(int64_t B, int cus) {
-  const int64_t quads = (B + kNW - 1) / kNW, blocks = (int64_t)kC51BlocksPerCU * cus;
-  return kNW * ((quads + blocks - 1) / blocks);
+// the statistics launch of both distributional units: nb slots of {sum w loss,
+// sum loss} into stats[2] = the sums / Bg
+int launch_dqn_dist_stats(const double* partials, int nb, double Bg, float* stats, hipStream_t st) {
+  hipLaunchKernelGGL(c51_stats_kernel, dim3(1), dim3(64), 0, st, partials, nb, Bg, stats);
+  return check_launch("c51_stats_kernel");
 }
 
 // an upper bound of the row blocks of any device: one per quad of rows
 int64_t c51_partials_bytes(int64_t B) {
   return B < 1 ? 0 : (B + kNW - 1) / kNW * 2 * (int64_t)sizeof(double);
-}
-
-static bool c51_aligned16(const void* p, int64_t ld) {
-  return !p || ((reinterpret_cast<uintptr_t>(p) & 15) == 0 && (ld & 3) == 0);
 }
 
 // the checks both launchers share; 0 or SMI_E_ARG with the message set
@@ -400,13 +334,13 @@ int launch_c51_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
   if (lda < AN || ldt < AN || ldd < AN || (double_q && ldn < AN) ||
       (dueling && (ldv < N || ldvt < N || lddv < N || (double_q && ldvn < N))))
     return set_error(SMI_E_ARG, "dqn_c51_td: leading dims too small");
-  const int64_t rpb = c51_rows_per_block(B, c51_cus());
+  const int64_t rpb = dqn_rows_per_block(B, dqn_cus());
   const int64_t nb = (B + rpb - 1) / rpb;
   if (rpb > INT32_MAX || partials_bytes < nb * 2 * (int64_t)sizeof(double))
     return set_error(SMI_E_ARG, "dqn_c51_td: partials workspace too small "
                                 "(smi_dqn_c51_partials_bytes)");
-  const int vec = c51_aligned16(adv, lda) && c51_aligned16(adv_t, ldt) &&
-                  (!double_q || c51_aligned16(adv_n, ldn));
+  const int vec = dqn_aligned16(adv, lda) && dqn_aligned16(adv_t, ldt) &&
+                  (!double_q || dqn_aligned16(adv_n, ldn));
   const C51TdArgs p{adv, lda, adv_n, ldn, adv_t, ldt, val, ldv, val_n, ldvn, val_t, ldvt,
                     actions, as, rewards, rs, dones, ds, w, B, A, N, v_min, v_max, gamma,
                     B_global, row0, (int)rpb, vec, dadv, ldd, dval, lddv, td_all, m_out,
@@ -428,8 +362,7 @@ int launch_c51_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
     what = "c51_td_kernel<0,0>";
   }
   RC_CHECK(check_launch(what));
-  hipLaunchKernelGGL(c51_stats_kernel, dim3(1), dim3(64), 0, st, partials, (int)nb,
-                     (double)B_global, stats);
+  RC_CHECK(launch_dqn_dist_stats(partials, (int)nb, (double)B_global, stats, st));
   return check_launch(what);                     // smi_last_launch names the TD form
 }
 
@@ -440,10 +373,10 @@ int launch_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, i
   const int64_t AN = (int64_t)A * N;
   if (lda < AN || ldq < A || (dueling && ldv < N))
     return set_error(SMI_E_ARG, "dqn_c51_q: leading dims too small");
-  const int64_t cap = (int64_t)kC51BlocksPerCU * c51_cus();
+  const int64_t cap = (int64_t)kDistBlocksPerCU * dqn_cus();
   int64_t g = (rows + kNW - 1) / kNW;
   g = g < 1 ? 1 : (g > cap ? cap : g);
-  const int vec = c51_aligned16(adv, lda);
+  const int vec = dqn_aligned16(adv, lda);
   const size_t lds = (size_t)kNW * round4((int)AN) * sizeof(float);
   if (dueling) {
     hipLaunchKernelGGL((c51_q_kernel<true>), dim3((unsigned)g), dim3(kWG), lds, st, adv, lda, val,

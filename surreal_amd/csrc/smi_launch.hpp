@@ -92,6 +92,22 @@ int launch_c51_q(const float* adv, int64_t lda, const float* val, int64_t ldv, i
                  int N, float v_min, float v_max, int dueling, float* q, int64_t ldq,
                  int32_t* greedy, hipStream_t st);
 int64_t c51_partials_bytes(int64_t B);
+// the one-wave statistics launch of both distributional units: nb slots of
+// {sum w loss, sum loss} (fp64) into stats[2] = the sums / Bg
+int launch_dqn_dist_stats(const double* partials, int nb, double Bg, float* stats, hipStream_t st);
+// ---- dqn_quant_kernels.hip (quantile heads; checks as the categorical launchers')
+int launch_qr_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn,
+                 const float* adv_t, int64_t ldt, const float* val, int64_t ldv,
+                 const float* val_n, int64_t ldvn, const float* val_t, int64_t ldvt,
+                 const float* actions, int64_t as, const float* rewards, int64_t rs,
+                 const float* dones, int64_t ds, const float* w, int64_t B, int64_t B_global,
+                 int64_t row0, int A, int N, float kappa, float gamma, int dueling, int double_q,
+                 float* dadv, int64_t ldd, float* dval, int64_t lddv, float* td_all, float* t_out,
+                 int32_t* astar_out, double* partials, int64_t partials_bytes, float* stats,
+                 hipStream_t st);
+int launch_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
+                int N, int dueling, float* q, int64_t ldq, int32_t* greedy, hipStream_t st);
+int64_t qr_partials_bytes(int64_t B);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
 // skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
 // rows: the uint8 images come through the learners' time-major row map

@@ -85,6 +85,18 @@ exchange image) in place of smi_dqn_td and the same backward: the loss is the
 cross-entropy of the projected target distribution against the online net's
 log-softmax at the action taken, and `td_error` holds each row's loss (>= 0):
 the priority signal update_priorities_from_td reads.
+
+Quantile heads (algo.distributional.kind = 'quantile'; QR-DQN, Dabney et al.
+2018; this build's own specification, dqn_quant_kernels.hip): the same head
+layout with `atoms` quantile values per action (1 to 256, A atoms <= 4096) and
+no support, so v_min / v_max are not read.  forward() returns the mean
+quantiles (smi_dqn_qr_q), the agents act on their arg-max, and learn() runs
+smi_dqn_qr_td (smi_dqn_qr_td_shard under dp) in the same place: the loss of a
+row is the quantile-Huber loss (threshold algo.distributional.kappa; 0 is the
+pinball loss) summed over the online quantiles of the action taken and
+averaged over the target quantiles r + gamma (1 - d) theta_target(s')[a*, .],
+and `td_error` holds it (>= 0).  dp, the exchange image, graph replay and
+checkpoints are the categorical head's: nothing in them knows the head.
 """
 import numpy as np
 import torch
@@ -231,10 +243,32 @@ def check_atoms(A, atoms, v_min, v_max):
     return atoms, v_min, v_max
 
 
+QR_MAX_QUANTILES = 256    # one thread of a workgroup per quantile (dqn_quant_kernels.hip: kQrMaxN)
+QR_MAX_SLAB = 4096        # A * quantiles (kQrMaxSlab)
+
+
+def check_quantiles(A, quantiles, kappa, kind='quantile'):
+    """the ranges smi_dqn_qr_* serve, as (quantiles, kappa)"""
+    if kind != 'quantile':
+        raise ConfigError("DQN algo.distributional.kind must be 'categorical' or 'quantile', got "
+                          '{!r}'.format(kind))
+    quantiles, kappa = int(quantiles), float(kappa)
+    if not 1 <= quantiles <= QR_MAX_QUANTILES:
+        raise ConfigError('DQN algo.distributional.atoms (the quantile count) must be in [1, {}], '
+                          'got {}'.format(QR_MAX_QUANTILES, quantiles))
+    if A * quantiles > QR_MAX_SLAB:
+        raise ConfigError('DQN algo.distributional: {} actions x {} quantiles is over the '
+                          'kernel\'s {} values per row'.format(A, quantiles, QR_MAX_SLAB))
+    if not kappa >= 0.0:
+        raise ConfigError('DQN algo.distributional.kappa must be >= 0, got {}'.format(kappa))
+    return quantiles, kappa
+
+
 def dqn_model_kwargs(learner_config, env_config):
     """(D, A, hidden, dueling, FFQfunc keyword arguments): dqn_conv_specs for a
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
-    atoms, v_min and v_max.  Host only."""
+    atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead.
+    Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -243,7 +277,11 @@ def dqn_model_kwargs(learner_config, env_config):
         D, A, hidden, dueling = dqn_specs(learner_config, env_config)
         kw = {}
     dist = learner_config['algo'].get('distributional') or {}
-    if dist.get('enabled', False):
+    kind = dist.get('kind', 'categorical')
+    if dist.get('enabled', False) and kind != 'categorical':
+        kw['quantiles'], kw['kappa'] = check_quantiles(A, dist.get('atoms', 51),
+                                                       dist.get('kappa', 1.0), kind)
+    elif dist.get('enabled', False):
         kw['atoms'], kw['v_min'], kw['v_max'] = check_atoms(
             A, dist.get('atoms', 51), dist.get('v_min', -10.0), dist.get('v_max', 10.0))
     return D, A, hidden, dueling, kw
@@ -274,15 +312,23 @@ class FFQfunc(nn.Module):
     With convs ([[cout, k, stride]], input_shape (C, H, W)) the input is a
     uint8 or float32 (rows, C, H, W) device tensor and D_in is ignored.  With
     atoms (categorical heads over the support [v_min, v_max]) the action
-    stream ends in A * atoms logits and the state stream in atoms."""
+    stream ends in A * atoms logits and the state stream in atoms; with
+    quantiles (quantile heads with Huber threshold kappa; not together with
+    atoms) in A * quantiles values and quantiles."""
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
-                 convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None):
+                 convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
+                 quantiles=None, kappa=1.0):
         super().__init__()
         self.atoms, self.v_min, self.v_max = None, None, None
+        self.quantiles, self.kappa = None, None
+        if atoms is not None and quantiles is not None:
+            raise ConfigError('FFQfunc takes atoms (categorical heads) or quantiles, not both')
         if atoms is not None:
             self.atoms, self.v_min, self.v_max = check_atoms(int(action_dim), atoms, v_min, v_max)
-        N = self.atoms or 1
+        if quantiles is not None:
+            self.quantiles, self.kappa = check_quantiles(int(action_dim), quantiles, kappa)
+        N = self.atoms or self.quantiles or 1
         hs = [int(h) for h in fc_hidden_sizes]
         if not 1 <= len(hs) <= 3:
             raise ConfigError('FFQfunc takes 1 to 3 hidden widths')
@@ -356,7 +402,8 @@ class FFQfunc(nn.Module):
         D, hs, A = self.dims
         c = FFQfunc(D, A, hs, self.dueling, self.device, convs=self.convs,
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
-                    v_min=self.v_min, v_max=self.v_max)
+                    v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
+                    kappa=self.kappa if self.quantiles else 1.0)
         c.copy_from(self)
         return c
 
@@ -369,9 +416,10 @@ class FFQfunc(nn.Module):
     def forward(self, x):
         """q values [rows][A] (q_net.py:41-65,112-119) of a float32 device matrix
         (with convs: of a uint8 or float32 (rows, C, H, W) device tensor); with
-        atoms the expected values of the categorical heads (smi_dqn_c51_q)"""
+        atoms the expected values of the categorical heads (smi_dqn_c51_q), with
+        quantiles their means (smi_dqn_qr_q)"""
         adv, val = self.logits(x)
-        if self.atoms:
+        if self.atoms or self.quantiles:
             return _QNet(self, {}).expected_q(adv, val, adv.shape[0], 'f')
         if not self.dueling:
             return adv.clone()
@@ -431,11 +479,15 @@ class _QNet(LaunchNet):
                 dy = dx
 
     def expected_q(self, adv, val, rows, pre, greedy=None):
-        """Q [rows][A] of a categorical model's logits (fwd's outputs); greedy
-        (int32 [rows], optional) receives each row's first arg-max"""
+        """Q [rows][A] of a categorical or quantile model's head outputs (fwd's);
+        greedy (int32 [rows], optional) receives each row's first arg-max"""
         m = self.m
         A = m.dims[2]
         q = self.buf(pre + '_q', (rows, A))
+        if m.quantiles:
+            L.call('smi_dqn_qr_q', p(adv), adv.stride(0), p(val), m.quantiles, rows, A, m.quantiles,
+                   int(m.dueling), p(q), A, p(greedy), self.st)
+            return q
         L.call('smi_dqn_c51_q', p(adv), adv.stride(0), p(val), m.atoms, rows, A, m.atoms, m.v_min,
                m.v_max, int(m.dueling), p(q), A, p(greedy), self.st)
         return q
@@ -535,7 +587,8 @@ class DQNLearner(DeviceLearner):
     with model.convs; discrete actions).  A batch with a 'weights' entry (float32 [B] or [B, 1],
     replay.PrioritizedReplay.sample_batch) weights the Huber loss; after every
     learn() `td_error` is a device view [B] of Q(s, a) - y, with categorical
-    heads of each row's cross-entropy (>= 0)
+    heads of each row's cross-entropy (>= 0), with quantile heads of each row's
+    quantile-Huber loss (>= 0)
     (PrioritizedReplay.update_priorities_from_td).  With dp, `td_error` is
     [B_global]: the TD errors of the WHOLE draw, in draw order, on every rank
     (replay.sample_shard's idx_all names their slots)."""
@@ -562,7 +615,7 @@ class DQNLearner(DeviceLearner):
         gen = torch.Generator().manual_seed(seed)
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
         self.pixel = 'convs' in conv_kw
-        self.atoms = self.q_func.atoms
+        self.atoms, self.quantiles = self.q_func.atoms, self.q_func.quantiles
         self.q_target = self.q_func.clone()                   # dqn.py:17
         self.dp = self._dp_group(dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
@@ -641,7 +694,7 @@ class DQNLearner(DeviceLearner):
         adv_n = val_n = None
         if self.double_q:
             adv_n, val_n = net.fwd(obs_next, B, 'n')
-        N = self.atoms or 1
+        N = self.atoms or self.quantiles or 1
         dadv = net.buf('dadv', (B, A * N))
         dval = net.buf('dval', (B, N)) if dueling else None
         if self.dp is not None and (self._xbuf is None
@@ -650,9 +703,10 @@ class DQNLearner(DeviceLearner):
             # td_all (B_global) | stats (2)], the three as views of it
             self._xbuf, self.opt['g'], (self.td_error, self.stats_buf) = exchange_image(
                 self.device, self.q_func.flat.numel(), (B * self.dp.world_size, 2))
-        if self.atoms:
-            self._gradient_c51(net, B, (adv, adv_n, adv_t), (val, val_n, val_t), (act, a_s),
-                               (rew, r_s), (don, d_s), weights, dadv, dval)
+        if self.atoms or self.quantiles:
+            (self._gradient_c51 if self.atoms else self._gradient_qr)(
+                net, B, (adv, adv_n, adv_t), (val, val_n, val_t), (act, a_s), (rew, r_s), (don, d_s),
+                weights, dadv, dval)
         elif self.dp is None:
             self.td_error = net.buf('td', (B,))
             L.call('smi_dqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), 1, p(val_n), 1,
@@ -685,6 +739,25 @@ class DQNLearner(DeviceLearner):
                    p(self.stats_buf), net.st)
         else:
             L.call('smi_dqn_c51_td_shard', *args, B * self.dp.world_size, self.dp.rank * B, *tail,
+                   p(self.td_error), None, None, p(part), need, p(self.stats_buf), net.st)
+
+    def _gradient_qr(self, net, B, advs, vals, act, rew, don, weights, dadv, dval):
+        """_gradient's TD step for quantile heads: smi_dqn_qr_td and the
+        statistics launch, or the shard form into the exchange image's views"""
+        A, N, q = self.action_dim, self.quantiles, self.q_func
+        (adv, adv_n, adv_t), (val, val_n, val_t) = advs, vals
+        need = int(L.lib().smi_dqn_qr_partials_bytes(B))
+        part = net.buf('qr_partials', (need // 8,), torch.float64)
+        args = [p(adv), A * N, p(adv_n), A * N, p(adv_t), A * N, p(val), N, p(val_n), N, p(val_t), N,
+                p(act[0]), act[1], p(rew[0]), rew[1], p(don[0]), don[1], p(weights), B]
+        tail = [A, N, q.kappa, float(self.algo.gamma), int(q.dueling), int(self.double_q),
+                p(dadv), A * N, p(dval), N]
+        if self.dp is None:
+            self.td_error = net.buf('td', (B,))
+            L.call('smi_dqn_qr_td', *args, *tail, p(self.td_error), None, None, p(part), need,
+                   p(self.stats_buf), net.st)
+        else:
+            L.call('smi_dqn_qr_td_shard', *args, B * self.dp.world_size, self.dp.rank * B, *tail,
                    p(self.td_error), None, None, p(part), need, p(self.stats_buf), net.st)
 
     # ------------------------------------------------------- reference API

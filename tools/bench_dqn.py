@@ -30,7 +30,14 @@ math in eager torch on the same GPU tensors (log_softmax, index_add_
 projection, autograd to the three head outputs): what a user would otherwise
 write.  Each timed sample is --calls back-to-back calls between two events.
 
-Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10] [--pixel | --gpus N | --atoms N]
+--quantiles N [--kappa K] (1 <= N <= 256) does the same for the quantile head
+(QR-DQN): one smi_dqn_qr_td call next to the same math in eager torch (the
+pairs as u [B][N][N], torch.where for the Huber branches, autograd to the head
+outputs), and learn() with algo.distributional.kind = 'quantile' next to the
+scalar learner's.
+
+Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
+                                 [--pixel | --gpus N | --atoms N | --quantiles N [--kappa K]]
 """
 import argparse
 import copy
@@ -247,8 +254,29 @@ def torch_c51(adv, val, adv_n, val_n, adv_t, val_t, act, rew, done, w, A, N, v_m
     return torch.autograd.grad((w * loss).mean(), (adv, val)), loss.detach()
 
 
-def atoms_main(args):
-    N, B, D, v_min, v_max, gamma = args.atoms, 512, 17, -10.0, 10.0, 0.99
+def torch_qr(adv, val, adv_n, val_n, adv_t, val_t, act, rew, done, w, A, N, kappa, gamma):
+    """the quantile TD step in eager torch: dueling quantiles, double-Q arg-max of
+    their means, every (online, target) pair, the weighted quantile-Huber loss
+    and its gradients at (adv, val)"""
+    B = adv.shape[0]
+    th = lambda a, v: (lambda l: (l - l.mean(1, keepdim=True)) + v[:, None, :])(a.view(B, A, N))  # noqa: E731
+    rows = torch.arange(B, device=adv.device)
+    with torch.no_grad():
+        astar = th(adv_n, val_n).mean(2).argmax(1)
+        T = rew + gamma * ((1 - done) * th(adv_t, val_t)[rows, astar])
+    tau = (2 * torch.arange(N, device=adv.device, dtype=adv.dtype) + 1) / (2 * N)
+    u = T[:, None, :] - th(adv, val)[rows, act][:, :, None]
+    au = u.abs()
+    hub = torch.where(au <= kappa, 0.5 * u * u, kappa * (au - 0.5 * kappa)) / kappa if kappa > 0 else au
+    loss = ((tau[None, :, None] - (u.detach() < 0).float()).abs() * hub).sum(1).mean(1)
+    return torch.autograd.grad((w * loss).mean(), (adv, val)), loss.detach()
+
+
+def dist_main(args):
+    """--atoms N (the categorical head) or --quantiles N (the quantile head)"""
+    quant = bool(args.quantiles)
+    N, B, D, v_min, v_max, gamma = args.quantiles or args.atoms, 512, 17, -10.0, 10.0, 0.99
+    key = 'quantiles' if quant else 'atoms'
     p, st = L.ptr, L.stream()
     for A in (6, 18):
         g = torch.Generator().manual_seed(A)
@@ -258,8 +286,15 @@ def atoms_main(args):
         act, rew, done, w = b['actions'], b['rewards'], b['dones'], b['weights']
         dadv, dval, td = torch.zeros(B, A * N).cuda(), torch.zeros(B, N).cuda(), torch.zeros(B).cuda()
         stats = torch.zeros(2).cuda()
-        need = int(L.lib().smi_dqn_c51_partials_bytes(B))
+        need = int((L.lib().smi_dqn_qr_partials_bytes if quant else L.lib().smi_dqn_c51_partials_bytes)(B))
         part = torch.zeros(need // 8, dtype=torch.float64).cuda()
+
+        def hip_qr():
+            for _ in range(args.calls):
+                L.call('smi_dqn_qr_td', p(adv), A * N, p(adv_n), A * N, p(adv_t), A * N, p(val), N,
+                       p(val_n), N, p(val_t), N, p(act), 1, p(rew), 1, p(done), 1, p(w), B, A, N,
+                       args.kappa, gamma, 1, 1, p(dadv), A * N, p(dval), N, p(td), None, None, p(part),
+                       need, p(stats), st)
 
         def hip():
             for _ in range(args.calls):
@@ -273,9 +308,15 @@ def atoms_main(args):
             for _ in range(args.calls):
                 torch_c51(ga, gv, adv_n, val_n, adv_t, val_t, act.view(B).long(), rew, done,
                           w.view(B), A, N, v_min, v_max, gamma)
-        for name, fn in (('c51_td_and_stats', hip), ('torch_eager_c51_td', eager)):
+
+        def eager_qr():
+            for _ in range(args.calls):
+                torch_qr(ga, gv, adv_n, val_n, adv_t, val_t, act.view(B).long(), rew, done,
+                         w.view(B), A, N, args.kappa, gamma)
+        for name, fn in ((('qr_td_and_stats', hip_qr), ('torch_eager_qr_td', eager_qr)) if quant else
+                         (('c51_td_and_stats', hip), ('torch_eager_c51_td', eager))):
             med, q1, q3 = (1e3 * t / args.calls for t in timed(fn, args.iters, args.warmup))
-            print(json.dumps({'measurement': name, 'B': B, 'A': A, 'atoms': N,
+            print(json.dumps({'measurement': name, 'B': B, 'A': A, key: N,
                               'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
                               'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
                               'iters': args.iters}), flush=True)
@@ -285,11 +326,13 @@ def atoms_main(args):
         lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
         lc.replay.batch_size = B
         lc.algo.distributional.enabled, lc.algo.distributional.atoms = atoms is not None, N
+        if quant:
+            lc.algo.distributional.kind, lc.algo.distributional.kappa = 'quantile', args.kappa
         for graph in (False, True):
             learner = DQNLearner(lc, discrete_env_config(D, A), seed=0, use_graph=graph)
             med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
             print(json.dumps({'measurement': 'dqn_learn_' + ('graph' if graph else 'eager'),
-                              'atoms': atoms, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                              key: atoms, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
                               'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
 
 
@@ -302,13 +345,17 @@ def main():
                     help='N >= 2: the data-parallel loop, one process per GPU')
     ap.add_argument('--atoms', type=int, default=0,
                     help='N: the categorical (C51) head with N atoms instead of scalar heads')
+    ap.add_argument('--quantiles', type=int, default=0,
+                    help='N: the quantile (QR-DQN) head with N quantiles instead of scalar heads')
+    ap.add_argument('--kappa', type=float, default=1.0,
+                    help='--quantiles: the Huber threshold (0: the pinball loss)')
     ap.add_argument('--calls', type=int, default=20,
-                    help='--atoms: back-to-back kernel calls per timed sample')
+                    help='--atoms / --quantiles: back-to-back kernel calls per timed sample')
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
-    if args.atoms:
-        return atoms_main(args)
+    if args.atoms or args.quantiles:
+        return dist_main(args)
     if args.pixel:
         return pixel_main(args)
     B, D, A = 512, 17, 6
