@@ -1097,6 +1097,93 @@ int smi_dqn_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, i
 /* bytes of smi_dqn_qr_td's partials workspace for B rows (host only) */
 int64_t smi_dqn_qr_partials_bytes(int64_t B);
 
+/* ------------------------------------------- implicit quantile (IQN) DQN pieces */
+/* The implicit quantile head (IQN, Dabney et al. 2018b) of DQNLearner: the net
+ * takes a quantile fraction tau per SAMPLE ROW r = b N + n (N samples of
+ * observation b), so head outputs are adv [B N][ld >= A] and val [B N] (read
+ * only with dueling) and one observation's block is sample major, [N][A].
+ * The full specification (operation and sum orders, NaN rules, the cosine):
+ * csrc/dqn_iqn_kernels.hip.
+ *
+ * smi_iqn_taus: tau_out[row N + n] for rows [row0, row0 + rows) of a draw, a
+ * stateless counter-based generator: word 0 of Philox4x32-10 keyed by seed
+ * with the counter {sample index (row0 + row) N + n (64 bit), *step, stream_id},
+ * mapped to ((x >> 9) + 0.5) 2^-23: exact in fp32, never 0 or 1.  step is a
+ * DEVICE int32 (the learner's Adam step counter: a replayed graph draws new
+ * fractions).  SMI_E_ARG: NULL pointer, rows < 1, N outside [1, 64], row0 < 0,
+ * stream_id < 0. */
+int smi_iqn_taus(uint64_t seed, const int32_t* step, int stream_id, int64_t row0, int64_t rows,
+                 int N, float* tau_out, void* stream);
+/* Z [B N][ldz >= d] = H1[b] (.) phi,  phi[r][j] = relu(bias[j] + sum_i cos(pi i
+ * tau[r]) weight[j][i]), i < n_cos; H1 [B][ldh >= d], weight [d][n_cos], bias
+ * [d]; phi [B N][ldphi >= d] is written when not NULL (the backward reads it).
+ * One fp32-MFMA launch whose cosine operand is computed in registers.
+ * SMI_E_ARG: NULL required pointer, B < 1, N outside [1, 64], n_cos no multiple
+ * of 4 in [4, 64], d < 1, a leading dimension below d. */
+int smi_iqn_embed_forward(const float* tau, const float* H1, int64_t ldh, int64_t B, int N,
+                          const float* weight, const float* bias, int n_cos, int d, float* Z,
+                          int64_t ldz, float* phi, int64_t ldphi, void* stream);
+/* The backward of smi_iqn_embed_forward from dZ [B N][ldz]:
+ *   dH1 [B][lddh] = [H1 > 0] sum_n dZ[b N + n] (.) phi[b N + n]      (n ascending)
+ *   dW [d][n_cos] = sum_r dpre[r][j] cos(pi i tau[r]),  db [d] = sum_r dpre[r][j],
+ *   dpre = dZ (.) H1[b] (.) [phi > 0]
+ * dW and db are WRITTEN (any offset of a gradient image).  The row sum of dW
+ * is split over workgroups into scratch (smi_iqn_embed_scratch_bytes, may be
+ * NULL when that is 0) and added in a fixed order: no atomics, the same bits on
+ * every run.  dZ may arrive masked by Z > 0.  Two or three launches.  SMI_E_ARG
+ * as the forward, and too little scratch. */
+int smi_iqn_embed_backward(const float* dZ, int64_t ldz, const float* tau, const float* H1,
+                           int64_t ldh, const float* phi, int64_t ldphi, int64_t B, int N,
+                           float* dW, float* db, int n_cos, int d, float* dH1, int64_t lddh,
+                           void* scratch, int64_t scratch_bytes, void* stream);
+/* bytes of smi_iqn_embed_backward's scratch (host only) */
+int64_t smi_iqn_embed_scratch_bytes(int64_t B, int N, int n_cos, int d);
+/* smi_dqn_qr_td for implicit quantiles: N online samples with fractions tau
+ * [B N], N_target samples of the target net (adv_target, val_target: [B
+ * N_target] rows) and of the selecting online net at s' (adv_next, val_next;
+ * double_q), both in [1, 64], A max(N, N_target) <= 4096.  Per row b:
+ *   theta[n][a] = (adv[n][a] - mean_a' adv[n][a']) + val[n] (dueling) | adv[n][a]
+ *   Q[a] = mean over the net's samples;  a* = first arg-max of Q(s')
+ *   T_j = r + gamma ((1 - d) theta_target(s')[j][a*]);  u_ij = T_j - theta(s)[i][a_taken]
+ *   the pair terms, S_i and G_i of smi_dqn_qr_td with tau_i = tau[b N + i], j < N_target
+ *   loss = (sum_i S_i) / N_target;  g_i = (w (-(G_i / N_target))) / B
+ * Outputs: dadv [B N][ldd >= A] (every entry written), dval [B N] (dueling),
+ * td_out [B], t_out [B][N_target] and astar_out [B] (may be NULL), stats[2] =
+ * { mean(w loss), mean(loss) }; partials: smi_iqn_partials_bytes(B) bytes.
+ * NaN / inf as smi_dqn_qr_td.  SMI_E_ARG (nothing launched): NULL required
+ * pointer, B < 1, A < 1, a sample count outside [1, 64], A max(N, N_target) >
+ * 4096, kappa < 0 or NaN, a leading dimension below A, dueling without its
+ * pointers, too few partials bytes. */
+int smi_iqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+               const float* adv_target, int64_t ldt, const float* val, const float* val_next,
+               const float* val_target, const float* tau, const float* actions,
+               int64_t action_stride, const float* rewards, int64_t reward_stride,
+               const float* dones, int64_t done_stride, const float* w, int64_t B, int A, int N,
+               int N_target, float kappa, float gamma, int dueling, int double_q, float* dadv,
+               int64_t ldd, float* dval, float* td_out, float* t_out, int32_t* astar_out,
+               void* partials, int64_t partials_bytes, float* stats, void* stream);
+/* One rank's shard of smi_iqn_td, with exactly the three differences of
+ * smi_dqn_td_shard (g divides by B_global; td_all [B_global] receives the
+ * shard's losses at row0 + i and +0.0f elsewhere; stats are the shard's sums /
+ * B_global).  tau is the shard's own rows.  SMI_E_ARG: everything smi_iqn_td
+ * rejects, B_global < B, row0 < 0, row0 + B > B_global. */
+int smi_iqn_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                     const float* adv_target, int64_t ldt, const float* val, const float* val_next,
+                     const float* val_target, const float* tau, const float* actions,
+                     int64_t action_stride, const float* rewards, int64_t reward_stride,
+                     const float* dones, int64_t done_stride, const float* w, int64_t B,
+                     int64_t B_global, int64_t row0, int A, int N, int N_target, float kappa,
+                     float gamma, int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                     float* td_all, float* t_out, int32_t* astar_out, void* partials,
+                     int64_t partials_bytes, float* stats, void* stream);
+/* q_out [rows][ldq >= A] = the mean over K samples of theta (adv [rows K][lda >=
+ * A], val [rows K]); greedy_out [rows] (int32, may be NULL) = the first index
+ * of each row's maximum (FFQfunc.forward, QAgentBatch.act). */
+int smi_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int A, int K,
+              int dueling, float* q_out, int64_t ldq, int32_t* greedy_out, void* stream);
+/* bytes of smi_iqn_td's partials workspace for B rows (host only) */
+int64_t smi_iqn_partials_bytes(int64_t B);
+
 /* ------------------------------------------------------ DDPG n-step target */
 /* Replaces the target of DDPGLearner._optimize (surreal/learner/ddpg.py:279-283):
  *   y = r + gamma_n * q_next * (1 - done); with twin critics y = min(y, y2). */

@@ -189,6 +189,20 @@ _SIGS = {
                                                      P, P, c_i64, P, P]),
     'smi_dqn_qr_q': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, c_int, c_int, P, c_i64, P, P]),
     'smi_dqn_qr_partials_bytes': (c_i64, [c_i64]),
+    'smi_iqn_taus': (c_int, [ctypes.c_uint64, P, c_int, c_i64, c_i64, c_int, P, P]),
+    'smi_iqn_embed_forward': (c_int, [P, P, c_i64, c_i64, c_int, P, P, c_int, c_int, P, c_i64, P,
+                                      c_i64, P]),
+    'smi_iqn_embed_backward': (c_int, [P, c_i64, P, P, c_i64, P, c_i64, c_i64, c_int, P, P, c_int,
+                                       c_int, P, c_i64, P, c_i64, P]),
+    'smi_iqn_embed_scratch_bytes': (c_i64, [c_i64, c_int, c_int, c_int]),
+    'smi_iqn_td': (c_int, [P, c_i64] * 3 + [P] * 4 + [P, c_i64] * 3 + [P, c_i64, c_int, c_int, c_int,
+                                                                   c_f32, c_f32, c_int, c_int, P,
+                                                                   c_i64, P, P, P, P, P, c_i64, P, P]),
+    'smi_iqn_td_shard': (c_int, [P, c_i64] * 3 + [P] * 4 + [P, c_i64] * 3 +
+                         [P, c_i64, c_i64, c_i64, c_int, c_int, c_int, c_f32, c_f32, c_int, c_int, P,
+                          c_i64, P, P, P, P, P, c_i64, P, P]),
+    'smi_iqn_q': (c_int, [P, c_i64, P, c_i64, c_int, c_int, c_int, P, c_i64, P, P]),
+    'smi_iqn_partials_bytes': (c_i64, [c_i64]),
     'smi_neg_mean_grad': (c_int, [P, c_i64, c_i64, P, P, P]),
     'smi_tanh_backward': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, P, c_i64, P]),
     'smi_copy_cols': (c_int, [P, c_i64, c_i64, c_int, P, c_i64, P]),

@@ -344,7 +344,10 @@ class QAgentBatch(object):
     and one D2H copy returns the N actions.  With algo.distributional.enabled
     the model has categorical heads and smi_dqn_c51_q's greedy output (the
     first maximum of the expected values) takes smi_dqn_greedy's place; with
-    kind 'quantile' smi_dqn_qr_q's (the first maximum of the mean quantiles)."""
+    kind 'quantile' smi_dqn_qr_q's (the first maximum of the mean quantiles); with
+    kind 'implicit' each agent draws act_atoms quantile fractions (smi_iqn_taus
+    on the batch's own counter; kept as `tau`) and smi_iqn_q's arg-max of the
+    mean over them decides."""
 
     def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
         from .config import ConfigError
@@ -368,6 +371,8 @@ class QAgentBatch(object):
         self.T = np.zeros(self.n, dtype=np.int64)           # q_agent.py:33, per agent
         self._bufs = {}
         self._greedy = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.tau = None                 # implicit heads: the fractions of the last act()
+        self._tau_step = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def load_module_dict(self, module_dict):
         self.q_func.load_state_dict(module_dict['q_func'].state_dict())
@@ -415,8 +420,12 @@ class QAgentBatch(object):
         if greedy.any():
             xd = torch.from_numpy(x).to(self.device)
             net = _QNet(self.q_func, self._bufs)
-            adv, val = net.fwd(xd, self.n, 'act')
-            if self.q_func.atoms or self.q_func.quantiles:    # arg-max of the expected values
+            if self.q_func.implicit:      # act_atoms fractions per agent, a counter of its own
+                self.tau = net.taus(0, self._tau_step, 0, 0, self.n,
+                                    self.q_func.implicit['act_atoms'], 'act_tau')
+                self._tau_step.add_(1)
+            adv, val = net.fwd(xd, self.n, 'act', self.tau)
+            if self.q_func.atoms or self.q_func.quantiles or self.q_func.implicit:    # arg-max of the expected values
                 net.expected_q(adv, val, self.n, 'act', greedy=self._greedy)
             else:
                 L.call('smi_dqn_greedy', L.ptr(adv), A, L.ptr(val), 1, self.n, A,

@@ -27,7 +27,7 @@ CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-obje
 # measured at 128 segments, one MI355X: lstm_fwd 43.0 -> 40.9 us, lstm_bwd
 # 34.5 -> 27.0 us per launch, learn 3.48 -> 3.29 ms; the flag on the MFMA forms
 # of lstm_mfma.hip changed their rounding)
-# dqn_dist_kernels.hip and dqn_quant_kernels.hip are compiled without the
+# dqn_dist_kernels.hip, dqn_quant_kernels.hip and dqn_iqn_kernels.hip are compiled without the
 # packed-fp32 VALU forms (v_pk_add / mul / fma_f32): their per-lane arithmetic
 # is scalar by design (the host pass of the same command does not know the
 # feature and says so)
@@ -36,7 +36,7 @@ UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('sampler_kernels.hip', []), ('per_kernels.hip', []),
          ('linear_kernels.hip', []), ('linear_dw.hip', []), ('ddpg_kernels.hip', []),
          ('dqn_kernels.hip', []), ('dqn_dist_kernels.hip', NO_PK_F32),
-         ('dqn_quant_kernels.hip', NO_PK_F32),
+         ('dqn_quant_kernels.hip', NO_PK_F32), ('dqn_iqn_kernels.hip', NO_PK_F32),
          ('lstm_mfma.hip', []), ('lstm_valu.hip', ['-fno-slp-vectorize']), ('cnn_kernels.hip', []),
          ('conv_kernels.hip', []), ('stem.hip', []),
          ('head_kernels.hip', []), ('ppo_rnn_kernels.hip', []), ('ppo_rnn.hip', []),

@@ -203,7 +203,10 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
         },
         # distributional heads.  kind 'categorical' (C51): atoms on the support
         # [v_min, v_max]; kind 'quantile' (QR-DQN): atoms is the quantile count,
-        # kappa the Huber threshold (0: the pinball loss), v_min / v_max are not read
+        # kappa the Huber threshold (0: the pinball loss), v_min / v_max are not read;
+        # kind 'implicit' (IQN): atoms online samples per row (8 where the key is
+        # absent; set it, this table's 51 is the categorical default), and the
+        # optional keys target_atoms (= atoms), act_atoms (32), embed_dim (64)
         'distributional': {'enabled': False, 'kind': 'categorical', 'atoms': 51, 'v_min': -10.0,
                            'v_max': 10.0, 'kappa': 1.0},
     },

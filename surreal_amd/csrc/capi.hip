@@ -660,6 +660,84 @@ int smi_dqn_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, i
 
 int64_t smi_dqn_qr_partials_bytes(int64_t B) { return qr_partials_bytes(B); }
 
+int smi_iqn_taus(uint64_t seed, const int32_t* step, int stream_id, int64_t row0, int64_t rows,
+                 int N, float* tau_out, void* stream) {
+  REQUIRE(step && tau_out, "iqn_taus: null pointer");
+  return launch_iqn_taus(seed, step, stream_id, row0, rows, N, tau_out, SMI_STREAM(stream));
+}
+
+int smi_iqn_embed_forward(const float* tau, const float* H1, int64_t ldh, int64_t B, int N,
+                          const float* weight, const float* bias, int n_cos, int d, float* Z,
+                          int64_t ldz, float* phi, int64_t ldphi, void* stream) {
+  REQUIRE(tau && H1 && weight && bias && Z, "iqn_embed_forward: null pointer");
+  return launch_iqn_embed_fwd(tau, H1, ldh, B, N, weight, bias, n_cos, d, Z, ldz, phi, ldphi,
+                              SMI_STREAM(stream));
+}
+
+int smi_iqn_embed_backward(const float* dZ, int64_t ldz, const float* tau, const float* H1,
+                           int64_t ldh, const float* phi, int64_t ldphi, int64_t B, int N,
+                           float* dW, float* db, int n_cos, int d, float* dH1, int64_t lddh,
+                           void* scratch, int64_t scratch_bytes, void* stream) {
+  REQUIRE(dZ && tau && H1 && phi && dW && db && dH1, "iqn_embed_backward: null pointer");
+  return launch_iqn_embed_bwd(dZ, ldz, tau, H1, ldh, phi, ldphi, B, N, dW, db, n_cos, d, dH1, lddh,
+                              static_cast<float*>(scratch), scratch_bytes, SMI_STREAM(stream));
+}
+
+int64_t smi_iqn_embed_scratch_bytes(int64_t B, int N, int n_cos, int d) {
+  return iqn_embed_scratch_bytes(B, N, n_cos, d);
+}
+
+int smi_iqn_td_shard(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+                     const float* adv_target, int64_t ldt, const float* val, const float* val_next,
+                     const float* val_target, const float* tau, const float* actions,
+                     int64_t action_stride, const float* rewards, int64_t reward_stride,
+                     const float* dones, int64_t done_stride, const float* w, int64_t B,
+                     int64_t B_global, int64_t row0, int A, int N, int N_target, float kappa,
+                     float gamma, int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                     float* td_all, float* t_out, int32_t* astar_out, void* partials,
+                     int64_t partials_bytes, float* stats, void* stream) {
+  REQUIRE(adv && adv_target && tau && actions && rewards && dones && dadv && td_all && partials &&
+              stats, "iqn_td: null pointer");
+  REQUIRE(!double_q || adv_next, "iqn_td: double_q without the online samples at s' (null pointer)");
+  REQUIRE(B >= 1, "iqn_td: B < 1");
+  REQUIRE(B_global >= B, "iqn_td_shard: B_global < B");
+  REQUIRE(row0 >= 0, "iqn_td_shard: row0 < 0");
+  REQUIRE(row0 <= B_global - B, "iqn_td_shard: row0 + B > B_global");
+  REQUIRE(!dueling || (val && val_target && dval && (!double_q || val_next)),
+          "iqn_td: dueling needs val, val_target, dval (and val_next with double_q)");
+  return launch_iqn_td(adv, lda, adv_next, ldn, adv_target, ldt, val, val_next, val_target, tau,
+                       actions, action_stride, rewards, reward_stride, dones, done_stride, w, B,
+                       B_global, row0, A, N, N_target, kappa, gamma, dueling, double_q, dadv, ldd,
+                       dval, td_all, t_out, astar_out, static_cast<double*>(partials),
+                       partials_bytes, stats, SMI_STREAM(stream));
+}
+
+int smi_iqn_td(const float* adv, int64_t lda, const float* adv_next, int64_t ldn,
+               const float* adv_target, int64_t ldt, const float* val, const float* val_next,
+               const float* val_target, const float* tau, const float* actions,
+               int64_t action_stride, const float* rewards, int64_t reward_stride,
+               const float* dones, int64_t done_stride, const float* w, int64_t B, int A, int N,
+               int N_target, float kappa, float gamma, int dueling, int double_q, float* dadv,
+               int64_t ldd, float* dval, float* td_out, float* t_out, int32_t* astar_out,
+               void* partials, int64_t partials_bytes, float* stats, void* stream) {
+  return smi_iqn_td_shard(adv, lda, adv_next, ldn, adv_target, ldt, val, val_next, val_target, tau,
+                          actions, action_stride, rewards, reward_stride, dones, done_stride, w, B,
+                          B, 0, A, N, N_target, kappa, gamma, dueling, double_q, dadv, ldd, dval,
+                          td_out, t_out, astar_out, partials, partials_bytes, stats, stream);
+}
+
+int smi_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int A, int K,
+              int dueling, float* q_out, int64_t ldq, int32_t* greedy_out, void* stream) {
+  REQUIRE(adv && q_out, "iqn_q: null pointer");
+  REQUIRE(rows >= 0, "iqn_q: rows < 0");
+  REQUIRE(!dueling || val, "iqn_q: dueling needs val");
+  if (rows == 0) return SMI_OK;
+  return launch_iqn_q(adv, lda, val, rows, A, K, dueling, q_out, ldq, greedy_out,
+                      SMI_STREAM(stream));
+}
+
+int64_t smi_iqn_partials_bytes(int64_t B) { return iqn_partials_bytes(B); }
+
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream) {
   REQUIRE(q && dq && n > 0, "neg_mean_grad: bad args");

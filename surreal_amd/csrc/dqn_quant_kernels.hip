@@ -109,7 +109,6 @@ namespace smi {
 constexpr int kQrMaxN = 256;                     // one thread of a workgroup per quantile
 constexpr int kQrMaxSlab = 4096;                 // A N: 4 wave slabs of 16 KiB in the first form
 constexpr int kQrWaveN = 64;                     // N up to here: one wave per row
-constexpr int kQrRun = 8;                        // targets summed in fp32 before the fp64 add
 
 struct QrTdArgs {
   const float* adv; int64_t lda;
@@ -213,39 +212,7 @@ __device__ __forceinline__ int qr_row_argmax(const float* __restrict__ slab, int
   return best;
 }
 
-// ---- both forms: one online quantile's sums over the N targets, j ascending;
-// tj(j) is T_j in every lane (a readlane or an LDS broadcast)
-struct QrSums { float S, G; };
-template <bool HUBER, typename TJ>
-__device__ __forceinline__ QrSums qr_pairs(float th, float tau, float kappa, int N, TJ tj) {
-#pragma clang fp contract(off)
-  const float omt = 1.f - tau, hk = 0.5f * kappa, nk = -kappa;
-  double Sd = 0.0, Gd = 0.0;
-  for (int j0 = 0; j0 < N; j0 += kQrRun) {
-    const int j1 = j0 + kQrRun < N ? j0 + kQrRun : N;
-    float s = 0.f, g = 0.f;
-    for (int j = j0; j < j1; ++j) {
-      const float u = tj(j) - th;
-      const float c = u < 0.f ? omt : tau;
-      const float au = fabsf(u);
-      if (HUBER) {
-        const float h = au <= kappa ? 0.5f * (u * u) : kappa * (au - hk);
-        const float k = u < nk ? nk : (u > kappa ? kappa : u);
-        s = s + c * h;
-        g = g + c * k;
-      } else {
-        const float sg = u > 0.f ? 1.f : (u < 0.f ? -1.f : u);   // 0 and NaN stay
-        s = s + c * au;
-        g = g + c * sg;
-      }
-    }
-    Sd += (double)s;
-    Gd += (double)g;
-  }
-  float S = (float)Sd, G = (float)Gd;
-  if (HUBER) { S = S / kappa; G = G / kappa; }
-  return {S, G};
-}
+// (qr_pairs, the sums of one online quantile over the targets: dqn_rows.hpp)
 
 // one quantile's gradient into the row's dadv / dval
 template <bool DUELING>

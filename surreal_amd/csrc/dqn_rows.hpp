@@ -1,11 +1,12 @@
 // dqn_rows.hpp — per-row helpers shared by dqn_kernels.hip (scalar heads),
-// dqn_dist_kernels.hip (categorical heads) and dqn_quant_kernels.hip (quantile
-// heads): the action index, the staging of one row's A N head outputs in LDS,
+// dqn_dist_kernels.hip (categorical heads), dqn_quant_kernels.hip (quantile
+// heads) and dqn_iqn_kernels.hip (implicit quantile heads): the action index, the staging of one row's A N head outputs in LDS,
 // the wave-scope LDS ordering and lane broadcast, the dueling mean over the
 // actions, and the host rules both distributional launchers follow (the
 // staging form, the rows of a workgroup).  The statistics launch the two
 // distributional units share is launch_dqn_dist_stats (dqn_dist_kernels.hip).
 #pragma once
+#include <math.h>
 #include <stdint.h>
 #include <hip/hip_runtime.h>
 
@@ -83,6 +84,43 @@ __device__ __forceinline__ float dqn_col_mean(const float* __restrict__ slab, in
   float s = slab[i];
   for (int a = 1; a < A; ++a) s = s + slab[a * N + i];
   return s / (float)A;
+}
+
+// the quantile pair loss of dqn_quant_kernels.hip and dqn_iqn_kernels.hip (the
+// specification: the former's header): one online quantile's sums over the N
+// targets, j ascending; tj(j) is T_j in every lane (a readlane or an LDS
+// broadcast); tau is the online quantile's fraction
+constexpr int kQrRun = 8;                        // targets summed in fp32 before the fp64 add
+struct QrSums { float S, G; };
+template <bool HUBER, typename TJ>
+__device__ __forceinline__ QrSums qr_pairs(float th, float tau, float kappa, int N, TJ tj) {
+#pragma clang fp contract(off)
+  const float omt = 1.f - tau, hk = 0.5f * kappa, nk = -kappa;
+  double Sd = 0.0, Gd = 0.0;
+  for (int j0 = 0; j0 < N; j0 += kQrRun) {
+    const int j1 = j0 + kQrRun < N ? j0 + kQrRun : N;
+    float s = 0.f, g = 0.f;
+    for (int j = j0; j < j1; ++j) {
+      const float u = tj(j) - th;
+      const float c = u < 0.f ? omt : tau;
+      const float au = fabsf(u);
+      if (HUBER) {
+        const float h = au <= kappa ? 0.5f * (u * u) : kappa * (au - hk);
+        const float k = u < nk ? nk : (u > kappa ? kappa : u);
+        s = s + c * h;
+        g = g + c * k;
+      } else {
+        const float sg = u > 0.f ? 1.f : (u < 0.f ? -1.f : u);   // 0 and NaN stay
+        s = s + c * au;
+        g = g + c * sg;
+      }
+    }
+    Sd += (double)s;
+    Gd += (double)g;
+  }
+  float S = (float)Sd, G = (float)Gd;
+  if (HUBER) { S = S / kappa; G = G / kappa; }
+  return {S, G};
 }
 
 // ------------------------------------------------------------------- host

@@ -108,6 +108,29 @@ int launch_qr_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn,
 int launch_qr_q(const float* adv, int64_t lda, const float* val, int64_t ldv, int64_t rows, int A,
                 int N, int dueling, float* q, int64_t ldq, int32_t* greedy, hipStream_t st);
 int64_t qr_partials_bytes(int64_t B);
+// ---- dqn_iqn_kernels.hip (implicit quantile heads; shape and leading-dimension
+// checks are the launchers' own: SMI_E_ARG with a message, nothing launched)
+int launch_iqn_taus(uint64_t seed, const int32_t* step, int stream_id, int64_t row0, int64_t rows,
+                    int N, float* tau, hipStream_t st);
+int launch_iqn_embed_fwd(const float* tau, const float* H1, int64_t ldh, int64_t B, int N,
+                         const float* W, const float* bias, int n_cos, int d, float* Z,
+                         int64_t ldz, float* phi, int64_t ldp, hipStream_t st);
+int launch_iqn_embed_bwd(const float* dZ, int64_t ldz, const float* tau, const float* H1,
+                         int64_t ldh, const float* phi, int64_t ldp, int64_t B, int N, float* dW,
+                         float* db, int n_cos, int d, float* dH1, int64_t lddh, float* scratch,
+                         int64_t scratch_bytes, hipStream_t st);
+int64_t iqn_embed_scratch_bytes(int64_t B, int N, int n_cos, int d);
+int launch_iqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn,
+                  const float* adv_t, int64_t ldt, const float* val, const float* val_n,
+                  const float* val_t, const float* tau, const float* actions, int64_t as,
+                  const float* rewards, int64_t rs, const float* dones, int64_t ds, const float* w,
+                  int64_t B, int64_t B_global, int64_t row0, int A, int N, int Nt, float kappa,
+                  float gamma, int dueling, int double_q, float* dadv, int64_t ldd, float* dval,
+                  float* td_all, float* t_out, int32_t* astar_out, double* partials,
+                  int64_t partials_bytes, float* stats, hipStream_t st);
+int launch_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int A, int K,
+                 int dueling, float* q, int64_t ldq, int32_t* greedy, hipStream_t st);
+int64_t iqn_partials_bytes(int64_t B);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
 // skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
 // rows: the uint8 images come through the learners' time-major row map

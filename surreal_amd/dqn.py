@@ -97,6 +97,28 @@ pinball loss) summed over the online quantiles of the action taken and
 averaged over the target quantiles r + gamma (1 - d) theta_target(s')[a*, .],
 and `td_error` holds it (>= 0).  dp, the exchange image, graph replay and
 checkpoints are the categorical head's: nothing in them knows the head.
+
+Implicit quantile heads (algo.distributional.kind = 'implicit'; IQN, Dabney et
+al. 2018b; this build's own specification, dqn_iqn_kernels.hip): the net takes
+a quantile fraction tau per sample, so heads stay scalar (A and 1 outputs) and
+one new pair fc_tau_layer.{weight [d][embed_dim], bias [d]}, d = S h1, sits at
+the END of the flat buffer and of the state_dict (every other offset is the
+scalar model's).  A forward is: the first layer (after the conv stem, if any)
+to H1 [B][d]; smi_iqn_embed_forward, Z [B N][d] = H1[b] (.) relu(bias + cos(pi
+i tau) W^T) for the N fractions of each row; the deeper layers on the B N
+sample rows, so adv is [B N][A] and val [B N][1] (sample major).  learn()
+draws three sets of fractions (smi_iqn_taus, streams 0 online / 1 selecting /
+2 target, counter = the device Adam step, so a graph replay draws new ones and
+a dp rank draws the global draw's fractions of its rows), runs the three
+forwards (atoms online samples, target_atoms for the other two), smi_iqn_td
+(smi_iqn_td_shard under dp), the usual backward on the B N rows down to dZ
+(the layer above masks by Z > 0, which leaves every gradient unchanged),
+smi_iqn_embed_backward (dH1 and fc_tau_layer's gradients, written at their
+offsets of the gradient image), the first layer's weight gradient (and the
+conv backward) from dH1, and the one smi_adam_clip.  The fractions used stay
+readable as learner.tau / tau_next / tau_target.  forward() and the agents
+draw act_atoms fractions per row from a counter of their own and take the
+mean over them (smi_iqn_q).  v_min / v_max are not read.
 """
 import numpy as np
 import torch
@@ -264,11 +286,36 @@ def check_quantiles(A, quantiles, kappa, kind='quantile'):
     return quantiles, kappa
 
 
+IQN_MAX_SAMPLES = 64      # one lane per sample (dqn_iqn_kernels.hip: kIqnMaxN)
+IQN_MAX_SLAB = 4096       # A * samples (kIqnMaxSlab)
+IQN_MAX_COS = 64          # cosines of the embedding (kIqnMaxCos)
+
+
+def check_implicit(A, atoms=8, target_atoms=None, act_atoms=32, embed_dim=64, kappa=1.0):
+    """the ranges smi_iqn_* serve, as the dict FFQfunc(implicit=...) takes"""
+    out = {'atoms': int(atoms), 'target_atoms': int(atoms if target_atoms is None else target_atoms),
+           'act_atoms': int(act_atoms), 'embed_dim': int(embed_dim), 'kappa': float(kappa)}
+    for k in ('atoms', 'target_atoms', 'act_atoms'):
+        if not 1 <= out[k] <= IQN_MAX_SAMPLES:
+            raise ConfigError('DQN algo.distributional.{} must be in [1, {}], got {}'.format(
+                k, IQN_MAX_SAMPLES, out[k]))
+    if not 4 <= out['embed_dim'] <= IQN_MAX_COS or out['embed_dim'] % 4:
+        raise ConfigError('DQN algo.distributional.embed_dim must be a multiple of 4 in [4, {}], '
+                          'got {}'.format(IQN_MAX_COS, out['embed_dim']))
+    most = max(out['atoms'], out['target_atoms'], out['act_atoms'])
+    if A * most > IQN_MAX_SLAB:
+        raise ConfigError('DQN algo.distributional: {} actions x {} samples is over the kernel\'s '
+                          '{} values per row'.format(A, most, IQN_MAX_SLAB))
+    if not out['kappa'] >= 0.0:
+        raise ConfigError('DQN algo.distributional.kappa must be >= 0, got {}'.format(out['kappa']))
+    return out
+
+
 def dqn_model_kwargs(learner_config, env_config):
     """(D, A, hidden, dueling, FFQfunc keyword arguments): dqn_conv_specs for a
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
-    atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead.
-    Host only."""
+    atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
+    with kind 'implicit' the dict of check_implicit.  Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -278,7 +325,11 @@ def dqn_model_kwargs(learner_config, env_config):
         kw = {}
     dist = learner_config['algo'].get('distributional') or {}
     kind = dist.get('kind', 'categorical')
-    if dist.get('enabled', False) and kind != 'categorical':
+    if dist.get('enabled', False) and kind == 'implicit':
+        kw['implicit'] = check_implicit(A, dist.get('atoms', 8), dist.get('target_atoms'),
+                                        dist.get('act_atoms', 32), dist.get('embed_dim', 64),
+                                        dist.get('kappa', 1.0))
+    elif dist.get('enabled', False) and kind != 'categorical':
         kw['quantiles'], kw['kappa'] = check_quantiles(A, dist.get('atoms', 51),
                                                        dist.get('kappa', 1.0), kind)
     elif dist.get('enabled', False):
@@ -292,7 +343,7 @@ def ffq_param_names(n_convs, n_hidden, dueling):
     names = [f'conv_layers.{i}.{p}' for i in range(n_convs) for p in ('weight', 'bias')]
     for stream in ('fc_action_layers', 'fc_state_layers')[:2 if dueling else 1]:
         names += [f'{stream}.{i}.{p}' for i in range(n_hidden + 1) for p in ('weight', 'bias')]
-    return names
+    return names            # (an implicit model appends fc_tau_layer.{weight, bias})
 
 
 class _ConvAt(_LinearView):
@@ -314,16 +365,23 @@ class FFQfunc(nn.Module):
     atoms (categorical heads over the support [v_min, v_max]) the action
     stream ends in A * atoms logits and the state stream in atoms; with
     quantiles (quantile heads with Huber threshold kappa; not together with
-    atoms) in A * quantiles values and quantiles."""
+    atoms) in A * quantiles values and quantiles.  With implicit (the dict of
+    check_implicit; not together with either) the heads stay scalar and
+    fc_tau_layer embeds a quantile fraction per sample row (module docstring)."""
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
                  convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
-                 quantiles=None, kappa=1.0):
+                 quantiles=None, kappa=1.0, implicit=None):
         super().__init__()
         self.atoms, self.v_min, self.v_max = None, None, None
         self.quantiles, self.kappa = None, None
-        if atoms is not None and quantiles is not None:
-            raise ConfigError('FFQfunc takes atoms (categorical heads) or quantiles, not both')
+        self.implicit = None
+        if (atoms is not None) + (quantiles is not None) + (implicit is not None) > 1:
+            raise ConfigError('FFQfunc takes atoms (categorical heads), quantiles or implicit, '
+                              'not two of them')
+        if implicit is not None:
+            self.implicit = check_implicit(int(action_dim), **dict(implicit))
+            self.kappa = self.implicit['kappa']
         if atoms is not None:
             self.atoms, self.v_min, self.v_max = check_atoms(int(action_dim), atoms, v_min, v_max)
         if quantiles is not None:
@@ -353,7 +411,9 @@ class FFQfunc(nn.Module):
             out * hs[-1] + out                                              # noqa: E731
         fc0 = sum(co * ci * k * k + co for ci, _, _, co, k, _, _ in self.conv_geoms)
         n = fc0 + S * h1 * D + S * h1 + deep(A * N) + (deep(N) if dueling else 0)
-        flat = torch.zeros(n, dtype=torch.float32, device=self.device)
+        n_cos = self.implicit['embed_dim'] if self.implicit else 0
+        n_tau = S * h1 * n_cos + S * h1 if self.implicit else 0       # fc_tau_layer, at the end
+        flat = torch.zeros(n + n_tau, dtype=torch.float32, device=self.device)
         self.__dict__['flat'] = flat
         if self.convs:
             off, cl = 0, []
@@ -386,6 +446,11 @@ class FFQfunc(nn.Module):
             self.fc_state_layers = nn.ModuleList(streams[1])
             for lin in self.fc_state_layers:
                 lin.reset_parameters(generator)
+        if self.implicit:
+            self.fc_tau_layer = _LinearView(flat, n, n_cos, S * h1)
+            self.fc_tau_layer.reset_parameters(generator)
+            # the counter of forward()'s own fraction draws
+            self.__dict__['tau_step'] = torch.zeros(1, dtype=torch.int32, device=self.device)
 
     def streams(self):
         return [self.fc_action_layers] + ([self.fc_state_layers] if self.dueling else [])
@@ -403,21 +468,30 @@ class FFQfunc(nn.Module):
         c = FFQfunc(D, A, hs, self.dueling, self.device, convs=self.convs,
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
                     v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
-                    kappa=self.kappa if self.quantiles else 1.0)
+                    kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit)
         c.copy_from(self)
         return c
 
-    def logits(self, x):
+    def logits(self, x, tau=None):
         """the raw streams (adv [rows][A * atoms] action major, val [rows][atoms]
-        | None); for scalar heads (adv [rows][A], val [rows][1] | None)"""
+        | None); for scalar heads (adv [rows][A], val [rows][1] | None); for an
+        implicit model at the fractions tau (float32 device [rows * N], row
+        major): (adv [rows * N][A], val [rows * N][1] | None)"""
         x = x.contiguous() if self.convs else (x if x.stride(-1) == 1 else x.contiguous())
-        return _QNet(self, {}).fwd(x, x.shape[0], 'f')
+        return _QNet(self, {}).fwd(x, x.shape[0], 'f', tau)
 
     def forward(self, x):
         """q values [rows][A] (q_net.py:41-65,112-119) of a float32 device matrix
         (with convs: of a uint8 or float32 (rows, C, H, W) device tensor); with
         atoms the expected values of the categorical heads (smi_dqn_c51_q), with
-        quantiles their means (smi_dqn_qr_q)"""
+        quantiles their means (smi_dqn_qr_q), with implicit the means over
+        act_atoms sampled fractions (smi_iqn_q)"""
+        if self.implicit:      # the mean over act_atoms fractions per row, drawn here
+            net, rows = _QNet(self, {}), x.shape[0]
+            tau = net.taus(0, self.tau_step, 0, 0, rows, self.implicit['act_atoms'], 'f_tau')
+            self.tau_step.add_(1)
+            adv, val = self.logits(x, tau)
+            return net.expected_q(adv, val, rows, 'f')
         adv, val = self.logits(x)
         if self.atoms or self.quantiles:
             return _QNet(self, {}).expected_q(adv, val, adv.shape[0], 'f')
@@ -484,6 +558,10 @@ class _QNet(LaunchNet):
         m = self.m
         A = m.dims[2]
         q = self.buf(pre + '_q', (rows, A))
+        if m.implicit:
+            L.call('smi_iqn_q', p(adv), adv.stride(0), p(val), rows, A, adv.shape[0] // rows,
+                   int(m.dueling), p(q), A, p(greedy), self.st)
+            return q
         if m.quantiles:
             L.call('smi_dqn_qr_q', p(adv), adv.stride(0), p(val), m.quantiles, rows, A, m.quantiles,
                    int(m.dueling), p(q), A, p(greedy), self.st)
@@ -492,10 +570,19 @@ class _QNet(LaunchNet):
                m.v_max, int(m.dueling), p(q), A, p(greedy), self.st)
         return q
 
-    def fwd(self, x, rows, pre):
+    def taus(self, seed, step, stream_id, row0, rows, N, name):
+        """rows * N quantile fractions of an implicit model (smi_iqn_taus)"""
+        tau = self.buf(name, (rows * N,))
+        L.call('smi_iqn_taus', int(seed), p(step), stream_id, row0, rows, N, p(tau), self.st)
+        return tau
+
+    def fwd(self, x, rows, pre, tau=None, keep_phi=False):
         """(ADV [rows][A], VAL [rows][1] | None), with atoms (ADV [rows][A * atoms],
         VAL [rows][atoms] | None); the hidden activations stay in
-        the buffers pre_h1 ([rows][S h1], both streams) and pre_h{k}_{s}"""
+        the buffers pre_h1 ([rows][S h1], both streams) and pre_h{k}_{s}.  An
+        implicit model takes tau [rows * N]: H1 is embedded into pre_z [rows *
+        N][S h1] (phi into pre_phi with keep_phi, for bwd) and every later
+        layer, ADV and VAL have rows * N sample rows"""
         m = self.m
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
@@ -504,6 +591,18 @@ class _QNet(LaunchNet):
         self.check_rows(x, rows, D, 'q_func')
         H1 = self.buf(pre + '_h1', (rows, S * hs[0]))
         self.lin(x, x.stride(0), rows, D, m.w1, D, m.b1, S * hs[0], RELU, H1, S * hs[0])
+        if m.implicit:
+            if (tau is None or tau.dtype != torch.float32 or tau.dim() != 1 or not tau.is_contiguous()
+                    or tau.numel() % rows or not 1 <= tau.numel() // rows <= IQN_MAX_SAMPLES):
+                raise ValueError(f'q_func: an implicit model takes float32 fractions [{rows} * N], '
+                                 f'1 <= N <= {IQN_MAX_SAMPLES}')
+            N, d, tl = tau.numel() // rows, S * hs[0], m.fc_tau_layer
+            Z = self.buf(pre + '_z', (rows * N, d))
+            phi = self.buf(pre + '_phi', (rows * N, d)) if keep_phi else None
+            L.call('smi_iqn_embed_forward', p(tau), p(H1), d, rows, N, p(tl.weight), p(tl.bias),
+                   m.implicit['embed_dim'], d, p(Z), d, p(phi), d, self.st)
+            self.bufs[pre + '_tau'] = tau
+            H1, rows = Z, rows * N
         outs = []
         for s, layers in enumerate(m.streams()):
             prev, ld = H1[:, s * hs[0]:], S * hs[0]
@@ -533,6 +632,11 @@ class _QNet(LaunchNet):
             x = self.bufs[f'{pre}_c{len(m.convs) - 1}'].view(rows, -1)
         H1 = self.bufs[pre + '_h1']
         dH1 = self.buf(pre + '_dh1', (rows, S * hs[0]))
+        B, hid, dhid = rows, H1, dH1
+        if m.implicit:           # the streams run on the sample rows, from Z down to dZ
+            H1 = self.bufs[pre + '_z']
+            rows = H1.shape[0]
+            dH1 = self.buf(pre + '_dz', (rows, S * hs[0]))
         for s, layers in enumerate(m.streams()):
             acts = [(H1[:, s * hs[0]:], S * hs[0])] + \
                 [(self.bufs[f'{pre}_h{k + 1}_{s}'], hs[k]) for k in range(1, len(hs))]
@@ -549,6 +653,15 @@ class _QNet(LaunchNet):
                 L.call('smi_linear_backward_input', p(dy), ldg, rows, n_out, p(lin.weight),
                        hs[k - 1], hs[k - 1], p(xk), ldx, p(dx), lddx, st)
                 dy, ldg = dx, lddx
+        if m.implicit:
+            tau, phi, tl, d = self.bufs[pre + '_tau'], self.bufs[pre + '_phi'], m.fc_tau_layer, S * hs[0]
+            n_cos, N = m.implicit['embed_dim'], rows // B
+            need = int(L.lib().smi_iqn_embed_scratch_bytes(B, N, n_cos, d))
+            scratch = self.buf('iqn_scratch', (max(need // 4, 1),))
+            L.call('smi_iqn_embed_backward', p(dH1), d, p(tau), p(hid), d, p(phi), d, B, N,
+                   p(g[m.off(tl.weight):]), p(g[m.off(tl.bias):]), n_cos, d, p(dhid), d, p(scratch),
+                   need, st)
+            rows, dH1 = B, dhid
         # both streams' first layers: one weight-gradient GEMM over dH1 [rows][S h1]
         L.call('smi_linear_backward_weight', p(dH1), S * hs[0], rows, S * hs[0], p(x), x.stride(0),
                D, p(g[m.off(m.w1):]), D, p(g[m.off(m.b1):]), 0, st)
@@ -616,6 +729,9 @@ class DQNLearner(DeviceLearner):
         self.q_func = FFQfunc(D, A, hidden, dueling, self.device, gen, **conv_kw)
         self.pixel = 'convs' in conv_kw
         self.atoms, self.quantiles = self.q_func.atoms, self.q_func.quantiles
+        self.implicit = self.q_func.implicit
+        self._tau_seed = int(seed)
+        self.tau = self.tau_next = self.tau_target = None     # the fractions of the last learn()
         self.q_target = self.q_func.clone()                   # dqn.py:17
         self.dp = self._dp_group(dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
@@ -689,22 +805,36 @@ class DQNLearner(DeviceLearner):
         st = L.stream(self.device)
         dueling = self.q_func.dueling
         net, tnet = _QNet(self.q_func, self._bufs), _QNet(self.q_target, self._bufs)
-        adv_t, val_t = tnet.fwd(obs_next, B, 't')
-        adv, val = net.fwd(obs, B, 'q')
+        if self.implicit:
+            # the whole draw's fractions of this learner's rows: streams 0 online,
+            # 1 selecting, 2 target, counted by the device Adam step
+            q, row0 = self.implicit, (self.dp.rank * B if self.dp is not None else 0)
+            draw = lambda sid, n, name: net.taus(self._tau_seed, self.opt['step'], sid, row0, B,   # noqa: E731
+                                                 n, name)
+            self.tau = draw(0, q['atoms'], 'tau')
+            self.tau_next = draw(1, q['target_atoms'], 'tau_next') if self.double_q else None
+            self.tau_target = draw(2, q['target_atoms'], 'tau_target')
+        adv_t, val_t = tnet.fwd(obs_next, B, 't', self.tau_target)
+        adv, val = net.fwd(obs, B, 'q', self.tau, keep_phi=True)
         adv_n = val_n = None
         if self.double_q:
-            adv_n, val_n = net.fwd(obs_next, B, 'n')
+            adv_n, val_n = net.fwd(obs_next, B, 'n', self.tau_next)
         N = self.atoms or self.quantiles or 1
-        dadv = net.buf('dadv', (B, A * N))
-        dval = net.buf('dval', (B, N)) if dueling else None
+        if self.implicit:                        # sample rows, scalar heads
+            dadv = net.buf('dadv', (B * self.implicit['atoms'], A))
+            dval = net.buf('dval', (B * self.implicit['atoms'], 1)) if dueling else None
+        else:
+            dadv = net.buf('dadv', (B, A * N))
+            dval = net.buf('dval', (B, N)) if dueling else None
         if self.dp is not None and (self._xbuf is None
                                     or self.td_error.numel() != B * self.dp.world_size):
             # what the one all-reduce per learn() carries: [gradient | pad |
             # td_all (B_global) | stats (2)], the three as views of it
             self._xbuf, self.opt['g'], (self.td_error, self.stats_buf) = exchange_image(
                 self.device, self.q_func.flat.numel(), (B * self.dp.world_size, 2))
-        if self.atoms or self.quantiles:
-            (self._gradient_c51 if self.atoms else self._gradient_qr)(
+        if self.atoms or self.quantiles or self.implicit:
+            (self._gradient_c51 if self.atoms else self._gradient_qr if self.quantiles
+             else self._gradient_iqn)(
                 net, B, (adv, adv_n, adv_t), (val, val_n, val_t), (act, a_s), (rew, r_s), (don, d_s),
                 weights, dadv, dval)
         elif self.dp is None:
@@ -758,6 +888,25 @@ class DQNLearner(DeviceLearner):
                    p(self.stats_buf), net.st)
         else:
             L.call('smi_dqn_qr_td_shard', *args, B * self.dp.world_size, self.dp.rank * B, *tail,
+                   p(self.td_error), None, None, p(part), need, p(self.stats_buf), net.st)
+
+    def _gradient_iqn(self, net, B, advs, vals, act, rew, don, weights, dadv, dval):
+        """_gradient's TD step for implicit quantile heads: smi_iqn_td and the
+        statistics launch, or the shard form into the exchange image's views"""
+        A, q = self.action_dim, self.implicit
+        (adv, adv_n, adv_t), (val, val_n, val_t) = advs, vals
+        need = int(L.lib().smi_iqn_partials_bytes(B))
+        part = net.buf('iqn_partials', (need // 8,), torch.float64)
+        args = [p(adv), A, p(adv_n), A, p(adv_t), A, p(val), p(val_n), p(val_t), p(self.tau),
+                p(act[0]), act[1], p(rew[0]), rew[1], p(don[0]), don[1], p(weights), B]
+        tail = [A, q['atoms'], q['target_atoms'], q['kappa'], float(self.algo.gamma),
+                int(self.q_func.dueling), int(self.double_q), p(dadv), A, p(dval)]
+        if self.dp is None:
+            self.td_error = net.buf('td', (B,))
+            L.call('smi_iqn_td', *args, *tail, p(self.td_error), None, None, p(part), need,
+                   p(self.stats_buf), net.st)
+        else:
+            L.call('smi_iqn_td_shard', *args, B * self.dp.world_size, self.dp.rank * B, *tail,
                    p(self.td_error), None, None, p(part), need, p(self.stats_buf), net.st)
 
     # ------------------------------------------------------- reference API

@@ -36,8 +36,16 @@ pairs as u [B][N][N], torch.where for the Huber branches, autograd to the head
 outputs), and learn() with algo.distributional.kind = 'quantile' next to the
 scalar learner's.
 
+--implicit [--atoms N] (1 <= N <= 64, default 8) times the implicit quantile
+head (IQN) at B = 512, N = N' samples, d = 256 and 64 cosines: one
+smi_iqn_embed_forward and one smi_iqn_embed_backward call with the bytes per
+second of what each must read and write once, one smi_iqn_td call at A in
+{6, 18}, and learn() with algo.distributional.kind = 'implicit', eager and as
+a graph replay.
+
 Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
-                                 [--pixel | --gpus N | --atoms N | --quantiles N [--kappa K]]
+                                 [--pixel | --gpus N | --atoms N | --quantiles N [--kappa K]
+                                  | --implicit [--atoms N]]
 """
 import argparse
 import copy
@@ -336,6 +344,72 @@ def dist_main(args):
                               'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
 
 
+def implicit_main(args):
+    """--implicit [--atoms N]: the implicit quantile (IQN) kernels at B = 512, N = N' samples,
+    d = 256, 64 cosines (bytes: what each launch must read and write once), and learn()"""
+    N, B, D, d, n_cos, gamma = args.atoms or 8, 512, 17, 256, 64, 0.99
+    p, st, M = L.ptr, L.stream(), 512 * (args.atoms or 8)
+    g = torch.Generator().manual_seed(N)
+    tau = torch.rand(M, generator=g).cuda()
+    H1, W, bias = torch.rand(B, d, generator=g).cuda(), (torch.randn(d, n_cos, generator=g) / 8).cuda(), \
+        torch.zeros(d).cuda()
+    Z, phi, dZ, dH1 = torch.zeros(M, d).cuda(), torch.zeros(M, d).cuda(), torch.randn(M, d, generator=g).cuda(), \
+        torch.zeros(B, d).cuda()
+    dW, db = torch.zeros(d, n_cos).cuda(), torch.zeros(d).cuda()
+    need = int(L.lib().smi_iqn_embed_scratch_bytes(B, N, n_cos, d))
+    scratch = torch.zeros(max(need // 4, 1)).cuda()
+
+    def fwd():
+        for _ in range(args.calls):
+            L.call('smi_iqn_embed_forward', p(tau), p(H1), d, B, N, p(W), p(bias), n_cos, d, p(Z), d,
+                   p(phi), d, st)
+
+    def bwd():
+        for _ in range(args.calls):
+            L.call('smi_iqn_embed_backward', p(dZ), d, p(tau), p(H1), d, p(phi), d, B, N, p(dW), p(db),
+                   n_cos, d, p(dH1), d, p(scratch), need, st)
+    # forward: Z and phi out, H1 in; backward: dZ and phi in twice (dH1, dW), H1 in, dH1 out
+    for name, fn, nbytes in (('iqn_embed_forward', fwd, 4 * (2 * M * d + B * d)),
+                             ('iqn_embed_backward', bwd, 4 * (4 * M * d + 3 * B * d))):
+        med, q1, q3 = (1e3 * t / args.calls for t in timed(fn, args.iters, args.warmup))
+        print(json.dumps({'measurement': name, 'B': B, 'atoms': N, 'd': d, 'n_cos': n_cos,
+                          'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                          'q3_us': round(q3, 2), 'GB_per_s': round(nbytes / med / 1e3, 1),
+                          'calls_per_sample': args.calls, 'iters': args.iters}), flush=True)
+    for A in (6, 18):
+        adv, adv_n, adv_t = (torch.randn(M, A, generator=g).cuda() for _ in range(3))
+        val, val_n, val_t = (torch.randn(M, generator=g).cuda() for _ in range(3))
+        b = dqn_batch(B, D, A, 0)
+        act, rew, done, w = b['actions'], b['rewards'], b['dones'], b['weights']
+        dadv, dval, td, stats = torch.zeros(M, A).cuda(), torch.zeros(M).cuda(), torch.zeros(B).cuda(), \
+            torch.zeros(2).cuda()
+        pneed = int(L.lib().smi_iqn_partials_bytes(B))
+        part = torch.zeros(pneed // 8, dtype=torch.float64).cuda()
+
+        def td_call():
+            for _ in range(args.calls):
+                L.call('smi_iqn_td', p(adv), A, p(adv_n), A, p(adv_t), A, p(val), p(val_n), p(val_t),
+                       p(tau), p(act), 1, p(rew), 1, p(done), 1, p(w), B, A, N, N, args.kappa, gamma, 1, 1,
+                       p(dadv), A, p(dval), p(td), None, None, p(part), pneed, p(stats), st)
+        med, q1, q3 = (1e3 * t / args.calls for t in timed(td_call, args.iters, args.warmup))
+        print(json.dumps({'measurement': 'iqn_td_and_stats', 'B': B, 'A': A, 'atoms': N,
+                          'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                          'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
+                          'iters': args.iters}), flush=True)
+    A = 6
+    b = dqn_batch(B, D, A, 0)
+    lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = B
+    lc.model.fc_hidden_sizes = [128, 128]
+    lc.algo.distributional.update(enabled=True, kind='implicit', atoms=N, kappa=args.kappa)
+    for graph in (False, True):
+        learner = DQNLearner(lc, discrete_env_config(D, A), seed=0, use_graph=graph)
+        med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
+        print(json.dumps({'measurement': 'dqn_learn_' + ('graph' if graph else 'eager'),
+                          'implicit_atoms': N, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                          'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
@@ -347,6 +421,8 @@ def main():
                     help='N: the categorical (C51) head with N atoms instead of scalar heads')
     ap.add_argument('--quantiles', type=int, default=0,
                     help='N: the quantile (QR-DQN) head with N quantiles instead of scalar heads')
+    ap.add_argument('--implicit', action='store_true',
+                    help='the implicit quantile (IQN) head; --atoms N is its sample count (8)')
     ap.add_argument('--kappa', type=float, default=1.0,
                     help='--quantiles: the Huber threshold (0: the pinball loss)')
     ap.add_argument('--calls', type=int, default=20,
@@ -354,6 +430,8 @@ def main():
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
+    if args.implicit:
+        return implicit_main(args)
     if args.atoms or args.quantiles:
         return dist_main(args)
     if args.pixel:
