@@ -1184,6 +1184,68 @@ int smi_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int
 /* bytes of smi_iqn_td's partials workspace for B rows (host only) */
 int64_t smi_iqn_partials_bytes(int64_t B);
 
+/* --------------------------------------------- noisy linear layers (NoisyNet) */
+/* Factorised-Gaussian noisy layers (Fortunato et al. 2018) of DQNLearner /
+ * FFQfunc / QAgentBatch.  A layer (in -> out) has w_mu, w_sig [out][ldw >= in],
+ * b_mu, b_sig [out] and the noise vectors f_in [in], f_out [out]; its weight is
+ * w_mu + w_sig (.) (f_out f_in^T) and its bias b_mu + b_sig (.) f_out, neither
+ * of which is ever written to memory.  The full specification (sum orders, the
+ * draw): csrc/noisy_kernels.hip.  fp32, deterministic (no atomics).
+ *
+ * The widths of up to SMI_NOISY_MAX_LAYERS layers are passed by value. */
+#define SMI_NOISY_MAX_LAYERS 8
+typedef struct smi_noisy_dims {
+  int32_t in_dim[SMI_NOISY_MAX_LAYERS];
+  int32_t out_dim[SMI_NOISY_MAX_LAYERS];
+} smi_noisy_dims;
+/* layer l of a gradient image: weight [out][in] at w_off[l], bias [out] at
+ * b_off[l] (floats from the base pointer) */
+typedef struct smi_noisy_table {
+  int64_t w_off[SMI_NOISY_MAX_LAYERS];
+  int64_t b_off[SMI_NOISY_MAX_LAYERS];
+  int32_t in_dim[SMI_NOISY_MAX_LAYERS];
+  int32_t out_dim[SMI_NOISY_MAX_LAYERS];
+} smi_noisy_table;
+/* smi_noisy_draw: the noise image of a net, per layer [f_in (in) | f_out (out)],
+ * layers concatenated.  Element e of layer l: (x0, x1) = words 0 and 1 of
+ * Philox4x32-10 keyed by seed with the counter {e, l, *step, stream_id};
+ * u = ((x >> 9) + 0.5) 2^-23 (smi_iqn_taus's rule), eps = sqrtf(-2 logf(u1))
+ * cospif(2 u2), f = copysignf(sqrtf(|eps|), eps).  f_image receives f, eps_image
+ * (may be NULL) eps.  step is a DEVICE int32 (a replayed graph draws new
+ * noise); a layer's slice depends on no other layer's widths and on no row
+ * offset, so every data-parallel rank draws the same noise.  SMI_E_ARG: NULL
+ * step or f_image, n_layers outside [1, 8], a width < 1, stream_id < 0. */
+int smi_noisy_draw(uint64_t seed, const int32_t* step, int stream_id, int n_layers,
+                   smi_noisy_dims dims, float* f_image, float* eps_image, void* stream);
+/* y[r][o] = act((b_mu[o] + sum_i x[r][i] w_mu[o][i]) + f_out[o] * (b_sig[o] +
+ * sum_i (x[r][i] f_in[i]) w_sig[o][i])), act 0 none / 1 ReLU / 2 tanh: one GEMM
+ * with two accumulator chains over one staged x tile.  Operands as
+ * smi_linear_forward (leading dimensions, unaligned bases; 16-byte loads where
+ * an operand allows); b_mu / b_sig may be NULL (read as 0).  SMI_E_ARG: NULL
+ * required pointer, rows / in_dim / out_dim < 1, a leading dimension below the
+ * width it strides, act outside 0..2. */
+int smi_noisy_forward(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                      const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                      const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                      int64_t ldy, void* stream);
+/* dx[r][i] = [relu_mask[r][i] > 0] * (sum_o dy[r][o] w_mu[o][i] + f_in[i] *
+ * sum_o (dy[r][o] f_out[o]) w_sig[o][i]); relu_mask (may be NULL) as in
+ * smi_linear_backward_input.  SMI_E_ARG as smi_noisy_forward. */
+int smi_noisy_backward_input(const float* dy, int64_t ldg, int rows, int out_dim,
+                             const float* w_mu, const float* w_sig, int64_t ldw, int in_dim,
+                             const float* f_in, const float* f_out, const float* relu_mask,
+                             int64_t ldm, float* dx, int64_t lddx, void* stream);
+/* The sigma gradients of every layer of a net from its mu gradients, one launch:
+ *   g_sig[w_off + o in + i] = g_mu[w_off + o in + i] * (f_out[o] * f_in[i])
+ *   g_sig[b_off + o]        = g_mu[b_off + o] * f_out[o]
+ * with g_mu read from g_mu_base and g_sig WRITTEN (every entry) at the same
+ * offsets of g_sig_base; f_image is smi_noisy_draw's image of the same layers.
+ * Call it after the mu weight gradients are complete (after the dW group's
+ * flush).  SMI_E_ARG: NULL pointer, n_layers outside [1, 8], a width < 1, an
+ * offset < 0. */
+int smi_noisy_sigma_grad(const float* g_mu_base, float* g_sig_base, const float* f_image,
+                         int n_layers, smi_noisy_table table, void* stream);
+
 /* ------------------------------------------------------ DDPG n-step target */
 /* Replaces the target of DDPGLearner._optimize (surreal/learner/ddpg.py:279-283):
  *   y = r + gamma_n * q_next * (1 - done); with twin critics y = min(y, y2). */

@@ -93,6 +93,42 @@ class RNNArgs(ctypes.Structure):
     ]
 
 
+NOISY_MAX_LAYERS = 8
+
+
+class NoisyDims(ctypes.Structure):
+    """struct smi_noisy_dims (include/surreal_mi.h), passed by value."""
+    _fields_ = [('in_dim', ctypes.c_int32 * NOISY_MAX_LAYERS),
+                ('out_dim', ctypes.c_int32 * NOISY_MAX_LAYERS)]
+
+
+class NoisyTable(ctypes.Structure):
+    """struct smi_noisy_table (include/surreal_mi.h), passed by value."""
+    _fields_ = [('w_off', c_i64 * NOISY_MAX_LAYERS), ('b_off', c_i64 * NOISY_MAX_LAYERS),
+                ('in_dim', ctypes.c_int32 * NOISY_MAX_LAYERS),
+                ('out_dim', ctypes.c_int32 * NOISY_MAX_LAYERS)]
+
+
+def noisy_dims(widths):
+    """(n_layers, NoisyDims) of [(in, out), ...]"""
+    if not 1 <= len(widths) <= NOISY_MAX_LAYERS:
+        raise ValueError(f'noisy layers: 1..{NOISY_MAX_LAYERS} layers, got {len(widths)}')
+    d = NoisyDims()
+    for i, (k, n) in enumerate(widths):
+        d.in_dim[i], d.out_dim[i] = int(k), int(n)
+    return len(widths), d
+
+
+def noisy_table(layers):
+    """(n_layers, NoisyTable) of [(w_off, b_off, in, out), ...]"""
+    if not 1 <= len(layers) <= NOISY_MAX_LAYERS:
+        raise ValueError(f'noisy layers: 1..{NOISY_MAX_LAYERS} layers, got {len(layers)}')
+    t = NoisyTable()
+    for i, (wo, bo, k, n) in enumerate(layers):
+        t.w_off[i], t.b_off[i], t.in_dim[i], t.out_dim[i] = int(wo), int(bo), int(k), int(n)
+    return len(layers), t
+
+
 RNN_PH_GAE, RNN_PH_PREP, RNN_PH_POLICY_FWD, RNN_PH_POLICY_BWD, RNN_PH_POLICY_APPLY, \
     RNN_PH_VALUE_GRAD, RNN_PH_VALUE_APPLY, RNN_PH_ZSTATS, RNN_PH_ZAPPLY, RNN_PH_POLICY_DECIDE = range(10)
 RNN_PSTAT = 16
@@ -203,6 +239,12 @@ _SIGS = {
                           c_i64, P, P, P, P, P, c_i64, P, P]),
     'smi_iqn_q': (c_int, [P, c_i64, P, c_i64, c_int, c_int, c_int, P, c_i64, P, P]),
     'smi_iqn_partials_bytes': (c_i64, [c_i64]),
+    'smi_noisy_draw': (c_int, [ctypes.c_uint64, P, c_int, c_int, NoisyDims, P, P, P]),
+    'smi_noisy_forward': (c_int, [P, c_i64, c_int, c_int, P, P, c_i64, P, P, P, P, c_int, c_int, P,
+                                  c_i64, P]),
+    'smi_noisy_backward_input': (c_int, [P, c_i64, c_int, c_int, P, P, c_i64, c_int, P, P, P, c_i64,
+                                         P, c_i64, P]),
+    'smi_noisy_sigma_grad': (c_int, [P, P, P, c_int, NoisyTable, P]),
     'smi_neg_mean_grad': (c_int, [P, c_i64, c_i64, P, P, P]),
     'smi_tanh_backward': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, P, c_i64, P]),
     'smi_copy_cols': (c_int, [P, c_i64, c_i64, c_int, P, c_i64, P]),

@@ -347,11 +347,18 @@ class QAgentBatch(object):
     kind 'quantile' smi_dqn_qr_q's (the first maximum of the mean quantiles); with
     kind 'implicit' each agent draws act_atoms quantile fractions (smi_iqn_taus
     on the batch's own counter; kept as `tau`) and smi_iqn_q's arg-max of the
-    mean over them decides."""
+    mean over them decides.  With model.noisy.enabled and agent_mode 'training'
+    every agent is greedy on the noisy net: one noise image per act()
+    (smi_noisy_draw on the batch's own counter; kept as `noise`), shared by
+    the batch's rows, and no draw from `random` is made; the eval modes act as
+    above on the mu parameters.  (A noise row per agent is out of scope: the
+    rows of one act() share the image.)"""
 
-    def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None):
+    def __init__(self, learner_config, env_config, n_agents, agent_mode='training', device=None,
+                 seed=0):
+        """seed: of the noise draws of a noisy model (give every actor process its own)"""
         from .config import ConfigError
-        from .dqn import FFQfunc, dqn_model_kwargs
+        from .dqn import NOISE_KEY, FFQfunc, dqn_model_kwargs
         lc, ec = as_config(learner_config), as_config(env_config)
         D, A, hidden, dueling, conv_kw = dqn_model_kwargs(lc, ec)
         ex = lc.algo.exploration
@@ -373,6 +380,9 @@ class QAgentBatch(object):
         self._greedy = torch.zeros(self.n, dtype=torch.int32, device=self.device)
         self.tau = None                 # implicit heads: the fractions of the last act()
         self._tau_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self.noise = None               # noisy layers, training mode: the image of the last act()
+        self._noise_step = torch.zeros(1, dtype=torch.int32, device=self.device)
+        self._noise_seed = int(seed) ^ NOISE_KEY
 
     def load_module_dict(self, module_dict):
         self.q_func.load_state_dict(module_dict['q_func'].state_dict())
@@ -410,13 +420,18 @@ class QAgentBatch(object):
         A = self.action_dim
         actions = np.zeros(self.n, dtype=np.int64)
         greedy = np.zeros(self.n, dtype=bool)
-        for i in range(self.n):                                         # q_agent.py:35-48
-            eps = self.eps(i)
-            self.T[i] += 1
-            if self.agent_mode == 'eval_deterministic' or random.random() > eps:
-                greedy[i] = True
-            else:
-                actions[i] = random.randrange(A)
+        noisy = bool(self.q_func.noisy) and self.agent_mode == 'training'
+        if noisy:                       # the noise explores: every agent is greedy on the noisy net
+            self.T += 1
+            greedy[:] = True
+        else:
+            for i in range(self.n):                                     # q_agent.py:35-48
+                eps = self.eps(i)
+                self.T[i] += 1
+                if self.agent_mode == 'eval_deterministic' or random.random() > eps:
+                    greedy[i] = True
+                else:
+                    actions[i] = random.randrange(A)
         if greedy.any():
             xd = torch.from_numpy(x).to(self.device)
             net = _QNet(self.q_func, self._bufs)
@@ -424,7 +439,11 @@ class QAgentBatch(object):
                 self.tau = net.taus(0, self._tau_step, 0, 0, self.n,
                                     self.q_func.implicit['act_atoms'], 'act_tau')
                 self._tau_step.add_(1)
-            adv, val = net.fwd(xd, self.n, 'act', self.tau)
+            self.noise = None
+            if noisy:
+                self.noise = net.draw(self._noise_seed, self._noise_step, 0, 'act_noise')
+                self._noise_step.add_(1)
+            adv, val = net.fwd(xd, self.n, 'act', self.tau, noise=self.noise)
             if self.q_func.atoms or self.q_func.quantiles or self.q_func.implicit:    # arg-max of the expected values
                 net.expected_q(adv, val, self.n, 'act', greedy=self._greedy)
             else:

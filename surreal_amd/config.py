@@ -181,6 +181,9 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
         'convs': [],
         'fc_hidden_sizes': [128, 128],
         'dueling': True,
+        # noisy linear layers (NoisyNet, factorised Gaussian noise) in place of
+        # every FC layer; sigma0 / sqrt(in_features) initialises every sigma entry
+        'noisy': {'enabled': False, 'sigma0': 0.5},
     },
     'algo': {
         'lr': 1e-3,

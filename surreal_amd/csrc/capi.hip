@@ -738,6 +738,34 @@ int smi_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int
 
 int64_t smi_iqn_partials_bytes(int64_t B) { return iqn_partials_bytes(B); }
 
+int smi_noisy_draw(uint64_t seed, const int32_t* step, int stream_id, int n_layers,
+                   smi_noisy_dims dims, float* f_image, float* eps_image, void* stream) {
+  return launch_noisy_draw(seed, step, stream_id, n_layers, dims, f_image, eps_image,
+                           SMI_STREAM(stream));
+}
+
+int smi_noisy_forward(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                      const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                      const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                      int64_t ldy, void* stream) {
+  return launch_noisy_fwd(x, ldx, rows, in_dim, w_mu, w_sig, ldw, b_mu, b_sig, f_in, f_out,
+                          out_dim, act, y, ldy, SMI_STREAM(stream));
+}
+
+int smi_noisy_backward_input(const float* dy, int64_t ldg, int rows, int out_dim,
+                             const float* w_mu, const float* w_sig, int64_t ldw, int in_dim,
+                             const float* f_in, const float* f_out, const float* relu_mask,
+                             int64_t ldm, float* dx, int64_t lddx, void* stream) {
+  return launch_noisy_bwd_dx(dy, ldg, rows, out_dim, w_mu, w_sig, ldw, in_dim, f_in, f_out,
+                             relu_mask, ldm, dx, lddx, SMI_STREAM(stream));
+}
+
+int smi_noisy_sigma_grad(const float* g_mu_base, float* g_sig_base, const float* f_image,
+                         int n_layers, smi_noisy_table table, void* stream) {
+  return launch_noisy_sigma_grad(g_mu_base, g_sig_base, f_image, n_layers, table,
+                                 SMI_STREAM(stream));
+}
+
 int smi_neg_mean_grad(const float* q, int64_t q_stride, int64_t n, float* dq, float* loss,
                       void* stream) {
   REQUIRE(q && dq && n > 0, "neg_mean_grad: bad args");

@@ -103,6 +103,7 @@
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "dqn_rows.hpp"
+#include "philox.hpp"
 
 namespace smi {
 
@@ -115,17 +116,7 @@ constexpr int kIqnDwRows = 256;                  // rows per range of the weight
 constexpr int kIqnDwMaxSplit = 64;
 
 // ------------------------------------------------------------------ fractions
-__device__ __forceinline__ uint32_t iqn_philox(uint32_t k0, uint32_t k1, uint32_t c0, uint32_t c1,
-                                               uint32_t c2, uint32_t c3) {
-  for (int r = 0; r < 10; ++r) {
-    const uint32_t h0 = __umulhi(0xD2511F53u, c0), l0 = 0xD2511F53u * c0;
-    const uint32_t h1 = __umulhi(0xCD9E8D57u, c2), l1 = 0xCD9E8D57u * c2;
-    c0 = h1 ^ c1 ^ k0; c1 = l1; c2 = h0 ^ c3 ^ k1; c3 = l0;
-    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-  }
-  return c0;
-}
-
+// (iqn_philox: philox.hpp, shared with noisy_kernels.hip)
 __global__ void __launch_bounds__(kWG)
 iqn_taus_kernel(uint64_t seed, const int32_t* __restrict__ step, uint32_t stream_id, int64_t row0,
                 int64_t count, int N, float* __restrict__ tau) {

@@ -131,6 +131,21 @@ int launch_iqn_td(const float* adv, int64_t lda, const float* adv_n, int64_t ldn
 int launch_iqn_q(const float* adv, int64_t lda, const float* val, int64_t rows, int A, int K,
                  int dueling, float* q, int64_t ldq, int32_t* greedy, hipStream_t st);
 int64_t iqn_partials_bytes(int64_t B);
+// ---- noisy_kernels.hip (noisy linear layers; every argument check is the
+// launchers' own: SMI_E_ARG with a message, nothing launched)
+int launch_noisy_draw(uint64_t seed, const int32_t* step, int stream_id, int n_layers,
+                      const smi_noisy_dims& dims, float* f_image, float* eps_image,
+                      hipStream_t st);
+int launch_noisy_fwd(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                     const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                     const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                     int64_t ldy, hipStream_t st);
+int launch_noisy_bwd_dx(const float* dy, int64_t ldg, int rows, int out_dim, const float* w_mu,
+                        const float* w_sig, int64_t ldw, int in_dim, const float* f_in,
+                        const float* f_out, const float* mask, int64_t ldm, float* dx,
+                        int64_t lddx, hipStream_t st);
+int launch_noisy_sigma_grad(const float* g_mu_base, float* g_sig_base, const float* f_image,
+                            int n_layers, const smi_noisy_table& tab, hipStream_t st);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
 // skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
 // rows: the uint8 images come through the learners' time-major row map

@@ -119,6 +119,19 @@ conv backward) from dH1, and the one smi_adam_clip.  The fractions used stay
 readable as learner.tau / tau_next / tau_target.  forward() and the agents
 draw act_atoms fractions per row from a counter of their own and take the
 mean over them (smi_iqn_q).  v_min / v_max are not read.
+
+Noisy linear layers (model.noisy.enabled; NoisyNet, factorised Gaussian noise,
+noisy_kernels.hip): every FC layer computes with W_mu + W_sig (.) (f_out f_in^T)
+and b_mu + b_sig (.) f_out without writing either; the sigma parameters are a
+second image of the FC range appended at the very end of the flat buffer
+(ffq_sigma_shift) and of the state_dict (ffq_sigma_names), so the target copy,
+the exchange image, Adam with its norm clip and the checkpoints cover them as
+part of the one buffer.  learn() draws three noise images per step from the
+device Adam step (smi_noisy_draw; streams 0 online at s, 1 online at s' with
+double-Q, 2 target; learner.noise, noise_next, noise_target; key = the seed XOR
+NOISE_KEY, apart from the implicit heads' fractions), the same on every
+data-parallel rank, and after the grouped mu weight gradients one
+smi_noisy_sigma_grad fills the sigma range of the gradient image.
 """
 import numpy as np
 import torch
@@ -311,11 +324,52 @@ def check_implicit(A, atoms=8, target_atoms=None, act_atoms=32, embed_dim=64, ka
     return out
 
 
+NOISE_KEY = 0x6E6F697379          # XORed into a seed for the noise draws ('noisy')
+
+
+def check_noisy(sigma0):
+    """model.noisy.sigma0 as a float: positive and finite"""
+    try:
+        sigma0 = float(sigma0)
+    except (TypeError, ValueError):
+        raise ConfigError('DQN model.noisy.sigma0 must be a number, got {!r}'.format(sigma0))
+    if not (sigma0 > 0.0 and np.isfinite(sigma0)):
+        raise ConfigError('DQN model.noisy.sigma0 must be positive and finite, got {}'.format(sigma0))
+    return sigma0
+
+
+def ffq_sigma_names(n_hidden, dueling):
+    """what a noisy model appends to the state_dict, after every other name: the
+    FC layers' sigma entries in the layer order of ffq_param_names"""
+    return [f'{stream}.{i}.{p}_sigma' for stream in ('fc_action_layers', 'fc_state_layers')[:2 if dueling else 1]
+            for i in range(n_hidden + 1) for p in ('weight', 'bias')]
+
+
+def ffq_sigma_shift(fc0, n, n_tau):
+    """a noisy model's flat buffer is [convs (fc0) | FC range [fc0, n) | fc_tau_layer
+    (n_tau) | the FC range's sigma image]: the FC parameter at offset o has its
+    sigma at o + this shift.  Host only."""
+    return n + n_tau - fc0
+
+
+def ffq_noisy_layers(D, hidden, dueling, out_widths):
+    """the noisy layers of a net in noise-image order, [(in, out)]: the stacked
+    first layer, then per stream its deeper layers; out_widths: the streams'
+    output widths.  Host only."""
+    S = 2 if dueling else 1
+    layers = [(D, S * hidden[0])]
+    for s in range(S):
+        layers += [(hidden[k - 1], hidden[k]) for k in range(1, len(hidden))]
+        layers.append((hidden[-1], out_widths[s]))
+    return layers
+
+
 def dqn_model_kwargs(learner_config, env_config):
     """(D, A, hidden, dueling, FFQfunc keyword arguments): dqn_conv_specs for a
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
     atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
-    with kind 'implicit' the dict of check_implicit.  Host only."""
+    with kind 'implicit' the dict of check_implicit; model.noisy.enabled adds
+    noisy = sigma0.  Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -335,6 +389,9 @@ def dqn_model_kwargs(learner_config, env_config):
     elif dist.get('enabled', False):
         kw['atoms'], kw['v_min'], kw['v_max'] = check_atoms(
             A, dist.get('atoms', 51), dist.get('v_min', -10.0), dist.get('v_max', 10.0))
+    noisy = learner_config['model'].get('noisy') or {}
+    if noisy.get('enabled', False):
+        kw['noisy'] = check_noisy(noisy.get('sigma0', 0.5))
     return D, A, hidden, dueling, kw
 
 
@@ -367,12 +424,21 @@ class FFQfunc(nn.Module):
     quantiles (quantile heads with Huber threshold kappa; not together with
     atoms) in A * quantiles values and quantiles.  With implicit (the dict of
     check_implicit; not together with either) the heads stay scalar and
-    fc_tau_layer embeds a quantile fraction per sample row (module docstring)."""
+    fc_tau_layer embeds a quantile fraction per sample row (module docstring).
+    With noisy (sigma0) every FC layer is a noisy linear layer (noisy_kernels.hip;
+    the stacked first layer is one layer of S h1 outputs, fc_tau_layer and the
+    convolutions stay plain): the sigma parameters are a second image of the FC
+    range at the end of the flat buffer (ffq_sigma_shift), every entry sigma0 /
+    sqrt(in_features), and the state_dict ends in ffq_sigma_names.  In train()
+    mode forward() / logits() draw one noise image per call from a counter of
+    the model's own (noise_step; the last image stays in `noise`); in eval()
+    mode they run the mu parameters through the plain layers."""
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
                  convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
-                 quantiles=None, kappa=1.0, implicit=None):
+                 quantiles=None, kappa=1.0, implicit=None, noisy=None):
         super().__init__()
+        self.noisy = None if noisy is None else check_noisy(noisy)
         self.atoms, self.v_min, self.v_max = None, None, None
         self.quantiles, self.kappa = None, None
         self.implicit = None
@@ -413,8 +479,10 @@ class FFQfunc(nn.Module):
         n = fc0 + S * h1 * D + S * h1 + deep(A * N) + (deep(N) if dueling else 0)
         n_cos = self.implicit['embed_dim'] if self.implicit else 0
         n_tau = S * h1 * n_cos + S * h1 if self.implicit else 0       # fc_tau_layer, at the end
-        flat = torch.zeros(n + n_tau, dtype=torch.float32, device=self.device)
+        n_sig = n - fc0 if self.noisy else 0                          # the sigma image, at the very end
+        flat = torch.zeros(n + n_tau + n_sig, dtype=torch.float32, device=self.device)
         self.__dict__['flat'] = flat
+        self.sig_shift = ffq_sigma_shift(fc0, n, n_tau)
         if self.convs:
             off, cl = 0, []
             for ci, _, _, co, k, _, _ in self.conv_geoms:
@@ -451,6 +519,48 @@ class FFQfunc(nn.Module):
             self.fc_tau_layer.reset_parameters(generator)
             # the counter of forward()'s own fraction draws
             self.__dict__['tau_step'] = torch.zeros(1, dtype=torch.int32, device=self.device)
+        if self.noisy:
+            self.noisy_layers = ffq_noisy_layers(D, hs, self.dueling, (A * N, N))
+            with torch.no_grad():
+                flat[fc0 + self.sig_shift:b1 + S * h1 + self.sig_shift] = self.noisy / D ** 0.5
+                for layers in self.streams():
+                    for lin in layers[1:]:
+                        for t in self.sigma_of(lin):
+                            t.fill_(self.noisy / lin.in_features ** 0.5)
+            # the counter of forward()'s own noise draws and the last image drawn
+            self.__dict__['noise_step'] = torch.zeros(1, dtype=torch.int32, device=self.device)
+            self.__dict__['noise'] = None
+            self.noise_seed = 0          # of forward()'s draws; set it per process
+
+    def sigma_of(self, lin):
+        """(weight_sigma, bias_sigma) views of an FC layer of a noisy model"""
+        w = self.flat[self.off(lin.weight) + self.sig_shift:][:lin.weight.numel()]
+        b = self.flat[self.off(lin.bias) + self.sig_shift:][:lin.bias.numel()]
+        return w.view(lin.weight.shape), b
+
+    def _sigma_items(self):
+        names = ffq_sigma_names(len(self.dims[1]), self.dueling)
+        views = [t for layers in self.streams() for lin in layers for t in self.sigma_of(lin)]
+        return list(zip(names, views))
+
+    def state_dict(self, *args, **kwargs):
+        sd = super().state_dict(*args, **kwargs)
+        if self.noisy:
+            keep, prefix = kwargs.get('keep_vars', False), kwargs.get('prefix', '')
+            for name, t in self._sigma_items():
+                sd[prefix + name] = t if keep else t.detach().clone()
+        return sd
+
+    def load_state_dict(self, state_dict, strict=True, **kwargs):
+        state_dict = dict(state_dict)
+        if self.noisy:
+            with torch.no_grad():
+                for name, t in self._sigma_items():
+                    if name in state_dict:
+                        t.copy_(torch.as_tensor(state_dict.pop(name)).to(self.device))
+                    elif strict:
+                        raise RuntimeError(f'FFQfunc.load_state_dict: missing {name!r}')
+        return super().load_state_dict(state_dict, strict=strict, **kwargs)
 
     def streams(self):
         return [self.fc_action_layers] + ([self.fc_state_layers] if self.dueling else [])
@@ -468,7 +578,8 @@ class FFQfunc(nn.Module):
         c = FFQfunc(D, A, hs, self.dueling, self.device, convs=self.convs,
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
                     v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
-                    kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit)
+                    kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit,
+                    noisy=self.noisy)
         c.copy_from(self)
         return c
 
@@ -478,7 +589,12 @@ class FFQfunc(nn.Module):
         implicit model at the fractions tau (float32 device [rows * N], row
         major): (adv [rows * N][A], val [rows * N][1] | None)"""
         x = x.contiguous() if self.convs else (x if x.stride(-1) == 1 else x.contiguous())
-        return _QNet(self, {}).fwd(x, x.shape[0], 'f', tau)
+        net, noise = _QNet(self, {}), None
+        if self.noisy and self.training:
+            noise = self.__dict__['noise'] = net.draw(self.noise_seed ^ NOISE_KEY, self.noise_step, 0,
+                                                      'f_noise')
+            self.noise_step.add_(1)
+        return net.fwd(x, x.shape[0], 'f', tau, noise=noise)
 
     def forward(self, x):
         """q values [rows][A] (q_net.py:41-65,112-119) of a float32 device matrix
@@ -526,7 +642,7 @@ class _QNet(LaunchNet):
             x = y
         return x.view(rows, -1)
 
-    def conv_bwd(self, x, rows, pre, dH1, g):
+    def conv_bwd(self, x, rows, pre, dH1, g, noise=None):
         """from dH1 (both streams' first-layer gradient) through the stem: the
         first FC layer's input gradient masked by the last conv activation, then
         per layer the weight gradient and (except layer 0) the input gradient"""
@@ -538,8 +654,7 @@ class _QNet(LaunchNet):
         need = max(int(L.lib().smi_conv2d_scratch_bytes(rows, *geo)) for geo in m.conv_geoms)
         scratch = self.buf('conv_scratch', ((need + 3) // 4,))
         dy = self.buf(f'{pre}_dc{n - 1}', tuple(acts[n].shape))
-        L.call('smi_linear_backward_input', p(dH1), S * hs[0], rows, S * hs[0], p(m.w1), D, D,
-               p(acts[n]), D, p(dy), D, self.st)
+        self.ndx(noise, 0, dH1, S * hs[0], rows, S * hs[0], m.w1, D, D, acts[n], D, dy, D)
         for i in range(n - 1, -1, -1):
             ci, H, W, co, k, s, pad = m.conv_geoms[i]
             conv, xi = m.conv_layers[i], acts[i]
@@ -570,19 +685,68 @@ class _QNet(LaunchNet):
                m.v_max, int(m.dueling), p(q), A, p(greedy), self.st)
         return q
 
+    def draw(self, seed, step, stream_id, name):
+        """the noise image of a noisy model's layers (smi_noisy_draw): per layer
+        [f_in | f_out]; the same on every data-parallel rank"""
+        nl, dims = L.noisy_dims(self.m.noisy_layers)
+        f = self.buf(name, (sum(k + n for k, n in self.m.noisy_layers),))
+        L.call('smi_noisy_draw', int(seed), p(step), stream_id, nl, dims, p(f), None, self.st)
+        return f
+
+    def _f(self, noise, li):
+        """(f_in, f_out) of noisy layer li in a noise image"""
+        lay = self.m.noisy_layers
+        o = sum(k + n for k, n in lay[:li])
+        return noise[o:], noise[o + lay[li][0]:]
+
+    def nlin(self, noise, li, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
+        """layer li's forward: LaunchNet.lin on the mu parameters without a
+        noise image, smi_noisy_forward with one"""
+        if noise is None:
+            return self.lin(x, ldx, rows, k, w, ldw, b, n, act, y, ldy)
+        sh = self.m.sig_shift
+        fi, fo = self._f(noise, li)
+        L.call('smi_noisy_forward', p(x), ldx, rows, k, p(w), p(self.m.flat[self.m.off(w) + sh:]),
+               ldw, p(b), p(self.m.flat[self.m.off(b) + sh:]), p(fi), p(fo), n, act, p(y), ldy,
+               self.st)
+
+    def ndx(self, noise, li, dy, ldg, rows, n_out, w, ldw, k, mask, ldm, dx, lddx):
+        """layer li's input gradient, plain or noisy as nlin"""
+        if noise is None:
+            return L.call('smi_linear_backward_input', p(dy), ldg, rows, n_out, p(w), ldw, k,
+                          p(mask), ldm, p(dx), lddx, self.st)
+        fi, fo = self._f(noise, li)
+        L.call('smi_noisy_backward_input', p(dy), ldg, rows, n_out, p(w),
+               p(self.m.flat[self.m.off(w) + self.m.sig_shift:]), ldw, k, p(fi), p(fo), p(mask), ldm,
+               p(dx), lddx, self.st)
+
+    def sigma_grad(self, g, noise):
+        """the sigma ranges of the gradient image g from its mu ranges, one launch
+        (after the weight-gradient group's flush)"""
+        m = self.m
+        D, hs, A = m.dims
+        S = 2 if m.dueling else 1
+        tab = [(m.off(m.w1), m.off(m.b1), D, S * hs[0])]
+        for layers in m.streams():
+            tab += [(m.off(lin.weight), m.off(lin.bias), lin.in_features, lin.out_features)
+                    for lin in layers[1:]]
+        nl, t = L.noisy_table(tab)
+        L.call('smi_noisy_sigma_grad', p(g), p(g[m.sig_shift:]), p(noise), nl, t, self.st)
+
     def taus(self, seed, step, stream_id, row0, rows, N, name):
         """rows * N quantile fractions of an implicit model (smi_iqn_taus)"""
         tau = self.buf(name, (rows * N,))
         L.call('smi_iqn_taus', int(seed), p(step), stream_id, row0, rows, N, p(tau), self.st)
         return tau
 
-    def fwd(self, x, rows, pre, tau=None, keep_phi=False):
+    def fwd(self, x, rows, pre, tau=None, keep_phi=False, noise=None):
         """(ADV [rows][A], VAL [rows][1] | None), with atoms (ADV [rows][A * atoms],
         VAL [rows][atoms] | None); the hidden activations stay in
         the buffers pre_h1 ([rows][S h1], both streams) and pre_h{k}_{s}.  An
         implicit model takes tau [rows * N]: H1 is embedded into pre_z [rows *
         N][S h1] (phi into pre_phi with keep_phi, for bwd) and every later
-        layer, ADV and VAL have rows * N sample rows"""
+        layer, ADV and VAL have rows * N sample rows.  noise: a noisy model's
+        noise image (draw); None runs the mu parameters through the plain layers"""
         m = self.m
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
@@ -590,7 +754,7 @@ class _QNet(LaunchNet):
             x = self.conv_fwd(x, rows, pre)
         self.check_rows(x, rows, D, 'q_func')
         H1 = self.buf(pre + '_h1', (rows, S * hs[0]))
-        self.lin(x, x.stride(0), rows, D, m.w1, D, m.b1, S * hs[0], RELU, H1, S * hs[0])
+        self.nlin(noise, 0, x, x.stride(0), rows, D, m.w1, D, m.b1, S * hs[0], RELU, H1, S * hs[0])
         if m.implicit:
             if (tau is None or tau.dtype != torch.float32 or tau.dim() != 1 or not tau.is_contiguous()
                     or tau.numel() % rows or not 1 <= tau.numel() // rows <= IQN_MAX_SAMPLES):
@@ -609,17 +773,18 @@ class _QNet(LaunchNet):
             for k in range(1, len(hs)):
                 H = self.buf(f'{pre}_h{k + 1}_{s}', (rows, hs[k]))
                 lin = layers[k]
-                self.lin(prev, ld, rows, hs[k - 1], lin.weight, hs[k - 1], lin.bias, hs[k], RELU,
-                         H, hs[k])
+                self.nlin(noise, s * len(hs) + k, prev, ld, rows, hs[k - 1], lin.weight, hs[k - 1],
+                          lin.bias, hs[k], RELU, H, hs[k])
                 prev, ld = H, hs[k]
             lin = layers[-1]
             n_out = lin.out_features
             out = self.buf(f'{pre}_out_{s}', (rows, n_out))
-            self.lin(prev, ld, rows, hs[-1], lin.weight, hs[-1], lin.bias, n_out, NONE, out, n_out)
+            self.nlin(noise, (s + 1) * len(hs), prev, ld, rows, hs[-1], lin.weight, hs[-1], lin.bias,
+                      n_out, NONE, out, n_out)
             outs.append(out)
         return outs[0], (outs[1] if m.dueling else None)
 
-    def bwd(self, x, rows, pre, douts, g):
+    def bwd(self, x, rows, pre, douts, g, noise=None):
         """from douts[s] = d loss / d (stream s's output) into the gradient image
         g (the flat layout); the weight-gradient calls queue into the caller's
         open group, so every dY / X buffer is written once and left alone"""
@@ -650,8 +815,8 @@ class _QNet(LaunchNet):
                 dx, lddx = grads[k - 1]
                 L.call('smi_linear_backward_weight', p(dy), ldg, rows, n_out, p(xk), ldx, hs[k - 1],
                        p(g[m.off(lin.weight):]), hs[k - 1], p(g[m.off(lin.bias):]), 0, st)
-                L.call('smi_linear_backward_input', p(dy), ldg, rows, n_out, p(lin.weight),
-                       hs[k - 1], hs[k - 1], p(xk), ldx, p(dx), lddx, st)
+                self.ndx(noise, s * len(hs) + k, dy, ldg, rows, n_out, lin.weight, hs[k - 1],
+                         hs[k - 1], xk, ldx, dx, lddx)
                 dy, ldg = dx, lddx
         if m.implicit:
             tau, phi, tl, d = self.bufs[pre + '_tau'], self.bufs[pre + '_phi'], m.fc_tau_layer, S * hs[0]
@@ -666,7 +831,7 @@ class _QNet(LaunchNet):
         L.call('smi_linear_backward_weight', p(dH1), S * hs[0], rows, S * hs[0], p(x), x.stride(0),
                D, p(g[m.off(m.w1):]), D, p(g[m.off(m.b1):]), 0, st)
         if m.convs:
-            self.conv_bwd(frames, rows, pre, dH1, g)
+            self.conv_bwd(frames, rows, pre, dH1, g, noise)
 
 
 class TargetUpdateTracker(object):
@@ -732,6 +897,11 @@ class DQNLearner(DeviceLearner):
         self.implicit = self.q_func.implicit
         self._tau_seed = int(seed)
         self.tau = self.tau_next = self.tau_target = None     # the fractions of the last learn()
+        self.noisy = self.q_func.noisy
+        # the noise draws take a key of their own: with the learner's seed they would share
+        # Philox blocks with the implicit heads' fractions (same step, streams 0 / 1 / 2)
+        self._noise_seed = int(seed) ^ NOISE_KEY
+        self.noise = self.noise_next = self.noise_target = None   # the noise images of the last learn()
         self.q_target = self.q_func.clone()                   # dqn.py:17
         self.dp = self._dp_group(dp, [self.q_func.flat, self.q_target.flat])
         self.opt = self.adam_state(self.q_func.flat, algo.lr)
@@ -814,11 +984,18 @@ class DQNLearner(DeviceLearner):
             self.tau = draw(0, q['atoms'], 'tau')
             self.tau_next = draw(1, q['target_atoms'], 'tau_next') if self.double_q else None
             self.tau_target = draw(2, q['target_atoms'], 'tau_target')
-        adv_t, val_t = tnet.fwd(obs_next, B, 't', self.tau_target)
-        adv, val = net.fwd(obs, B, 'q', self.tau, keep_phi=True)
+        if self.noisy:
+            # one noise image per forward, the same on every rank: streams 0 online
+            # at s, 1 online at s' (double-Q), 2 target, counted by the device Adam step
+            ndraw = lambda sid, name: net.draw(self._noise_seed, self.opt['step'], sid, name)   # noqa: E731
+            self.noise = ndraw(0, 'noise')
+            self.noise_next = ndraw(1, 'noise_next') if self.double_q else None
+            self.noise_target = ndraw(2, 'noise_target')
+        adv_t, val_t = tnet.fwd(obs_next, B, 't', self.tau_target, noise=self.noise_target)
+        adv, val = net.fwd(obs, B, 'q', self.tau, keep_phi=True, noise=self.noise)
         adv_n = val_n = None
         if self.double_q:
-            adv_n, val_n = net.fwd(obs_next, B, 'n', self.tau_next)
+            adv_n, val_n = net.fwd(obs_next, B, 'n', self.tau_next, noise=self.noise_next)
         N = self.atoms or self.quantiles or 1
         if self.implicit:                        # sample rows, scalar heads
             dadv = net.buf('dadv', (B * self.implicit['atoms'], A))
@@ -850,7 +1027,9 @@ class DQNLearner(DeviceLearner):
                    self.dp.rank * B, A, float(self.algo.gamma), int(dueling), int(self.double_q),
                    p(dadv), A, p(dval), p(self.td_error), None, p(self.stats_buf), st)
         with L.dw_group(st):
-            net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'])
+            net.bwd(obs, B, 'q', [dadv, dval] if dueling else [dadv], self.opt['g'], self.noise)
+        if self.noisy:
+            net.sigma_grad(self.opt['g'], self.noise)
 
     def _gradient_c51(self, net, B, advs, vals, act, rew, don, weights, dadv, dval):
         """_gradient's TD step for categorical heads: smi_dqn_c51_td and its

@@ -410,6 +410,59 @@ def implicit_main(args):
                           'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
 
 
+def noisy_main(args):
+    """--noisy [--pixel] [--atoms N | --quantiles N | --implicit]: learn() at B = 512 with the
+    plain and the noisy layers, eager and replayed, and the noisy forward against
+    smi_linear_forward at the FC shapes of the low-dim default and of the pixel model"""
+    B, D, A = 512, 17, 6
+    p, st = L.ptr, L.stream()
+    g = torch.Generator().manual_seed(0)
+    for K, N in ((17, 256), (128, 128), (128, 6), (3136, 1024), (512, 6)):
+        x, y = torch.randn(B, K, generator=g).cuda(), torch.zeros(B, N).cuda()
+        w, ws, b, bs = (torch.randn(*sh, generator=g).cuda() / K ** 0.5 for sh in ((N, K), (N, K), (N,), (N,)))
+        fi, fo = torch.randn(K, generator=g).cuda(), torch.randn(N, generator=g).cuda()
+
+        def plain():
+            for _ in range(args.calls):
+                L.call('smi_linear_forward', p(x), K, B, K, p(w), K, p(b), N, 1, p(y), N, st)
+
+        def noisy():
+            for _ in range(args.calls):
+                L.call('smi_noisy_forward', p(x), K, B, K, p(w), p(ws), K, p(b), p(bs), p(fi), p(fo), N, 1,
+                       p(y), N, st)
+        for name, fn in (('linear_forward', plain), ('noisy_forward', noisy)):
+            med, q1, q3 = (1e3 * t / args.calls for t in timed(fn, args.iters, args.warmup))
+            print(json.dumps({'measurement': name, 'rows': B, 'in': K, 'out': N,
+                              'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                              'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
+                              'iters': args.iters}), flush=True)
+    lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = B
+    lc.model.fc_hidden_sizes = [128, 128]
+    ec, b = discrete_env_config(D, A), None
+    if args.pixel:
+        shape = (4, 84, 84)
+        lc.model.convs, lc.model.fc_hidden_sizes = NATURE, [512]
+        ec, b = discrete_pixel_env_config(shape, A), pixel_batch(B, shape, A, 0)
+    b = b if b is not None else dqn_batch(B, D, A, 0)
+    if args.implicit:
+        lc.algo.distributional.update(enabled=True, kind='implicit', atoms=args.atoms or 8)
+    elif args.quantiles:
+        lc.algo.distributional.update(enabled=True, kind='quantile', atoms=args.quantiles, kappa=args.kappa)
+    elif args.atoms:
+        lc.algo.distributional.update(enabled=True, atoms=args.atoms)
+    for noisy_on in (False, True):
+        lc.model.noisy.enabled = noisy_on
+        for graph in (False, True):
+            learner = DQNLearner(lc, ec, seed=0, use_graph=graph)
+            med, q1, q3 = timed(lambda: learner.learn(b), args.iters, args.warmup)
+            print(json.dumps({'measurement': 'dqn_learn_' + ('graph' if graph else 'eager'),
+                              'noisy': noisy_on, 'pixel': bool(args.pixel), 'median_ms': round(med, 4),
+                              'q1_ms': round(q1, 4), 'q3_ms': round(q3, 4), 'iters': args.iters}),
+                  flush=True)
+            del learner
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
@@ -423,6 +476,9 @@ def main():
                     help='N: the quantile (QR-DQN) head with N quantiles instead of scalar heads')
     ap.add_argument('--implicit', action='store_true',
                     help='the implicit quantile (IQN) head; --atoms N is its sample count (8)')
+    ap.add_argument('--noisy', action='store_true',
+                    help='noisy linear layers against the plain ones; combines with --atoms, '
+                         '--quantiles, --implicit and --pixel')
     ap.add_argument('--kappa', type=float, default=1.0,
                     help='--quantiles: the Huber threshold (0: the pinball loss)')
     ap.add_argument('--calls', type=int, default=20,
@@ -430,6 +486,8 @@ def main():
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
+    if args.noisy:
+        return noisy_main(args)
     if args.implicit:
         return implicit_main(args)
     if args.atoms or args.quantiles:
