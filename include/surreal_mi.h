@@ -687,6 +687,29 @@ int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div
                                float* dw, float* db, void* scratch, int64_t scratch_bytes,
                                void* stream);
 
+/* The same layer with bf16 operands (model.conv_dtype = 'bf16' of the DQN
+ * models): the arguments, ranges, checks and error codes of smi_conv2d_* above,
+ * fp32 tensors in and out.  x (uint8: exactly), w and dy are rounded to bf16
+ * (nearest even; NaN, +-inf and -0.0 kept) while they are staged for
+ * v_mfma_f32_16x16x32_bf16, the products are exact in fp32 and summed in fp32;
+ * bias, / 255, ReLU and relu_mask act on the fp32 sums, db is the fp32 sum of dy
+ * as given.  With operands that are exact in bf16 the results are those of the
+ * fp32 layer up to the order of the fp32 sums.  The weight gradient's scratch
+ * has a size of its own (smi_conv2d_scratch_bytes_bf16); fixed summation
+ * order, two runs are bit-identical. */
+int64_t smi_conv2d_scratch_bytes_bf16(int64_t n, int cin, int h, int w, int cout, int k, int stride,
+                                      int pad);
+int smi_conv2d_forward_bf16(const void* x, int x_u8, int div255, int64_t n, int cin, int h, int w,
+                            const float* wgt, const float* bias, int cout, int k, int stride,
+                            int pad, int act, float* y, void* stream);
+int smi_conv2d_backward_input_bf16(const float* dy, int64_t n, int cin, int h, int w,
+                                   const float* wgt, int cout, int k, int stride, int pad,
+                                   const float* relu_mask, float* dx, void* stream);
+int smi_conv2d_backward_weight_bf16(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                                    int cin, int h, int w, int cout, int k, int stride, int pad,
+                                    float* dw, float* db, void* scratch, int64_t scratch_bytes,
+                                    void* stream);
+
 /* The pixel stem of free shape: CNNStemNetwork (builders.py:8-33) with the
  * layers of model.conv_spec (ddpg_configs.py:22-27) on any camera.  n conv
  * layers, 1 <= n <= 4, layer i = Conv2d(cout[i], k[i], stride[i]) without

@@ -298,6 +298,13 @@ _SIGS = {
     'smi_conv2d_backward_input': (c_int, [P, c_i64, c_int, c_int, c_int, P] + [c_int] * 4 + [P, P, P]),
     'smi_conv2d_backward_weight': (c_int, [P, P, c_int, c_int, c_i64] + [c_int] * 7 +
                                    [P, P, P, c_i64, P]),
+    'smi_conv2d_scratch_bytes_bf16': (c_i64, [c_i64] + [c_int] * 7),
+    'smi_conv2d_forward_bf16': (c_int, [P, c_int, c_int, c_i64, c_int, c_int, c_int, P, P] +
+                                [c_int] * 5 + [P, P]),
+    'smi_conv2d_backward_input_bf16': (c_int, [P, c_i64, c_int, c_int, c_int, P] + [c_int] * 4 +
+                                       [P, P, P]),
+    'smi_conv2d_backward_weight_bf16': (c_int, [P, P, c_int, c_int, c_i64] + [c_int] * 7 +
+                                        [P, P, P, c_i64, P]),
     'smi_stem_param_count': (c_i64, [c_int, P, P, P] + [c_int] * 4),
     'smi_stem_act_floats': (c_i64, [c_i64, c_int, P, P, P] + [c_int] * 4),
     'smi_stem_scratch_bytes': (c_i64, [c_i64, c_int, P, P, P] + [c_int] * 4),

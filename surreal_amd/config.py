@@ -179,6 +179,8 @@ DDPG_DEFAULT_LEARNER_CONFIG.extend(BASE_LEARNER_CONFIG)
 DQN_DEFAULT_LEARNER_CONFIG = Config({
     'model': {
         'convs': [],
+        # operand type of the conv layers' MFMAs: 'fp32' | 'bf16' (fp32 tensors and sums either way)
+        'conv_dtype': 'fp32',
         'fc_hidden_sizes': [128, 128],
         'dueling': True,
         # noisy linear layers (NoisyNet, factorised Gaussian noise) in place of

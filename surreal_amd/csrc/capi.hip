@@ -8,6 +8,7 @@
 #include "smi_internal.hpp"
 #include "rnn_layout.hpp"
 #include "conv_plan.hpp"
+#include "conv_bf16_plan.hpp"
 #include "stem_plan.hpp"
 
 namespace smi {
@@ -1138,6 +1139,52 @@ int smi_conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div
           "smi_conv2d_scratch_bytes");
   return conv2d_backward_weight(dy, x, x_u8 != 0, div255 != 0, n, g, dw, db,
                                 static_cast<float*>(scratch), SMI_STREAM(stream));
+}
+
+/* ---- the same layer with bf16 operands (conv_bf16_kernels.hip): same checks */
+int64_t smi_conv2d_scratch_bytes_bf16(int64_t n, int cin, int h, int w, int cout, int k, int stride,
+                                      int pad) {
+  if (n < 0 || !conv_geom_ok(cin, h, w, cout, k, stride, pad)) {
+    set_error(SMI_E_ARG, "conv2d_scratch_bytes_bf16: geometry out of range");
+    return -1;
+  }
+  return conv_bf16_scratch_bytes(conv_geom(cin, h, w, cout, k, stride, pad), n);
+}
+
+int smi_conv2d_forward_bf16(const void* x, int x_u8, int div255, int64_t n, int cin, int h, int w,
+                            const float* wgt, const float* bias, int cout, int k, int stride,
+                            int pad, int act, float* y, void* stream) {
+  REQUIRE(x && wgt && bias && y && n >= 0, "conv2d_forward_bf16: null pointer or negative n");
+  REQUIRE(act == ACT_NONE || act == ACT_RELU, "conv2d_forward_bf16: act is 0 (none) or 1 (ReLU)");
+  CONV_GEOM_CHECK("conv2d_forward_bf16");
+  return conv2d_forward_bf16(x, x_u8 != 0, div255 != 0, n,
+                             conv_geom(cin, h, w, cout, k, stride, pad), wgt, bias, act, y,
+                             SMI_STREAM(stream));
+}
+
+int smi_conv2d_backward_input_bf16(const float* dy, int64_t n, int cin, int h, int w,
+                                   const float* wgt, int cout, int k, int stride, int pad,
+                                   const float* relu_mask, float* dx, void* stream) {
+  REQUIRE(dy && wgt && dx && n >= 0, "conv2d_backward_input_bf16: null pointer or negative n");
+  CONV_GEOM_CHECK("conv2d_backward_input_bf16");
+  return conv2d_backward_input_bf16(dy, n, conv_geom(cin, h, w, cout, k, stride, pad), wgt,
+                                    relu_mask, dx, SMI_STREAM(stream));
+}
+
+int smi_conv2d_backward_weight_bf16(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                                    int cin, int h, int w, int cout, int k, int stride, int pad,
+                                    float* dw, float* db, void* scratch, int64_t scratch_bytes,
+                                    void* stream) {
+  REQUIRE(dy && x && dw && db && n >= 0, "conv2d_backward_weight_bf16: null pointer or negative n");
+  CONV_GEOM_CHECK("conv2d_backward_weight_bf16");
+  const ConvGeom g = conv_geom(cin, h, w, cout, k, stride, pad);
+  if (n == 0) return SMI_OK;
+  REQUIRE(scratch && scratch_bytes >= conv_bf16_scratch_bytes(g, n) &&
+          (reinterpret_cast<uintptr_t>(scratch) & 3) == 0,
+          "conv2d_backward_weight_bf16: scratch missing, misaligned or smaller than "
+          "smi_conv2d_scratch_bytes_bf16");
+  return conv2d_backward_weight_bf16(dy, x, x_u8 != 0, div255 != 0, n, g, dw, db,
+                                     static_cast<float*>(scratch), SMI_STREAM(stream));
 }
 #undef CONV_GEOM_CHECK
 

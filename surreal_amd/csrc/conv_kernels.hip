@@ -487,9 +487,15 @@ int conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255,
                        static_cast<const float*>(x), part, g, n, pl, pr, skip);
   ktime_end(kt, KT_CNN_BWD, 2.0 * (double)n * g.P * g.K * g.cout, st);
   RC_CHECK(check_launch("conv_dw_kernel"));
-  const int64_t nb = (pl.slab + 63) / 64;
+  return launch_conv_dw_reduce(part, pl.splits, pl.slab, (int64_t)g.cout * g.K, dw, db, div255, st,
+                               skip);
+}
+
+int launch_conv_dw_reduce(const float* part, int splits, int64_t slab, int64_t nw, float* dw,
+                          float* db, int div255, hipStream_t st, const int* skip) {
+  const int64_t nb = (slab + 63) / 64;
   hipLaunchKernelGGL(conv_dw_reduce, dim3((unsigned)(nb < 4096 ? nb : 4096)), dim3(kWG), 0, st, part,
-                     pl.splits, pl.slab, (int64_t)g.cout * g.K, dw, db, div255, skip);
+                     splits, slab, nw, dw, db, div255, skip);
   return check_launch("conv_dw_reduce");
 }
 

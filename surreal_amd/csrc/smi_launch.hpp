@@ -159,6 +159,21 @@ int conv2d_backward_input(const float* dy, int64_t n, const ConvGeom& g, const f
 int conv2d_backward_weight(const float* dy, const void* x, int x_u8, int div255, int64_t n,
                            const ConvGeom& g, float* dw, float* db, float* part, hipStream_t st,
                            const int* skip = nullptr, const PixRows* rows = nullptr);
+// dw [nw] and db [slab - nw] = the `splits` partial images of `slab` floats in
+// part, added in a fixed order (dw / 255 with div255)
+int launch_conv_dw_reduce(const float* part, int splits, int64_t slab, int64_t nw, float* dw,
+                          float* db, int div255, hipStream_t st, const int* skip);
+// ---- conv_bf16_kernels.hip (the same layer with bf16 operands on the bf16 MFMA, fp32
+// tensors and sums; part: conv_bf16_scratch_bytes(g, n), conv_bf16_plan.hpp)
+int conv2d_forward_bf16(const void* x, int x_u8, int div255, int64_t n, const ConvGeom& g,
+                        const float* wgt, const float* bias, int act, float* y, hipStream_t st,
+                        const int* skip = nullptr);
+int conv2d_backward_input_bf16(const float* dy, int64_t n, const ConvGeom& g, const float* wgt,
+                               const float* mask, float* dx, hipStream_t st,
+                               const int* skip = nullptr);
+int conv2d_backward_weight_bf16(const float* dy, const void* x, int x_u8, int div255, int64_t n,
+                                const ConvGeom& g, float* dw, float* db, float* part,
+                                hipStream_t st, const int* skip = nullptr);
 // ---- stem.hip (the pixel stem of free shape: fused or general, stem_plan.hpp)
 // A[i]: activation of layer i, [rows][act[i]] (the fused form takes A[0] == NULL
 // when no backward follows); feat [rows][F] at ldf

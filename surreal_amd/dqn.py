@@ -132,6 +132,18 @@ double-Q, 2 target; learner.noise, noise_next, noise_target; key = the seed XOR
 NOISE_KEY, apart from the implicit heads' fractions), the same on every
 data-parallel rank, and after the grouped mu weight gradients one
 smi_noisy_sigma_grad fills the sigma range of the gradient image.
+
+bf16 convolutions (model.conv_dtype = 'bf16', default 'fp32'; pixel models
+only, anything else is a ConfigError; conv_bf16_kernels.hip): every conv
+launch above becomes its smi_conv2d_*_bf16 twin, same arguments and one launch
+each, with a scratch size of its own.  The frames (exactly), the weights, the
+float activations a layer reads and the gradients arriving at a layer's output
+are rounded to bf16 (nearest even) while the kernels stage them for
+v_mfma_f32_16x16x32_bf16; sums, bias, / 255, ReLU, masks and db are fp32.
+Parameters, activations, gradients, Adam, the target copy, checkpoints, the
+exchange image and the publisher stay fp32: nothing outside the conv launches
+knows the option, so graph replay and dp are the fp32 model's.  The FC layers,
+the heads, the noisy layers and fc_tau_layer are untouched.
 """
 import numpy as np
 import torch
@@ -190,6 +202,8 @@ def dqn_specs(learner_config, env_config):
 
 
 MAX_CONVS = 4
+# model.conv_dtype -> suffix of the smi_conv2d_* symbols the conv layers run on
+CONV_DTYPES = {'fp32': '', 'bf16': '_bf16'}
 
 
 def conv_chain(input_shape, convs):
@@ -369,7 +383,8 @@ def dqn_model_kwargs(learner_config, env_config):
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
     atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
     with kind 'implicit' the dict of check_implicit; model.noisy.enabled adds
-    noisy = sigma0.  Host only."""
+    noisy = sigma0; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype.
+    Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -377,6 +392,14 @@ def dqn_model_kwargs(learner_config, env_config):
     else:
         D, A, hidden, dueling = dqn_specs(learner_config, env_config)
         kw = {}
+    conv_dtype = learner_config['model'].get('conv_dtype', 'fp32')
+    if conv_dtype not in CONV_DTYPES:
+        raise ConfigError("DQN model.conv_dtype must be 'fp32' or 'bf16', got {!r}".format(conv_dtype))
+    if conv_dtype != 'fp32':
+        if 'convs' not in kw:
+            raise ConfigError("DQN model.conv_dtype = 'bf16' needs model.convs: it is the operand "
+                              'type of the convolution layers')
+        kw['conv_dtype'] = conv_dtype
     dist = learner_config['algo'].get('distributional') or {}
     kind = dist.get('kind', 'categorical')
     if dist.get('enabled', False) and kind == 'implicit':
@@ -436,8 +459,12 @@ class FFQfunc(nn.Module):
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
                  convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
-                 quantiles=None, kappa=1.0, implicit=None, noisy=None):
+                 quantiles=None, kappa=1.0, implicit=None, noisy=None, conv_dtype='fp32'):
         super().__init__()
+        if conv_dtype not in CONV_DTYPES or (conv_dtype != 'fp32' and not convs):
+            raise ConfigError("FFQfunc conv_dtype is 'fp32' or, with convs, 'bf16'; got "
+                              '{!r}'.format(conv_dtype))
+        self.conv_dtype = conv_dtype
         self.noisy = None if noisy is None else check_noisy(noisy)
         self.atoms, self.v_min, self.v_max = None, None, None
         self.quantiles, self.kappa = None, None
@@ -579,7 +606,7 @@ class FFQfunc(nn.Module):
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
                     v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
                     kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit,
-                    noisy=self.noisy)
+                    noisy=self.noisy, conv_dtype=self.conv_dtype)
         c.copy_from(self)
         return c
 
@@ -636,7 +663,7 @@ class _QNet(LaunchNet):
             ho, wo = (H + 2 * pad - k) // s + 1, (W + 2 * pad - k) // s + 1
             y = self.buf(f'{pre}_c{i}', (rows, co, ho, wo))
             conv = m.conv_layers[i]
-            L.call('smi_conv2d_forward', p(x), int(x.dtype == torch.uint8),
+            L.call('smi_conv2d_forward' + CONV_DTYPES[m.conv_dtype], p(x), int(x.dtype == torch.uint8),
                    int(i == 0 and m.is_uint8), rows, ci, H, W, p(conv.weight), p(conv.bias), co, k,
                    s, pad, RELU, p(y), self.st)
             x = y
@@ -651,19 +678,21 @@ class _QNet(LaunchNet):
         S = 2 if m.dueling else 1
         n = len(m.conv_geoms)
         acts = [x] + [self.bufs[f'{pre}_c{i}'] for i in range(n)]
-        need = max(int(L.lib().smi_conv2d_scratch_bytes(rows, *geo)) for geo in m.conv_geoms)
+        sfx = CONV_DTYPES[m.conv_dtype]
+        scratch_bytes = getattr(L.lib(), 'smi_conv2d_scratch_bytes' + sfx)
+        need = max(int(scratch_bytes(rows, *geo)) for geo in m.conv_geoms)
         scratch = self.buf('conv_scratch', ((need + 3) // 4,))
         dy = self.buf(f'{pre}_dc{n - 1}', tuple(acts[n].shape))
         self.ndx(noise, 0, dH1, S * hs[0], rows, S * hs[0], m.w1, D, D, acts[n], D, dy, D)
         for i in range(n - 1, -1, -1):
             ci, H, W, co, k, s, pad = m.conv_geoms[i]
             conv, xi = m.conv_layers[i], acts[i]
-            L.call('smi_conv2d_backward_weight', p(dy), p(xi), int(xi.dtype == torch.uint8),
+            L.call('smi_conv2d_backward_weight' + sfx, p(dy), p(xi), int(xi.dtype == torch.uint8),
                    int(i == 0 and m.is_uint8), rows, ci, H, W, co, k, s, pad,
                    p(g[m.off(conv.weight):]), p(g[m.off(conv.bias):]), p(scratch), need, self.st)
             if i:
                 dx = self.buf(f'{pre}_dc{i - 1}', tuple(xi.shape))
-                L.call('smi_conv2d_backward_input', p(dy), rows, ci, H, W, p(conv.weight), co, k, s,
+                L.call('smi_conv2d_backward_input' + sfx, p(dy), rows, ci, H, W, p(conv.weight), co, k, s,
                        pad, p(xi), p(dx), self.st)
                 dy = dx
 

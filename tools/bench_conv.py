@@ -16,7 +16,10 @@ layer (F = 8 here, 0.1 % of the FLOP).
 rocprofv3 --kernel-trace --stats run of its own).  When MIOpen cannot run, that
 is printed and the project's numbers stand alone.  One JSON line per measurement.
 
-Usage: python tools/bench_conv.py [--batch 512] [--iters 30] [--warmup 5] [--ours-only]
+--bf16 times the bf16 form of the layer (conv_bf16_kernels.hip) against the
+fp32 form instead, alternately in one process, at batch 32 and --batch.
+
+Usage: python tools/bench_conv.py [--batch 512] [--iters 30] [--warmup 5] [--ours-only | --bf16]
 """
 import argparse
 import json
@@ -35,8 +38,8 @@ PEAK = 157.3e12
 P = L.ptr
 
 
-def alternate(fns, iters, warm):
-    """median ms of each fn, timed in turn within every iteration"""
+def samples(fns, iters, warm):
+    """sorted ms of each fn, timed in turn within every iteration"""
     for _ in range(warm):
         for f in fns:
             f()
@@ -50,18 +53,19 @@ def alternate(fns, iters, warm):
             e.record()
             evs[i].append((s, e))
     torch.cuda.synchronize()
-    out = []
-    for ev in evs:
-        ts = sorted(s.elapsed_time(e) for s, e in ev)
-        out.append(ts[len(ts) // 2])
-    return out
+    return [sorted(s.elapsed_time(e) for s, e in ev) for ev in evs]
+
+
+def alternate(fns, iters, warm):
+    """median ms of each fn, timed in turn within every iteration"""
+    return [ts[len(ts) // 2] for ts in samples(fns, iters, warm)]
 
 
 class Layer(object):
-    def __init__(self, n, cin, H, W, cout, k, s, p, u8, seed=0):
+    def __init__(self, n, cin, H, W, cout, k, s, p, u8, seed=0, sfx=''):
         g = torch.Generator().manual_seed(seed)
         self.geom = (cin, H, W, cout, k, s, p)
-        self.n, self.u8 = n, u8
+        self.n, self.u8, self.sfx = n, u8, sfx      # sfx '_bf16': the bf16 form of the layer
         self.ho, self.wo = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
         if u8:
             self.x = torch.randint(0, 256, (n, cin, H, W), generator=g, dtype=torch.uint8).cuda()
@@ -75,24 +79,24 @@ class Layer(object):
         self.y = torch.empty_like(self.dy)
         self.dx = torch.empty(n, cin, H, W).cuda()
         self.dw, self.db = torch.empty_like(self.w), torch.empty_like(self.b)
-        self.nbytes = int(L.lib().smi_conv2d_scratch_bytes(n, *self.geom))
+        self.nbytes = int(getattr(L.lib(), 'smi_conv2d_scratch_bytes' + sfx)(n, *self.geom))
         self.scratch = torch.empty(self.nbytes // 4 + 1).cuda()
         self.flop = 2.0 * n * self.ho * self.wo * cin * k * k * cout
         self.st = L.stream()
 
     def fwd(self):
         cin, H, W, cout, k, s, p = self.geom
-        L.call('smi_conv2d_forward', P(self.x), int(self.u8), int(self.u8), self.n, cin, H, W,
+        L.call('smi_conv2d_forward' + self.sfx, P(self.x), int(self.u8), int(self.u8), self.n, cin, H, W,
                P(self.w), P(self.b), cout, k, s, p, 1, P(self.y), self.st)
 
     def bwd_input(self):
         cin, H, W, cout, k, s, p = self.geom
-        L.call('smi_conv2d_backward_input', P(self.dy), self.n, cin, H, W, P(self.w), cout, k, s, p,
+        L.call('smi_conv2d_backward_input' + self.sfx, P(self.dy), self.n, cin, H, W, P(self.w), cout, k, s, p,
                P(self.xf), P(self.dx), self.st)
 
     def bwd_weight(self):
         cin, H, W, cout, k, s, p = self.geom
-        L.call('smi_conv2d_backward_weight', P(self.dy), P(self.x), int(self.u8), int(self.u8),
+        L.call('smi_conv2d_backward_weight' + self.sfx, P(self.dy), P(self.x), int(self.u8), int(self.u8),
                self.n, cin, H, W, cout, k, s, p, P(self.dw), P(self.db), P(self.scratch),
                self.nbytes, self.st)
 
@@ -115,15 +119,45 @@ def report(name, layer, ours_ms, torch_ms=None, **extra):
     print(json.dumps(d), flush=True)
 
 
+def bf16_main(args):
+    """--bf16: every Atari layer and direction at batch 32 and --batch, the
+    fp32 form and the bf16 form timed alternately in this process: medians,
+    the fp32 form's quartiles (its run-to-run spread) and the summed stem"""
+    for n in sorted({32, args.batch}):
+        total = {'fp32': 0.0, 'bf16': 0.0, 'fp32_q1': 0.0, 'fp32_q3': 0.0}
+        for name, geom in (('atari_l1', (4, 84, 84, 32, 8, 4, 4, True)),
+                           ('atari_l2', (32, 22, 22, 64, 4, 2, 2, False)),
+                           ('atari_l3', (64, 12, 12, 64, 3, 1, 1, False))):
+            a, b = Layer(n, *geom), Layer(n, *geom, sfx='_bf16')
+            for kind in ('fwd', 'bwd_weight') + (('bwd_input',) if name != 'atari_l1' else ()):
+                ta, tb = samples([getattr(a, kind), getattr(b, kind)], args.iters, args.warmup)
+                q = lambda ts, f: ts[int(f * len(ts))]                     # noqa: E731
+                # one learn() runs the stem forward three times and the backward once
+                reps = 3 if kind == 'fwd' else 1
+                for key, v in (('fp32', q(ta, .5)), ('bf16', q(tb, .5)), ('fp32_q1', q(ta, .25)),
+                               ('fp32_q3', q(ta, .75))):
+                    total[key] += reps * v
+                print(json.dumps({'measurement': f'{name}_{kind}', 'n': n, 'fp32_ms': round(q(ta, .5), 4),
+                                  'fp32_q1_ms': round(q(ta, .25), 4), 'fp32_q3_ms': round(q(ta, .75), 4),
+                                  'bf16_ms': round(q(tb, .5), 4), 'bf16_q1_ms': round(q(tb, .25), 4),
+                                  'bf16_q3_ms': round(q(tb, .75), 4)}), flush=True)
+        print(json.dumps(dict({'measurement': 'atari_stem_3_forwards_1_backward_ms', 'n': n},
+                              **{k: round(v, 4) for k, v in total.items()})), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--batch', type=int, default=512)
     ap.add_argument('--iters', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--ours-only', action='store_true')
+    ap.add_argument('--bf16', action='store_true',
+                    help='time the bf16 form (smi_conv2d_*_bf16) next to the fp32 one and nothing else')
     args = ap.parse_args()
     n = args.batch
     L.ensure_workspace(torch.device('cuda', torch.cuda.current_device()))
+    if args.bf16:
+        return bf16_main(args)
     atari = [('atari_l1', Layer(n, 4, 84, 84, 32, 8, 4, 4, True)),
              ('atari_l2', Layer(n, 32, 22, 22, 64, 4, 2, 2, False)),
              ('atari_l3', Layer(n, 64, 12, 12, 64, 3, 1, 1, False))]

@@ -14,6 +14,7 @@ B = 512, eager and as a graph replay, and next to each the same step written in
 eager torch on the same GPU (nn.Conv2d through MIOpen, fp32, Adam eps 1e-4,
 clip_grad_norm_ 10): the expectation a pixel learn() is reported against.  When
 the torch step cannot run, that is printed and the project's numbers stand alone.
+--conv-bf16 adds the same step with model.conv_dtype = 'bf16' to each.
 
 --gpus N (2 <= N <= 16) times the data-parallel loop instead: one process per
 GPU (torch.multiprocessing spawn, 'nccl' = RCCL), each with one
@@ -44,7 +45,7 @@ second of what each must read and write once, one smi_iqn_td call at A in
 a graph replay.
 
 Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
-                                 [--pixel | --gpus N | --atoms N | --quantiles N [--kappa K]
+                                 [--pixel [--conv-bf16] | --gpus N | --atoms N | --quantiles N [--kappa K]
                                   | --implicit [--atoms N]]
 """
 import argparse
@@ -166,9 +167,13 @@ def pixel_main(args):
         lc.replay.batch_size = B
         lc.model.convs, lc.model.fc_hidden_sizes = NATURE, [hidden]
         b = pixel_batch(B, shape, A, 0)
-        for name, graph in (('dqn_pixel_learn_eager', False), ('dqn_pixel_learn_graph', True)):
+        runs = [('dqn_pixel_learn_eager', False, 'fp32'), ('dqn_pixel_learn_graph', True, 'fp32')]
+        if args.conv_bf16:
+            runs += [('dqn_pixel_learn_eager', False, 'bf16'), ('dqn_pixel_learn_graph', True, 'bf16')]
+        for name, graph, conv_dtype in runs:
+            lc.model.conv_dtype = conv_dtype
             learner = DQNLearner(lc, ec, seed=0, use_graph=graph)
-            extra = {}
+            extra = {'conv_dtype': conv_dtype}
             if not graph:
                 learner.learn(b)
                 extra['library_calls_per_step'] = count_launches(lambda: learner.learn(b))[1]
@@ -468,6 +473,8 @@ def main():
     ap.add_argument('--iters', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--pixel', action='store_true')
+    ap.add_argument('--conv-bf16', action='store_true',
+                    help='--pixel with model.conv_dtype = bf16 next to the fp32 step')
     ap.add_argument('--gpus', type=int, default=1,
                     help='N >= 2: the data-parallel loop, one process per GPU')
     ap.add_argument('--atoms', type=int, default=0,
@@ -492,7 +499,7 @@ def main():
         return implicit_main(args)
     if args.atoms or args.quantiles:
         return dist_main(args)
-    if args.pixel:
+    if args.pixel or args.conv_bf16:
         return pixel_main(args)
     B, D, A = 512, 17, 6
     lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
