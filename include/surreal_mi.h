@@ -820,6 +820,21 @@ int smi_linear_forward(const float* x, int64_t ldx, int rows, int in_dim, const 
 int smi_linear_backward_input(const float* dy, int64_t ldg, int rows, int out_dim,
                               const float* w, int64_t ldw, int in_dim, const float* relu_mask,
                               int64_t ldm, float* dx, int64_t lddx, void* stream);
+/* The same two calls with bf16 operands (model.fc_dtype = 'bf16' of the DQN
+ * models; linear_bf16_kernels.hip): arguments, leading dimensions, checks and
+ * error codes are those above.  x, w and dy are rounded to bf16 (nearest even;
+ * NaN and infinities kept) while the kernel stages them for
+ * v_mfma_f32_16x16x32_bf16; products and sums, bias, activation and the mask
+ * test are fp32, and so is every tensor in memory.  Deterministic: a reduction
+ * too long for the output's tile count is cut into slabs that a fixed-order
+ * reducer adds (smi_last_launch then names the reducer). */
+int smi_linear_forward_bf16(const float* x, int64_t ldx, int rows, int in_dim, const float* w,
+                            int64_t ldw, const float* b, int out_dim, int act, float* y,
+                            int64_t ldy, void* stream);
+int smi_linear_backward_input_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                   const float* w, int64_t ldw, int in_dim,
+                                   const float* relu_mask, int64_t ldm, float* dx, int64_t lddx,
+                                   void* stream);
 /* smi_linear_forward plus y[r][out_dim + j] = s[r*lds + j] for j < s_cols in
  * the same launch: CriticNetworkX's cat(relu(x W1^T + b1), action) input of
  * its second layer (ddpg_net's critic, ddpg.py:244-352 callers) written by one

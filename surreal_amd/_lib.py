@@ -202,6 +202,10 @@ _SIGS = {
                                           c_i64, P]),
     'smi_linear_backward_weight': (c_int, [P, c_i64, c_int, c_int, P, c_i64, c_int, P, c_i64, P,
                                            c_int, P]),
+    'smi_linear_forward_bf16': (c_int, [P, c_i64, c_int, c_int, P, c_i64, P, c_int, c_int, P, c_i64,
+                                        P]),
+    'smi_linear_backward_input_bf16': (c_int, [P, c_i64, c_int, c_int, P, c_i64, c_int, P, c_i64, P,
+                                               c_i64, P]),
     'smi_mse_grad': (c_int, [P, c_i64, P, c_i64, P, P, P]),
     'smi_mse_grad_weighted': (c_int, [P, c_i64, P, P, c_i64, P, P, P, P]),
     'smi_mse_grad_weighted_shard': (c_int, [P, c_i64, P, P, c_i64, c_i64, c_i64, P, P, P, P]),

@@ -16,7 +16,8 @@ BUILD = os.path.join(ROOT, 'build', 'obj')
 LIB = os.path.join(HERE, 'libsurreal_mi.so')
 HEADERS = ['smi_device.hpp', 'smi_internal.hpp', 'lstm_cell.hpp', 'pol_rows.hpp', 'mt19937.hpp',
            'gemm_args.hpp', 'dw_plan.hpp', 'smi_shapes.hpp', 'smi_launch.hpp', 'rnn_layout.hpp',
-           'rnn_kernels.hpp', 'conv_plan.hpp', 'conv_bf16_plan.hpp', 'stem_plan.hpp', 'dqn_rows.hpp', 'philox.hpp']
+           'rnn_kernels.hpp', 'conv_plan.hpp', 'conv_bf16_plan.hpp', 'stem_plan.hpp', 'dqn_rows.hpp', 'philox.hpp',
+           'bf16_stage.hpp', 'linear_bf16_plan.hpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-object-version=5',
@@ -34,7 +35,8 @@ CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-obje
 NO_PK_F32 = ['-Xclang', '-target-feature', '-Xclang', '-packed-fp32-ops']
 UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('sampler_kernels.hip', []), ('per_kernels.hip', []),
-         ('linear_kernels.hip', []), ('linear_dw.hip', []), ('ddpg_kernels.hip', []),
+         ('linear_kernels.hip', []), ('linear_dw.hip', []), ('linear_bf16_kernels.hip', []),
+         ('ddpg_kernels.hip', []),
          ('dqn_kernels.hip', []), ('dqn_dist_kernels.hip', NO_PK_F32),
          ('dqn_quant_kernels.hip', NO_PK_F32), ('dqn_iqn_kernels.hip', NO_PK_F32),
          ('noisy_kernels.hip', []),

@@ -181,6 +181,9 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
         'convs': [],
         # operand type of the conv layers' MFMAs: 'fp32' | 'bf16' (fp32 tensors and sums either way)
         'conv_dtype': 'fp32',
+        # operand type of the FC layers' forward and input-gradient MFMAs: 'fp32' | 'bf16'
+        # (fp32 tensors, sums and weight gradients either way; not with noisy layers)
+        'fc_dtype': 'fp32',
         'fc_hidden_sizes': [128, 128],
         'dueling': True,
         # noisy linear layers (NoisyNet, factorised Gaussian noise) in place of

@@ -433,6 +433,28 @@ int smi_linear_backward_input(const float* dy, int64_t ldg, int rows, int out_di
                               SMI_STREAM(stream));
 }
 
+int smi_linear_forward_bf16(const float* x, int64_t ldx, int rows, int in_dim, const float* w,
+                            int64_t ldw, const float* b, int out_dim, int act, float* y,
+                            int64_t ldy, void* stream) {
+  REQUIRE(x && w && y && rows >= 0 && in_dim > 0 && out_dim > 0, "linear_forward_bf16: bad args");
+  REQUIRE(ldx >= in_dim && ldy >= out_dim && ldw >= in_dim,
+          "linear_forward_bf16: leading dims too small");
+  REQUIRE(act == ACT_NONE || act == ACT_RELU || act == ACT_TANH, "linear_forward_bf16: act 0/1/2");
+  return launch_linear_fwd_bf16(x, ldx, rows, in_dim, w, ldw, b, out_dim, act, y, ldy,
+                                SMI_STREAM(stream));
+}
+
+int smi_linear_backward_input_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                   const float* w, int64_t ldw, int in_dim, const float* relu_mask,
+                                   int64_t ldm, float* dx, int64_t lddx, void* stream) {
+  REQUIRE(dy && w && dx && rows >= 0 && in_dim > 0 && out_dim > 0 && ldw >= in_dim,
+          "linear_backward_input_bf16: bad args");
+  REQUIRE(ldg >= out_dim && lddx >= in_dim && (!relu_mask || ldm >= in_dim),
+          "linear_backward_input_bf16: leading dims too small");
+  return launch_linear_bwd_dx_bf16(dy, ldg, rows, out_dim, w, ldw, in_dim, relu_mask, ldm, dx, lddx,
+                                   SMI_STREAM(stream));
+}
+
 int smi_dw_group_begin(void) { return dw_group_begin(); }
 
 int smi_dw_group_flush(void* stream) { return dw_group_flush(SMI_STREAM(stream)); }

@@ -49,6 +49,7 @@
 #include "smi_device.hpp"
 #include "smi_internal.hpp"
 #include "smi_launch.hpp"
+#include "bf16_stage.hpp"
 #include "conv_bf16_plan.hpp"
 
 namespace smi {
@@ -60,27 +61,10 @@ constexpr int NJ = kConvTile * kConvBfChunk / kWG;     // staged elements per th
 static_assert(NJ == 16 && kWG == 256 && kConvTile == 64 && kConvBfChunk == 64,
               "the staging maps below are written for 256 threads, 64 x 64 slices");
 
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 __device__ __forceinline__ float ldf(const float* p) { return *p; }
 __device__ __forceinline__ float ldf(const unsigned char* p) { return (float)*p; }
 
-// 8 fp32 -> 8 bf16 (round to nearest even), element 0 in the low half of .x
-__device__ __forceinline__ uint4 pack8(const float* v) {
-  uint32_t u[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const bf16x2 h = {(__bf16)v[2 * i], (__bf16)v[2 * i + 1]};
-    u[i] = __builtin_bit_cast(uint32_t, h);
-  }
-  return make_uint4(u[0], u[1], u[2], u[3]);
-}
-
-__device__ __forceinline__ f32x4 mfma32(const uint4& a, const uint4& b, f32x4 c) {
-  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a),
-                                                 __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
+// (pack8, mfma32: bf16_stage.hpp)
 
 // one staged slice: acc[i][j] += A[rh 32 + i 16 ..][z] * B[qh 32 + j 16 ..][z]
 __device__ __forceinline__ void conv_mma(const uint4* As, const uint4* Bs, f32x4 (&acc)[2][2],

@@ -190,6 +190,14 @@ int stem_backward(const StemPlan& p, const float* prm, const PixRows& pr, int64_
 int launch_linear_fwd_cat(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
                           const float* b, int N, int act, float* Y, int64_t ldy, const float* S,
                           int64_t lds, int xcols, hipStream_t st);
+// ---- linear_bf16_kernels.hip (launch_linear_fwd / launch_linear_bwd_dx with bf16
+// operands on the bf16 MFMA, fp32 tensors and sums; arguments checked by the caller)
+int launch_linear_fwd_bf16(const float* X, int64_t ldx, int M, int K, const float* W, int64_t ldw,
+                           const float* b, int N, int act, float* Y, int64_t ldy, hipStream_t st,
+                           const int* skip = nullptr);
+int launch_linear_bwd_dx_bf16(const float* dY, int64_t ldg, int M, int N, const float* W,
+                              int64_t ldw, int K, const float* mask, int64_t ldm, float* dX,
+                              int64_t lddx, hipStream_t st, const int* skip = nullptr);
 // ---- head_kernels.hip
 bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
                    const float* W1, const float* W2, const float* W3);

@@ -142,8 +142,24 @@ are rounded to bf16 (nearest even) while the kernels stage them for
 v_mfma_f32_16x16x32_bf16; sums, bias, / 255, ReLU, masks and db are fp32.
 Parameters, activations, gradients, Adam, the target copy, checkpoints, the
 exchange image and the publisher stay fp32: nothing outside the conv launches
-knows the option, so graph replay and dp are the fp32 model's.  The FC layers,
-the heads, the noisy layers and fc_tau_layer are untouched.
+knows the option, so graph replay and dp are the fp32 model's.  The noisy
+layers and fc_tau_layer are untouched; the FC layers and the heads have a
+switch of their own:
+
+bf16 dense layers (model.fc_dtype = 'bf16', default 'fp32'; with
+model.noisy.enabled a ConfigError: the noisy layers have kernels of their own;
+linear_bf16_kernels.hip): every smi_linear_forward and smi_linear_backward_input
+of the FC stack above (the first layer after the observation or the stem, the
+deeper layers of both streams and the heads of every head kind, for implicit
+heads on the B N sample rows too) becomes its _bf16 twin, same arguments and
+one launch each.  The activations, the weights and the gradients arriving at a
+layer's output are rounded to bf16 (nearest even) while the kernels stage them
+for v_mfma_f32_16x16x32_bf16; sums, bias, ReLU and masks are fp32.  Every
+weight gradient stays on the grouped fp32 launch and reads the unrounded
+activations and output gradients; the IQN embedding kernels, fc_tau_layer, the
+convolutions (conv_dtype), the TD kernels, Adam, the target copy, checkpoints,
+the exchange image and the publisher are untouched: nothing outside the two
+launch sites (_QNet.lin, _QNet.ndx) knows the option.
 """
 import numpy as np
 import torch
@@ -204,6 +220,8 @@ def dqn_specs(learner_config, env_config):
 MAX_CONVS = 4
 # model.conv_dtype -> suffix of the smi_conv2d_* symbols the conv layers run on
 CONV_DTYPES = {'fp32': '', 'bf16': '_bf16'}
+# model.fc_dtype -> suffix of smi_linear_forward / smi_linear_backward_input of the FC stack
+FC_DTYPES = {'fp32': '', 'bf16': '_bf16'}
 
 
 def conv_chain(input_shape, convs):
@@ -383,8 +401,8 @@ def dqn_model_kwargs(learner_config, env_config):
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
     atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
     with kind 'implicit' the dict of check_implicit; model.noisy.enabled adds
-    noisy = sigma0; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype.
-    Host only."""
+    noisy = sigma0; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype;
+    model.fc_dtype = 'bf16' (not with noisy layers) adds fc_dtype.  Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -415,6 +433,14 @@ def dqn_model_kwargs(learner_config, env_config):
     noisy = learner_config['model'].get('noisy') or {}
     if noisy.get('enabled', False):
         kw['noisy'] = check_noisy(noisy.get('sigma0', 0.5))
+    fc_dtype = learner_config['model'].get('fc_dtype', 'fp32')
+    if fc_dtype not in FC_DTYPES:
+        raise ConfigError("DQN model.fc_dtype must be 'fp32' or 'bf16', got {!r}".format(fc_dtype))
+    if fc_dtype != 'fp32':
+        if 'noisy' in kw:
+            raise ConfigError("DQN model.fc_dtype = 'bf16' does not combine with model.noisy: the "
+                              'noisy layers run on kernels of their own')
+        kw['fc_dtype'] = fc_dtype
     return D, A, hidden, dueling, kw
 
 
@@ -459,8 +485,13 @@ class FFQfunc(nn.Module):
 
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
                  convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
-                 quantiles=None, kappa=1.0, implicit=None, noisy=None, conv_dtype='fp32'):
+                 quantiles=None, kappa=1.0, implicit=None, noisy=None, conv_dtype='fp32',
+                 fc_dtype='fp32'):
         super().__init__()
+        if fc_dtype not in FC_DTYPES or (fc_dtype != 'fp32' and noisy is not None):
+            raise ConfigError("FFQfunc fc_dtype is 'fp32' or, without noisy layers, 'bf16'; got "
+                              '{!r}'.format(fc_dtype))
+        self.fc_dtype = fc_dtype
         if conv_dtype not in CONV_DTYPES or (conv_dtype != 'fp32' and not convs):
             raise ConfigError("FFQfunc conv_dtype is 'fp32' or, with convs, 'bf16'; got "
                               '{!r}'.format(conv_dtype))
@@ -606,7 +637,7 @@ class FFQfunc(nn.Module):
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
                     v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
                     kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit,
-                    noisy=self.noisy, conv_dtype=self.conv_dtype)
+                    noisy=self.noisy, conv_dtype=self.conv_dtype, fc_dtype=self.fc_dtype)
         c.copy_from(self)
         return c
 
@@ -649,6 +680,11 @@ class _QNet(LaunchNet):
     def __init__(self, model, bufs):
         super().__init__(model.device, bufs)
         self.m = model
+
+    def lin(self, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
+        """a dense layer's forward on the model's fc_dtype"""
+        L.call('smi_linear_forward' + FC_DTYPES[self.m.fc_dtype], p(x), ldx, rows, k, p(w), ldw, p(b),
+               n, act, p(y), ldy, self.st)
 
     def conv_fwd(self, x, rows, pre):
         """the conv stem on (rows, C, H, W) uint8 or float32 frames, read in
@@ -740,10 +776,10 @@ class _QNet(LaunchNet):
                self.st)
 
     def ndx(self, noise, li, dy, ldg, rows, n_out, w, ldw, k, mask, ldm, dx, lddx):
-        """layer li's input gradient, plain or noisy as nlin"""
+        """layer li's input gradient, plain (on the model's fc_dtype) or noisy as nlin"""
         if noise is None:
-            return L.call('smi_linear_backward_input', p(dy), ldg, rows, n_out, p(w), ldw, k,
-                          p(mask), ldm, p(dx), lddx, self.st)
+            return L.call('smi_linear_backward_input' + FC_DTYPES[self.m.fc_dtype], p(dy), ldg, rows,
+                          n_out, p(w), ldw, k, p(mask), ldm, p(dx), lddx, self.st)
         fi, fo = self._f(noise, li)
         L.call('smi_noisy_backward_input', p(dy), ldg, rows, n_out, p(w),
                p(self.m.flat[self.m.off(w) + self.m.sig_shift:]), ldw, k, p(fi), p(fo), p(mask), ldm,

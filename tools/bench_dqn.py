@@ -44,9 +44,17 @@ second of what each must read and write once, one smi_iqn_td call at A in
 {6, 18}, and learn() with algo.distributional.kind = 'implicit', eager and as
 a graph replay.
 
+--fc-bf16 times model.fc_dtype = 'bf16' against 'fp32', the two arms alternating
+call by call in one process: smi_linear_forward and smi_linear_backward_input
+against their _bf16 twins at the FC shapes of the DQN models (512 rows, and the
+32768 sample rows of implicit heads at B = 512, N = 64), then learn() at the
+Atari shape (B = 32 and 512, conv_dtype 'bf16' on both arms) and of the
+low-dimensional model with implicit heads (B = 512, 64 samples), eager and as a
+graph replay.
+
 Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
                                  [--pixel [--conv-bf16] | --gpus N | --atoms N | --quantiles N [--kappa K]
-                                  | --implicit [--atoms N]]
+                                  | --implicit [--atoms N] | --fc-bf16]
 """
 import argparse
 import copy
@@ -84,6 +92,28 @@ def timed(fn, iters, warm):
     torch.cuda.synchronize()
     ts = sorted(s.elapsed_time(e) for s, e in evs)
     return ts[len(ts) // 2], ts[len(ts) // 4], ts[3 * len(ts) // 4]
+
+
+def timed_alternating(fns, iters, warm):
+    """timed() of several arms, one call of each per round: [(median, q1, q3)]"""
+    for _ in range(warm):
+        for fn in fns:
+            fn()
+    torch.cuda.synchronize()
+    evs = [[] for _ in fns]
+    for _ in range(iters):
+        for i, fn in enumerate(fns):
+            s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            s.record()
+            fn()
+            e.record()
+            evs[i].append((s, e))
+    torch.cuda.synchronize()
+    out = []
+    for ev in evs:
+        ts = sorted(s.elapsed_time(e) for s, e in ev)
+        out.append((ts[len(ts) // 2], ts[len(ts) // 4], ts[3 * len(ts) // 4]))
+    return out
 
 
 def count_launches(fn):
@@ -468,6 +498,64 @@ def noisy_main(args):
             del learner
 
 
+def fc_main(args):
+    """--fc-bf16: the FC layers and learn() with model.fc_dtype 'fp32' and 'bf16', alternating"""
+    p, st = L.ptr, L.stream()
+    g = torch.Generator().manual_seed(0)
+    for R, K, N in ((512, 17, 256), (512, 128, 128), (512, 128, 6), (512, 512, 6), (512, 3136, 1024),
+                    (32768, 128, 128), (32768, 128, 6)):
+        x, y = torch.randn(R, K, generator=g).cuda(), torch.zeros(R, N).cuda()
+        w, b = (torch.randn(*sh, generator=g).cuda() / K ** 0.5 for sh in ((N, K), (N,)))
+        dy, dx = torch.randn(R, N, generator=g).cuda(), torch.zeros(R, K).cuda()
+
+        def fwd(sfx):
+            def run():
+                for _ in range(args.calls):
+                    L.call('smi_linear_forward' + sfx, p(x), K, R, K, p(w), K, p(b), N, 1, p(y), N, st)
+            return run
+
+        def bwd(sfx):
+            def run():
+                for _ in range(args.calls):
+                    L.call('smi_linear_backward_input' + sfx, p(dy), N, R, N, p(w), K, K, p(x), K, p(dx),
+                           K, st)
+            return run
+        for name, mk in (('linear_forward', fwd), ('linear_backward_input', bwd)):
+            res = timed_alternating([mk(''), mk('_bf16')], args.iters, args.warmup)
+            for dtype, t in zip(('fp32', 'bf16'), res):
+                med, q1, q3 = (1e3 * v / args.calls for v in t)
+                print(json.dumps({'measurement': name, 'fc_dtype': dtype, 'rows': R, 'in': K, 'out': N,
+                                  'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                                  'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
+                                  'iters': args.iters}), flush=True)
+    D, A, shape = 17, 6, (4, 84, 84)
+    cases = []
+    for B in (32, 512):
+        lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+        lc.replay.batch_size = B
+        lc.model.convs, lc.model.fc_hidden_sizes, lc.model.conv_dtype = NATURE, [512], 'bf16'
+        cases.append(('dqn_pixel_learn', B, lc, discrete_pixel_env_config(shape, A),
+                      pixel_batch(B, shape, A, 0)))
+    lc = copy.deepcopy(DQN_DEFAULT_LEARNER_CONFIG)
+    lc.replay.batch_size = 512
+    lc.model.fc_hidden_sizes = [128, 128]
+    lc.algo.distributional.update(enabled=True, kind='implicit', atoms=64)
+    cases.append(('dqn_implicit64_learn', 512, lc, discrete_env_config(D, A), dqn_batch(512, D, A, 0)))
+    for name, B, lc, ec, b in cases:
+        for graph in (False, True):
+            learners = []
+            for dtype in ('fp32', 'bf16'):
+                lc.model.fc_dtype = dtype
+                learners.append(DQNLearner(lc, ec, seed=0, use_graph=graph))
+            res = timed_alternating([lambda ln=ln: ln.learn(b) for ln in learners], args.iters,
+                                    args.warmup)
+            for dtype, (med, q1, q3) in zip(('fp32', 'bf16'), res):
+                print(json.dumps({'measurement': name + ('_graph' if graph else '_eager'), 'B': B,
+                                  'fc_dtype': dtype, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
+                                  'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+            del learners
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--iters', type=int, default=40)
@@ -486,6 +574,8 @@ def main():
     ap.add_argument('--noisy', action='store_true',
                     help='noisy linear layers against the plain ones; combines with --atoms, '
                          '--quantiles, --implicit and --pixel')
+    ap.add_argument('--fc-bf16', action='store_true',
+                    help="model.fc_dtype = 'bf16' against 'fp32': the FC layers and learn()")
     ap.add_argument('--kappa', type=float, default=1.0,
                     help='--quantiles: the Huber threshold (0: the pinball loss)')
     ap.add_argument('--calls', type=int, default=20,
@@ -493,6 +583,8 @@ def main():
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
+    if args.fc_bf16:
+        return fc_main(args)
     if args.noisy:
         return noisy_main(args)
     if args.implicit:
