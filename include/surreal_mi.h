@@ -845,6 +845,24 @@ int smi_linear_forward_cat(const float* x, int64_t ldx, int rows, int in_dim, co
 int smi_linear_backward_weight(const float* dy, int64_t ldg, int rows, int out_dim,
                                const float* x, int64_t ldx, int in_dim, float* dw, int64_t lddw,
                                float* db, int accumulate, void* stream);
+/* The weight gradient with bf16 operands (model.fc_dtype = 'bf16_all';
+ * linear_bf16_kernels.hip): smi_linear_backward_weight's arguments, leading
+ * dimensions, checks and error codes; db may be NULL, rows == 0 writes nothing.
+ *   dw[o][i] (+)= sum_r bf16(dy[r][o]) bf16(x[r][i]);  db[o] (+)= sum_r dy[r][o]
+ * dy and x are rounded (nearest even; NaN and infinities kept) while the kernel
+ * stages them for v_mfma_f32_16x16x32_bf16; products and sums are fp32 and db
+ * sums the UNROUNDED dy.  It launches at the call and never joins a
+ * smi_dw_group_begin / _flush bracket, which stays valid around it.
+ * Deterministic: few output tiles over many rows are cut into row slabs that
+ * the fixed-order reducer adds (smi_last_launch then names the reducer). */
+int smi_linear_backward_weight_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                    const float* x, int64_t ldx, int in_dim, float* dw,
+                                    int64_t lddw, float* db, int accumulate, void* stream);
+/* Its plan as host arithmetic (no device call), a function of the shape and
+ * the workspace capacity alone: plan = {out tile (64 | 16), out tiles, in tiles
+ * (of 64), row slabs, rows per slab}.  Returns the slab count (1: no reducer;
+ * negative: error). */
+int smi_diag_linear_bf16_dw_plan(int out_dim, int in_dim, int rows, int64_t ws_floats, int* plan);
 /* Grouped weight gradients: smi_linear_backward_weight calls between
  * smi_dw_group_begin() and smi_dw_group_flush(stream) (row-major operands,
  * outputs <= 512 x 512, at most 8 per group) are queued and run as ONE launch

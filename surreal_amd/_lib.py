@@ -206,6 +206,9 @@ _SIGS = {
                                         P]),
     'smi_linear_backward_input_bf16': (c_int, [P, c_i64, c_int, c_int, P, c_i64, c_int, P, c_i64, P,
                                                c_i64, P]),
+    'smi_linear_backward_weight_bf16': (c_int, [P, c_i64, c_int, c_int, P, c_i64, c_int, P, c_i64,
+                                                P, c_int, P]),
+    'smi_diag_linear_bf16_dw_plan': (c_int, [c_int, c_int, c_int, c_i64, P]),
     'smi_mse_grad': (c_int, [P, c_i64, P, c_i64, P, P, P]),
     'smi_mse_grad_weighted': (c_int, [P, c_i64, P, P, c_i64, P, P, P, P]),
     'smi_mse_grad_weighted_shard': (c_int, [P, c_i64, P, P, c_i64, c_i64, c_i64, P, P, P, P]),

@@ -181,8 +181,9 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
         'convs': [],
         # operand type of the conv layers' MFMAs: 'fp32' | 'bf16' (fp32 tensors and sums either way)
         'conv_dtype': 'fp32',
-        # operand type of the FC layers' forward and input-gradient MFMAs: 'fp32' | 'bf16'
-        # (fp32 tensors, sums and weight gradients either way; not with noisy layers)
+        # operand type of the FC layers' MFMAs: 'fp32' | 'bf16' (forwards and input gradients;
+        # weight gradients stay fp32) | 'bf16_all' (the weight gradients too; db sums the
+        # unrounded dy).  fp32 tensors and sums with every value; not with noisy layers
         'fc_dtype': 'fp32',
         'fc_hidden_sizes': [128, 128],
         'dueling': True,

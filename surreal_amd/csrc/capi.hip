@@ -10,6 +10,7 @@
 #include "conv_plan.hpp"
 #include "conv_bf16_plan.hpp"
 #include "stem_plan.hpp"
+#include "linear_bf16_plan.hpp"
 
 namespace smi {
 
@@ -467,6 +468,24 @@ int smi_linear_backward_weight(const float* dy, int64_t ldg, int rows, int out_d
   REQUIRE(ldg >= out_dim && ldx >= in_dim, "linear_backward_weight: leading dims too small");
   return launch_linear_bwd_dw(dy, ldg, rows, out_dim, x, ldx, in_dim, dw, lddw, db, accumulate,
                               SMI_STREAM(stream));
+}
+
+int smi_linear_backward_weight_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                    const float* x, int64_t ldx, int in_dim, float* dw,
+                                    int64_t lddw, float* db, int accumulate, void* stream) {
+  REQUIRE(dy && x && dw && rows >= 0 && in_dim > 0 && out_dim > 0 && lddw >= in_dim,
+          "linear_backward_weight_bf16: bad args");
+  REQUIRE(ldg >= out_dim && ldx >= in_dim, "linear_backward_weight_bf16: leading dims too small");
+  return launch_linear_bwd_dw_bf16(dy, ldg, rows, out_dim, x, ldx, in_dim, dw, lddw, db, accumulate,
+                                   SMI_STREAM(stream));
+}
+
+int smi_diag_linear_bf16_dw_plan(int out_dim, int in_dim, int rows, int64_t ws_floats, int* plan) {
+  REQUIRE(plan && out_dim > 0 && in_dim > 0 && rows > 0 && ws_floats >= 0,
+          "diag_linear_bf16_dw_plan: bad args");
+  const LinBfPlan p = linear_bf16_dw_plan(out_dim, in_dim, rows, ws_floats);
+  plan[0] = 16 * p.nt; plan[1] = p.gm; plan[2] = p.gn; plan[3] = p.splits; plan[4] = p.kchunk;
+  return p.splits;
 }
 
 int smi_mse_grad(const float* q, int64_t q_stride, const float* y, int64_t n, float* dq,

@@ -8,8 +8,8 @@
 // even, NaN and infinities preserved).  A product of two bf16 values is exact
 // in fp32 and the MFMA accumulates in fp32: after staging the only rounding is
 // that of the fp32 sums.  Bias, activation and the mask test are fp32 in the
-// epilogue, written as in linear_kernels.hip.  The weight gradient is not here:
-// it stays on the fp32 units and reads the unrounded operands.
+// epilogue, written as in linear_kernels.hip.  The weight gradient with bf16
+// operands is the third kernel of this unit (below, before the host part).
 //
 // Both are  C[m][j] = sum_z A[m][z] B[j][z]  (fwd: A = X, B = W, z = k;
 // dX: A = dY, B = W^T, z = n).  256 threads; wave w owns rows 16 w .. 16 w + 15 of
@@ -262,6 +262,152 @@ linear_bf16_kernel(GemmArgs g) {
   }
 }
 
+// ------------------------------------------------------- weight gradient
+//   dW[o][i] (+)= sum_r bf16(dY[r][o]) bf16(X[r][i])     db[o] (+)= sum_r dY[r][o]
+// C[o][i] = sum_z A[o][z] B[i][z] with z = r the batch row: BOTH operands are
+// reduction-major in memory (r is the outer index of dY and of X), so both
+// tiles take the register transpose W takes in the input gradient.  MT = 4: a
+// 64 (out) x 64 (in) tile, wave w owns out rows 16 w .. 16 w + 15 and four
+// accumulators along in; MT = 1: the 16 (out) x 64 (in) tile of the head layers
+// (out <= 16), where the four waves' accumulators lie along in (wave w owns in
+// columns 16 w .. 16 w + 15) and the A image has 16 rows.  Chunks of 64 rows, two
+// stages, one barrier per chunk, the next chunk prefetched into registers, as
+// above.
+//
+// Staging: waves 0 and 1 transpose the dY tile, waves 2 and 3 the X tile, 32
+// floats per thread.  Thread t2 = tid & 127 of a wave pair takes column quad
+// cq = (t2 & 3) | (t2 >> 5) << 2 (16 quads = 64 columns; MT = 1: only t2 < 32
+// stage dY, 4 quads) and row octet zo = (t2 >> 2) & 7: 8 loads of 16 bytes
+// P[r0 + 8 zo + e][4 cq .. 4 cq + 3] (4 lanes cover 64 contiguous bytes of a row),
+// then per column the 8 rounded values along r as one 16-byte vector at image
+// row 4 cq + c, vector zo.  Banks, for both images alike: the store starts at
+// dword 36 (4 cq + c) + 4 zo = 16 (t2 & 3) + 4 zo + 36 c mod 64; 16 consecutive
+// lanes hold 4 values of t2 & 3 and 4 consecutive zo of one half of its range:
+// 16 different multiples of 4, every bank once.  The operand reads are those of
+// the other two kernels (row l & 15 of a 16-row block, vector l >> 4).
+//
+// db comes from the UNROUNDED dy, in fp32, without a launch of its own: in the
+// workgroups of in-tile 0 the dY threads add what they prefetched, before
+// pack8, to four per-thread column sums (rows ascending); after the last chunk
+// the 8 row-octet threads of a column are added through LDS, zo ascending, and
+// thread o writes db[o] or, split, column in_dim of the slab's partial image
+// (the reducer's ones_col / bias_out path).
+//
+// Split over the rows (linear_bf16_dw_plan): slabs of a multiple of 64 rows
+// over gridDim.z, partials [slab][out][in (+ 1)] in the library workspace, the
+// fixed-order reducer applies `accumulate`; unsplit, this epilogue does.
+template <int MT>
+__global__ void __launch_bounds__(kWG)
+linear_bf16_dw_kernel(GemmArgs g) {
+  if (g.skip && g.skip[0] != 0) return;
+  constexpr int AR = 16 * MT;                         // rows of the A image: the out tile
+  constexpr int NA = MT == 4 ? 4 : 1;                 // accumulators per wave
+  __shared__ uint4 As[2][AR * LDV];
+  __shared__ uint4 Bs[2][kLinBfRows * LDV];
+  __shared__ float dbs[8][AR];
+  const int tid = threadIdx.x, l = tid & 63;
+  const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const TileIdx ti = gemm_tile_index();
+  const int o0 = ti.mt * AR, i0 = ti.nt * kLinBfRows;
+  const int in_dim = g.ones_col >= 0 ? g.ones_col : g.N;
+  const int zb = ti.z * g.kchunk;
+  const int ze = min(g.K, zb + g.kchunk);
+  const int nc = (ze - zb + kLinBfChunk - 1) / kLinBfChunk;
+  const int t2 = tid & 127;
+  const int cq = (t2 & 3) | ((t2 >> 5) << 2), zo = (t2 >> 2) & 7;
+  const bool dyt = w < 2 && t2 < 32 * MT;             // this thread stages dY
+  const bool bias = g.ones_col >= 0 && ti.nt == 0;    // this workgroup sums db (uniform)
+
+  float pf[32];
+  float bsum[4] = {0.f, 0.f, 0.f, 0.f};
+  auto fetch = [&](int z0) {
+    if (w < 2) {
+      if (dyt) load_t4x8(g.A, g.a_cs, z0 + 8 * zo, ze, o0 + 4 * cq, g.M, g.avec, pf);
+    } else {
+      load_t4x8(g.B, g.b_rs, z0 + 8 * zo, ze, i0 + 4 * cq, in_dim, g.bvec, pf);
+    }
+  };
+  auto stage = [&](int s) {
+    if (w < 2 && !dyt) return;
+    if (bias && dyt) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) bsum[c] += pf[4 * e + c];
+    }
+    uint4* S = w < 2 ? As[s] : Bs[s];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      float col[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) col[e] = pf[4 * e + c];
+      S[(4 * cq + c) * LDV + zo] = pack8(col);
+    }
+  };
+
+  f32x4 acc[NA];
+#pragma unroll
+  for (int t = 0; t < NA; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const int lm = l & 15, lg = l >> 4;
+  const int ar = MT == 4 ? 16 * w : 0, br = MT == 4 ? 0 : 16 * w;
+  if (nc > 0) {
+    fetch(zb);
+    stage(0);
+  }
+  __syncthreads();
+  for (int c = 0; c < nc; ++c) {
+    const bool more = c + 1 < nc;
+    if (more) fetch(zb + (c + 1) * kLinBfChunk);
+    const uint4* ap = As[c & 1] + (ar + lm) * LDV + lg;
+    const uint4* bp = Bs[c & 1] + (br + lm) * LDV + lg;
+    uint4 a[2], b[NA][2];
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk) {
+      a[kk] = ap[4 * kk];
+#pragma unroll
+      for (int t = 0; t < NA; ++t) b[t][kk] = bp[16 * t * LDV + 4 * kk];
+    }
+#pragma unroll
+    for (int kk = 0; kk < 2; ++kk)
+#pragma unroll
+      for (int t = 0; t < NA; ++t) acc[t] = mfma32(a[kk], b[t][kk], acc[t]);
+    if (more) stage((c + 1) & 1);
+    __syncthreads();
+  }
+
+  // epilogue: D[out row 4 lg + e][in column lm] of each accumulator
+#pragma unroll
+  for (int t = 0; t < NA; ++t) {
+    const int i = i0 + br + 16 * t + lm;
+    if (i >= in_dim) continue;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int o = o0 + ar + 4 * lg + e;
+      if (o >= g.M) continue;
+      const float v = acc[t][e];
+      if (g.part) {                                   // slab: raw sums
+        g.part[((int64_t)ti.z * g.M + o) * g.N + i] = v;
+      } else {
+        float* d = g.C + (int64_t)o * g.ldc + i;
+        *d = g.accumulate ? *d + v : v;
+      }
+    }
+  }
+  if (!bias) return;
+  if (dyt) {
+#pragma unroll
+    for (int c = 0; c < 4; ++c) dbs[zo][4 * cq + c] = bsum[c];
+  }
+  __syncthreads();
+  const int o = o0 + tid;
+  if (tid >= AR || o >= g.M) return;
+  float s = dbs[0][tid];
+#pragma unroll
+  for (int z = 1; z < 8; ++z) s += dbs[z][tid];
+  if (g.part) g.part[((int64_t)ti.z * g.M + o) * g.N + g.ones_col] = s;
+  else g.bias_out[o] = g.accumulate ? g.bias_out[o] + s : s;
+}
+
 // ------------------------------------------------------------------- host
 static int linear_bf16_launch(int epi, GemmArgs g, hipStream_t st) {
   if (g.M <= 0) return SMI_OK;
@@ -318,6 +464,42 @@ int launch_linear_bwd_dx_bf16(const float* dY, int64_t ldg, int M, int N, const 
   g.B = W; g.b_rs = ldw; g.b_cs = 1;        // B(z = n', j = k') = W[n'][k']
   g.C = dX; g.ldc = lddx; g.mask = mask; g.ldm = ldm; g.ones_col = -1; g.skip = skip;
   return linear_bf16_launch(EPI_DX, g, st);
+}
+
+// launches at the call: never queued into an open dW group, whose state it
+// does not read or change (the group's partials are placed at its flush)
+int launch_linear_bwd_dw_bf16(const float* dY, int64_t ldg, int M, int N, const float* X,
+                              int64_t ldx, int K, float* dW, int64_t lddw, float* db,
+                              int accumulate, hipStream_t st, const int* skip) {
+  if (M <= 0) return SMI_OK;
+  auto al16 = [](const float* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
+  GemmArgs g{};
+  g.M = N; g.N = db ? K + 1 : K; g.K = M;
+  g.A = dY; g.a_rs = 1; g.a_cs = ldg;       // A(o, r) = dY[r][o]
+  g.B = X; g.b_rs = ldx; g.b_cs = 1;        // B(r, i) = X[r][i]; column K: the bias gradient
+  g.C = dW; g.ldc = lddw; g.accumulate = accumulate; g.skip = skip;
+  g.ones_col = db ? K : -1;
+  g.bias_out = db;
+  // both operands are read in quads along their columns
+  g.avec = al16(dY) && ldg % 4 == 0 && N % 4 == 0;
+  g.bvec = al16(X) && ldx % 4 == 0 && K % 4 == 0;
+  const LinBfPlan pl = linear_bf16_dw_plan(N, K, M, smi_workspace_floats());
+  g.kchunk = pl.kchunk;
+  g.part = nullptr;
+  if (pl.splits > 1) {
+    g.part = workspace_f32((int64_t)pl.splits * g.M * g.N);
+    if (!g.part) return set_error(SMI_E_ARG, "linear bf16: workspace unavailable for split-K");
+  }
+  const dim3 grid(pl.gm, pl.gn, pl.splits);
+  const int kslot = ktime_begin(st);
+  if (pl.nt == 4) hipLaunchKernelGGL(linear_bf16_dw_kernel<4>, grid, dim3(kWG), 0, st, g);
+  else hipLaunchKernelGGL(linear_bf16_dw_kernel<1>, grid, dim3(kWG), 0, st, g);
+  ktime_end(kslot, KT_GEMM_DW, dw_flops(g), st);
+  const int rc = check_launch(pl.nt == 4 ? "linear_bf16_kernel<dw,64>" : "linear_bf16_kernel<dw,16>");
+  if (rc || pl.splits == 1) return rc;
+  return splitk_reduce(g, pl.splits, EPI_DW, st,
+                       pl.nt == 4 ? "gemm_splitk_reduce_kernel<linear_bf16_kernel<dw,64>>"
+                                  : "gemm_splitk_reduce_kernel<linear_bf16_kernel<dw,16>>");
 }
 
 }  // namespace smi

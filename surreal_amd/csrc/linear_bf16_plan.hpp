@@ -47,6 +47,32 @@ inline LinBfPlan linear_bf16_plan(int M, int N, int K, int64_t ws_floats) {
   return p;
 }
 
+// The weight gradient dW [out][in] = sum over the rows (linear_bf16_dw_kernel):
+// 64 x 64 tiles, or 16 (out) x 64 (in) for the head layers; nt is the count of
+// 16-row blocks along out (4 or 1), kchunk the rows of a slab.  A slab's partial
+// image holds in + 1 columns (the last: the bias gradient), whether or not the
+// call asks for db: the plan is a function of the shape alone.
+inline LinBfPlan linear_bf16_dw_plan(int out, int in, int rows, int64_t ws_floats) {
+  LinBfPlan p{};
+  p.nt = out <= kLinBfNarrow ? 1 : 4;
+  p.gm = (int)lin_bf_ceil(out, 16 * p.nt);
+  p.gn = (int)lin_bf_ceil(in, kLinBfRows);
+  const int64_t chunks = lin_bf_ceil(rows, kLinBfChunk);
+  p.splits = 1;
+  p.kchunk = (int)(chunks * kLinBfChunk);
+  const int64_t tiles = (int64_t)p.gm * p.gn;
+  if (tiles < 1 || tiles >= kLinBfFill || chunks < 4) return p;
+  int64_t want = lin_bf_ceil(kLinBfTarget, tiles);
+  if (want > chunks / 2) want = chunks / 2;            // a slab holds at least two chunks
+  const int64_t cap = ws_floats / ((int64_t)out * (in + 1));
+  if (want > cap) want = cap;
+  if (want < 2) return p;
+  const int64_t per = lin_bf_ceil(chunks, want);
+  p.splits = (int)lin_bf_ceil(chunks, per);            // no empty slab; the last may be ragged
+  p.kchunk = (int)(per * kLinBfChunk);
+  return p;
+}
+
 // static LDS of a form: two stages of the A (64 rows) and B (16 nt rows) images
 constexpr int linear_bf16_lds_bytes(int nt) { return 2 * (kLinBfRows + 16 * nt) * kLinBfLdv * 16; }
 

@@ -198,6 +198,10 @@ int launch_linear_fwd_bf16(const float* X, int64_t ldx, int M, int K, const floa
 int launch_linear_bwd_dx_bf16(const float* dY, int64_t ldg, int M, int N, const float* W,
                               int64_t ldw, int K, const float* mask, int64_t ldm, float* dX,
                               int64_t lddx, hipStream_t st, const int* skip = nullptr);
+// launch_linear_bwd_dw's arguments; dY and X rounded to bf16, db from the fp32 dY
+int launch_linear_bwd_dw_bf16(const float* dY, int64_t ldg, int M, int N, const float* X,
+                              int64_t ldx, int K, float* dW, int64_t lddw, float* db,
+                              int accumulate, hipStream_t st, const int* skip = nullptr);
 // ---- head_kernels.hip
 bool head_fused_ok(int in, int64_t ldx, int h1, int h2, int out, const float* X,
                    const float* W1, const float* W2, const float* W3);

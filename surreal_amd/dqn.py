@@ -160,6 +160,17 @@ activations and output gradients; the IQN embedding kernels, fc_tau_layer, the
 convolutions (conv_dtype), the TD kernels, Adam, the target copy, checkpoints,
 the exchange image and the publisher are untouched: nothing outside the two
 launch sites (_QNet.lin, _QNet.ndx) knows the option.
+
+model.fc_dtype = 'bf16_all' is 'bf16' plus the weight gradients: every
+smi_linear_backward_weight of _QNet.bwd (the per-layer calls of both streams
+and the joint first-layer GEMM over dH1) becomes smi_linear_backward_weight_bf16,
+which rounds dy and x while staging them, sums db in fp32 from the unrounded
+dy, and launches where it stands instead of queueing into the grouped launch
+(the group's flush then has nothing to run for them).  The forward and the
+input gradients are those of 'bf16', bit for bit; fc_tau_layer's gradient stays
+in smi_iqn_embed_backward.  The small 512-row layers lose the grouped launch
+under this value and are not routed back: a model's numerics do not depend on
+a dispatch threshold.
 """
 import numpy as np
 import torch
@@ -220,8 +231,10 @@ def dqn_specs(learner_config, env_config):
 MAX_CONVS = 4
 # model.conv_dtype -> suffix of the smi_conv2d_* symbols the conv layers run on
 CONV_DTYPES = {'fp32': '', 'bf16': '_bf16'}
-# model.fc_dtype -> suffix of smi_linear_forward / smi_linear_backward_input of the FC stack
-FC_DTYPES = {'fp32': '', 'bf16': '_bf16'}
+# model.fc_dtype -> suffixes of the FC stack's smi_linear_forward, smi_linear_backward_input
+# and smi_linear_backward_weight
+FC_DTYPES = {'fp32': ('', '', ''), 'bf16': ('_bf16', '_bf16', ''),
+             'bf16_all': ('_bf16', '_bf16', '_bf16')}
 
 
 def conv_chain(input_shape, convs):
@@ -402,7 +415,8 @@ def dqn_model_kwargs(learner_config, env_config):
     atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
     with kind 'implicit' the dict of check_implicit; model.noisy.enabled adds
     noisy = sigma0; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype;
-    model.fc_dtype = 'bf16' (not with noisy layers) adds fc_dtype.  Host only."""
+    model.fc_dtype = 'bf16' or 'bf16_all' (not with noisy layers) adds fc_dtype.
+    Host only."""
     if 'pixel' in env_config['obs_spec']:
         shape, convs, A, hidden, dueling, u8 = dqn_conv_specs(learner_config, env_config)
         D = int(np.prod(conv_chain(shape, convs)[1]))
@@ -435,11 +449,12 @@ def dqn_model_kwargs(learner_config, env_config):
         kw['noisy'] = check_noisy(noisy.get('sigma0', 0.5))
     fc_dtype = learner_config['model'].get('fc_dtype', 'fp32')
     if fc_dtype not in FC_DTYPES:
-        raise ConfigError("DQN model.fc_dtype must be 'fp32' or 'bf16', got {!r}".format(fc_dtype))
+        raise ConfigError("DQN model.fc_dtype must be 'fp32', 'bf16' or 'bf16_all', got "
+                          '{!r}'.format(fc_dtype))
     if fc_dtype != 'fp32':
         if 'noisy' in kw:
-            raise ConfigError("DQN model.fc_dtype = 'bf16' does not combine with model.noisy: the "
-                              'noisy layers run on kernels of their own')
+            raise ConfigError('DQN model.fc_dtype = {!r} does not combine with model.noisy: the '
+                              'noisy layers run on kernels of their own'.format(fc_dtype))
         kw['fc_dtype'] = fc_dtype
     return D, A, hidden, dueling, kw
 
@@ -489,8 +504,8 @@ class FFQfunc(nn.Module):
                  fc_dtype='fp32'):
         super().__init__()
         if fc_dtype not in FC_DTYPES or (fc_dtype != 'fp32' and noisy is not None):
-            raise ConfigError("FFQfunc fc_dtype is 'fp32' or, without noisy layers, 'bf16'; got "
-                              '{!r}'.format(fc_dtype))
+            raise ConfigError("FFQfunc fc_dtype is 'fp32' or, without noisy layers, 'bf16' or "
+                              "'bf16_all'; got {!r}".format(fc_dtype))
         self.fc_dtype = fc_dtype
         if conv_dtype not in CONV_DTYPES or (conv_dtype != 'fp32' and not convs):
             raise ConfigError("FFQfunc conv_dtype is 'fp32' or, with convs, 'bf16'; got "
@@ -683,7 +698,7 @@ class _QNet(LaunchNet):
 
     def lin(self, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
         """a dense layer's forward on the model's fc_dtype"""
-        L.call('smi_linear_forward' + FC_DTYPES[self.m.fc_dtype], p(x), ldx, rows, k, p(w), ldw, p(b),
+        L.call('smi_linear_forward' + FC_DTYPES[self.m.fc_dtype][0], p(x), ldx, rows, k, p(w), ldw, p(b),
                n, act, p(y), ldy, self.st)
 
     def conv_fwd(self, x, rows, pre):
@@ -778,8 +793,8 @@ class _QNet(LaunchNet):
     def ndx(self, noise, li, dy, ldg, rows, n_out, w, ldw, k, mask, ldm, dx, lddx):
         """layer li's input gradient, plain (on the model's fc_dtype) or noisy as nlin"""
         if noise is None:
-            return L.call('smi_linear_backward_input' + FC_DTYPES[self.m.fc_dtype], p(dy), ldg, rows,
-                          n_out, p(w), ldw, k, p(mask), ldm, p(dx), lddx, self.st)
+            return L.call('smi_linear_backward_input' + FC_DTYPES[self.m.fc_dtype][1], p(dy), ldg,
+                          rows, n_out, p(w), ldw, k, p(mask), ldm, p(dx), lddx, self.st)
         fi, fo = self._f(noise, li)
         L.call('smi_noisy_backward_input', p(dy), ldg, rows, n_out, p(w),
                p(self.m.flat[self.m.off(w) + self.m.sig_shift:]), ldw, k, p(fi), p(fo), p(mask), ldm,
@@ -852,11 +867,13 @@ class _QNet(LaunchNet):
     def bwd(self, x, rows, pre, douts, g, noise=None):
         """from douts[s] = d loss / d (stream s's output) into the gradient image
         g (the flat layout); the weight-gradient calls queue into the caller's
-        open group, so every dY / X buffer is written once and left alone"""
+        open group, so every dY / X buffer is written once and left alone (with
+        fc_dtype 'bf16_all' they launch where they stand, on the _bf16 twin)"""
         m = self.m
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
         st = self.st
+        dw_call = 'smi_linear_backward_weight' + FC_DTYPES[m.fc_dtype][2]
         frames = x
         if m.convs:
             x = self.bufs[f'{pre}_c{len(m.convs) - 1}'].view(rows, -1)
@@ -878,7 +895,7 @@ class _QNet(LaunchNet):
                 n_out = lin.out_features
                 xk, ldx = acts[k - 1]
                 dx, lddx = grads[k - 1]
-                L.call('smi_linear_backward_weight', p(dy), ldg, rows, n_out, p(xk), ldx, hs[k - 1],
+                L.call(dw_call, p(dy), ldg, rows, n_out, p(xk), ldx, hs[k - 1],
                        p(g[m.off(lin.weight):]), hs[k - 1], p(g[m.off(lin.bias):]), 0, st)
                 self.ndx(noise, s * len(hs) + k, dy, ldg, rows, n_out, lin.weight, hs[k - 1],
                          hs[k - 1], xk, ldx, dx, lddx)
@@ -893,7 +910,7 @@ class _QNet(LaunchNet):
                    need, st)
             rows, dH1 = B, dhid
         # both streams' first layers: one weight-gradient GEMM over dH1 [rows][S h1]
-        L.call('smi_linear_backward_weight', p(dH1), S * hs[0], rows, S * hs[0], p(x), x.stride(0),
+        L.call(dw_call, p(dH1), S * hs[0], rows, S * hs[0], p(x), x.stride(0),
                D, p(g[m.off(m.w1):]), D, p(g[m.off(m.b1):]), 0, st)
         if m.convs:
             self.conv_bwd(frames, rows, pre, dH1, g, noise)

@@ -52,9 +52,14 @@ Atari shape (B = 32 and 512, conv_dtype 'bf16' on both arms) and of the
 low-dimensional model with implicit heads (B = 512, 64 samples), eager and as a
 graph replay.
 
+--fc-bf16-all times model.fc_dtype = 'bf16_all' against 'bf16' the same way:
+smi_linear_backward_weight against smi_linear_backward_weight_bf16 at those
+shapes, one call each (the small 512-row layers also as one grouped fp32 launch
+against three bf16 calls), then the same learn() cases with 'bf16' and 'bf16_all'.
+
 Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
                                  [--pixel [--conv-bf16] | --gpus N | --atoms N | --quantiles N [--kappa K]
-                                  | --implicit [--atoms N] | --fc-bf16]
+                                  | --implicit [--atoms N] | --fc-bf16 | --fc-bf16-all]
 """
 import argparse
 import copy
@@ -528,6 +533,62 @@ def fc_main(args):
                                   'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
                                   'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
                                   'iters': args.iters}), flush=True)
+    fc_learn(args, ('fp32', 'bf16'))
+
+
+def fc_all_main(args):
+    """--fc-bf16-all: smi_linear_backward_weight against its _bf16 twin, alternating (single calls
+    per layer; the three small 512-row layers also as one grouped fp32 launch against three bf16
+    calls), then learn() with model.fc_dtype 'bf16' and 'bf16_all'"""
+    p, st = L.ptr, L.stream()
+    L.ensure_workspace('cuda')                # the learners' workspace: the row slabs need it
+    g = torch.Generator().manual_seed(0)
+
+    def dw_call(sfx, t):
+        dy, x, dw, db = t
+        (R, N), K = dy.shape, x.shape[1]
+        L.call('smi_linear_backward_weight' + sfx, p(dy), N, R, N, p(x), K, K, p(dw), K, p(db), 0, st)
+
+    def report(name, res, **kw):
+        for dtype, t in zip(('fp32', 'bf16'), res):
+            med, q1, q3 = (1e3 * v / args.calls for v in t)
+            print(json.dumps(dict({'measurement': name, 'fc_dtype': dtype}, **kw,
+                                  median_us_per_call=round(med, 2), q1_us=round(q1, 2),
+                                  q3_us=round(q3, 2), calls_per_sample=args.calls, iters=args.iters)),
+                  flush=True)
+    small = []
+    for R, K, N in ((512, 17, 256), (512, 128, 128), (512, 512, 6), (512, 3136, 1024),
+                    (32768, 128, 128), (32768, 128, 6)):
+        t = (torch.randn(R, N, generator=g).cuda(), torch.randn(R, K, generator=g).cuda(),
+             torch.zeros(N, K).cuda(), torch.zeros(N).cuda())
+        if R == 512 and K * N < 1 << 20:
+            small.append(t)
+
+        def one(sfx, t=t):
+            def run():
+                for _ in range(args.calls):
+                    dw_call(sfx, t)
+            return run
+        report('linear_backward_weight', timed_alternating([one(''), one('_bf16')], args.iters, args.warmup),
+               rows=R, out=N, **{'in': K})
+
+    def grouped():
+        for _ in range(args.calls):
+            with L.dw_group(st):
+                for t in small:
+                    dw_call('', t)
+
+    def apart():
+        for _ in range(args.calls):
+            for t in small:
+                dw_call('_bf16', t)
+    report('linear_backward_weight_small3', timed_alternating([grouped, apart], args.iters, args.warmup),
+           rows=512, layers='17->256, 128->128, 512->6: fp32 one grouped launch, bf16 three calls')
+    fc_learn(args, ('bf16', 'bf16_all'))
+
+
+def fc_learn(args, arms):
+    """learn() with model.fc_dtype on the two arms, alternating step by step"""
     D, A, shape = 17, 6, (4, 84, 84)
     cases = []
     for B in (32, 512):
@@ -544,13 +605,13 @@ def fc_main(args):
     for name, B, lc, ec, b in cases:
         for graph in (False, True):
             learners = []
-            for dtype in ('fp32', 'bf16'):
+            for dtype in arms:
                 lc.model.fc_dtype = dtype
                 learners.append(DQNLearner(lc, ec, seed=0, use_graph=graph))
             res = timed_alternating([lambda ln=ln: ln.learn(b) for ln in learners], args.iters,
                                     args.warmup)
-            for dtype, (med, q1, q3) in zip(('fp32', 'bf16'), res):
-                print(json.dumps({'measurement': name + ('_graph' if graph else '_eager'), 'B': B,
+            for dtype, (med, q1, q3) in zip(arms, res):
+                print(json.dumps({'measurement': name +('_graph' if graph else '_eager'), 'B': B,
                                   'fc_dtype': dtype, 'median_ms': round(med, 4), 'q1_ms': round(q1, 4),
                                   'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
             del learners
@@ -576,6 +637,8 @@ def main():
                          '--quantiles, --implicit and --pixel')
     ap.add_argument('--fc-bf16', action='store_true',
                     help="model.fc_dtype = 'bf16' against 'fp32': the FC layers and learn()")
+    ap.add_argument('--fc-bf16-all', action='store_true',
+                    help="model.fc_dtype = 'bf16_all' against 'bf16': the FC weight gradients and learn()")
     ap.add_argument('--kappa', type=float, default=1.0,
                     help='--quantiles: the Huber threshold (0: the pinball loss)')
     ap.add_argument('--calls', type=int, default=20,
@@ -583,6 +646,8 @@ def main():
     args = ap.parse_args()
     if args.gpus != 1:
         return dp_main(args)
+    if args.fc_bf16_all:
+        return fc_all_main(args)
     if args.fc_bf16:
         return fc_main(args)
     if args.noisy:
