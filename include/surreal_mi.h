@@ -1291,6 +1291,31 @@ int smi_noisy_backward_input(const float* dy, int64_t ldg, int rows, int out_dim
                              const float* w_mu, const float* w_sig, int64_t ldw, int in_dim,
                              const float* f_in, const float* f_out, const float* relu_mask,
                              int64_t ldm, float* dx, int64_t lddx, void* stream);
+/* The same two calls with bf16 operands (model.noisy.dtype = 'bf16' / 'bf16_all'
+ * of the DQN model; noisy_bf16_kernels.hip): same arguments, same refusals, fp32
+ * tensors in memory, v_mfma_f32_16x16x32_bf16 with fp32 sums.  With bf16() =
+ * round to nearest even (NaN and infinities preserved):
+ *   y[r][o]  = act((S_mu + b_mu[o]) + f_out[o] * (S_sig + b_sig[o]))
+ *     S_mu  = sum_i bf16(x[r][i])           * bf16(w_mu[o][i])
+ *     S_sig = sum_i bf16(x[r][i] * f_in[i]) * bf16(w_sig[o][i])
+ *   dx[r][i] = [relu_mask[r][i] > 0] * (T_mu + f_in[i] * T_sig)
+ *     T_mu  = sum_o bf16(dy[r][o])            * bf16(w_mu[o][i])
+ *     T_sig = sum_o bf16(dy[r][o] * f_out[o]) * bf16(w_sig[o][i])
+ * The product with the noise is one fp32 multiply of the unrounded value,
+ * rounded once afterwards; the epilogue is fp32 in the order written.  64 x 64
+ * tiles, 64 x 16 for out_dim (dX: in_dim) <= 16; a reduction of at least 256
+ * under fewer than 256 tiles is split over slabs with a fixed-order reducer
+ * (partials of both sums in the library workspace, no atomics: two calls give
+ * the same bits).  smi_last_launch: "noisy_bf16_kernel<fwd|dx,64|16>", split:
+ * "noisy_bf16_reduce_kernel<noisy_bf16_kernel<..>>". */
+int smi_noisy_forward_bf16(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                           const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                           const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                           int64_t ldy, void* stream);
+int smi_noisy_backward_input_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                  const float* w_mu, const float* w_sig, int64_t ldw, int in_dim,
+                                  const float* f_in, const float* f_out, const float* relu_mask,
+                                  int64_t ldm, float* dx, int64_t lddx, void* stream);
 /* The sigma gradients of every layer of a net from its mu gradients, one launch:
  *   g_sig[w_off + o in + i] = g_mu[w_off + o in + i] * (f_out[o] * f_in[i])
  *   g_sig[b_off + o]        = g_mu[b_off + o] * f_out[o]

@@ -251,6 +251,10 @@ _SIGS = {
                                   c_i64, P]),
     'smi_noisy_backward_input': (c_int, [P, c_i64, c_int, c_int, P, P, c_i64, c_int, P, P, P, c_i64,
                                          P, c_i64, P]),
+    'smi_noisy_forward_bf16': (c_int, [P, c_i64, c_int, c_int, P, P, c_i64, P, P, P, P, c_int, c_int,
+                                       P, c_i64, P]),
+    'smi_noisy_backward_input_bf16': (c_int, [P, c_i64, c_int, c_int, P, P, c_i64, c_int, P, P, P,
+                                              c_i64, P, c_i64, P]),
     'smi_noisy_sigma_grad': (c_int, [P, P, P, c_int, NoisyTable, P]),
     'smi_neg_mean_grad': (c_int, [P, c_i64, c_i64, P, P, P]),
     'smi_tanh_backward': (c_int, [P, c_i64, P, c_i64, c_i64, c_int, P, c_i64, P]),

@@ -17,7 +17,7 @@ LIB = os.path.join(HERE, 'libsurreal_mi.so')
 HEADERS = ['smi_device.hpp', 'smi_internal.hpp', 'lstm_cell.hpp', 'pol_rows.hpp', 'mt19937.hpp',
            'gemm_args.hpp', 'dw_plan.hpp', 'smi_shapes.hpp', 'smi_launch.hpp', 'rnn_layout.hpp',
            'rnn_kernels.hpp', 'conv_plan.hpp', 'conv_bf16_plan.hpp', 'stem_plan.hpp', 'dqn_rows.hpp', 'philox.hpp',
-           'bf16_stage.hpp', 'linear_bf16_plan.hpp']
+           'bf16_stage.hpp', 'bf16_loads.hpp', 'linear_bf16_plan.hpp']
 HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
 ARCH = 'gfx950'
 CXXFLAGS = ['-O3', '-fPIC', '-std=c++17', f'--offload-arch={ARCH}', '-mcode-object-version=5',
@@ -39,7 +39,7 @@ UNITS = [('ppo_gae.hip', []), ('ppo_epochs.hip', []), ('ops_kernels.hip', []),
          ('ddpg_kernels.hip', []),
          ('dqn_kernels.hip', []), ('dqn_dist_kernels.hip', NO_PK_F32),
          ('dqn_quant_kernels.hip', NO_PK_F32), ('dqn_iqn_kernels.hip', NO_PK_F32),
-         ('noisy_kernels.hip', []),
+         ('noisy_kernels.hip', []), ('noisy_bf16_kernels.hip', []),
          ('lstm_mfma.hip', []), ('lstm_valu.hip', ['-fno-slp-vectorize']), ('cnn_kernels.hip', []),
          ('conv_kernels.hip', []), ('conv_bf16_kernels.hip', []), ('stem.hip', []),
          ('head_kernels.hip', []), ('ppo_rnn_kernels.hip', []), ('ppo_rnn.hip', []),

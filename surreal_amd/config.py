@@ -188,7 +188,10 @@ DQN_DEFAULT_LEARNER_CONFIG = Config({
         'fc_hidden_sizes': [128, 128],
         'dueling': True,
         # noisy linear layers (NoisyNet, factorised Gaussian noise) in place of
-        # every FC layer; sigma0 / sqrt(in_features) initialises every sigma entry
+        # every FC layer; sigma0 / sqrt(in_features) initialises every sigma entry.
+        # Optional key 'dtype' (read when enabled; absent = 'fp32'): the operand type of the
+        # noisy layers' MFMAs, 'fp32' | 'bf16' (forwards and input gradients) | 'bf16_all'
+        # (the mu weight gradients too); fp32 tensors and sums with every value
         'noisy': {'enabled': False, 'sigma0': 0.5},
     },
     'algo': {

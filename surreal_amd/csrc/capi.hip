@@ -802,6 +802,22 @@ int smi_noisy_backward_input(const float* dy, int64_t ldg, int rows, int out_dim
                              relu_mask, ldm, dx, lddx, SMI_STREAM(stream));
 }
 
+int smi_noisy_forward_bf16(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                           const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                           const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                           int64_t ldy, void* stream) {
+  return launch_noisy_fwd_bf16(x, ldx, rows, in_dim, w_mu, w_sig, ldw, b_mu, b_sig, f_in, f_out,
+                               out_dim, act, y, ldy, SMI_STREAM(stream));
+}
+
+int smi_noisy_backward_input_bf16(const float* dy, int64_t ldg, int rows, int out_dim,
+                                  const float* w_mu, const float* w_sig, int64_t ldw, int in_dim,
+                                  const float* f_in, const float* f_out, const float* relu_mask,
+                                  int64_t ldm, float* dx, int64_t lddx, void* stream) {
+  return launch_noisy_bwd_dx_bf16(dy, ldg, rows, out_dim, w_mu, w_sig, ldw, in_dim, f_in, f_out,
+                                  relu_mask, ldm, dx, lddx, SMI_STREAM(stream));
+}
+
 int smi_noisy_sigma_grad(const float* g_mu_base, float* g_sig_base, const float* f_image,
                          int n_layers, smi_noisy_table table, void* stream) {
   return launch_noisy_sigma_grad(g_mu_base, g_sig_base, f_image, n_layers, table,

@@ -146,6 +146,16 @@ int launch_noisy_bwd_dx(const float* dy, int64_t ldg, int rows, int out_dim, con
                         int64_t lddx, hipStream_t st);
 int launch_noisy_sigma_grad(const float* g_mu_base, float* g_sig_base, const float* f_image,
                             int n_layers, const smi_noisy_table& tab, hipStream_t st);
+// ---- noisy_bf16_kernels.hip (launch_noisy_fwd / launch_noisy_bwd_dx with bf16
+// operands on the bf16 MFMA, fp32 tensors and sums; the same argument checks)
+int launch_noisy_fwd_bf16(const float* x, int64_t ldx, int rows, int in_dim, const float* w_mu,
+                          const float* w_sig, int64_t ldw, const float* b_mu, const float* b_sig,
+                          const float* f_in, const float* f_out, int out_dim, int act, float* y,
+                          int64_t ldy, hipStream_t st);
+int launch_noisy_bwd_dx_bf16(const float* dy, int64_t ldg, int rows, int out_dim, const float* w_mu,
+                             const float* w_sig, int64_t ldw, int in_dim, const float* f_in,
+                             const float* f_out, const float* mask, int64_t ldm, float* dx,
+                             int64_t lddx, hipStream_t st);
 // ---- conv_kernels.hip (one general convolution layer; arguments checked by the caller)
 // skip: device stop flag (a launch whose flag is set writes nothing; NULL: run).
 // rows: the uint8 images come through the learners' time-major row map

@@ -171,6 +171,24 @@ input gradients are those of 'bf16', bit for bit; fc_tau_layer's gradient stays
 in smi_iqn_embed_backward.  The small 512-row layers lose the grouped launch
 under this value and are not routed back: a model's numerics do not depend on
 a dispatch threshold.
+
+bf16 noisy layers (model.noisy.dtype = 'bf16', an optional key of the noisy
+table read only when it is enabled; absent or 'fp32': the fp32 kernels;
+noisy_bf16_kernels.hip): every smi_noisy_forward and smi_noisy_backward_input
+(every launch of _QNet.nlin / _QNet.ndx that takes a noise image) becomes its
+_bf16 twin, same arguments and one launch each (a split reduction adds its
+reducer).  x, x (.) f_in, dy, dy (.) f_out, W_mu and W_sig are rounded to bf16
+(nearest even) while the kernel stages them, the product with the noise being
+one fp32 multiply of the unrounded value rounded once; sums, biases, f_out /
+f_in in the epilogue, ReLU and masks are fp32.  'bf16_all' also puts the mu
+weight gradients of _QNet.bwd (plain dy^T x) on smi_linear_backward_weight_bf16,
+launched where they stand as under fc_dtype 'bf16_all'; smi_noisy_sigma_grad
+runs after them, unchanged.  Without a noise image (eval agents, forward() in
+eval mode) the plain fp32 layers run on the mu parameters as before.  The
+value is kept as q_func.noisy_dtype and carried by clone(); nothing outside
+those launch sites knows it: QAgentBatch, data parallelism, graph replay,
+checkpoints and the publisher are the fp32 noisy model's.  model.fc_dtype
+other than 'fp32' with noisy layers stays a ConfigError.
 """
 import numpy as np
 import torch
@@ -235,6 +253,9 @@ CONV_DTYPES = {'fp32': '', 'bf16': '_bf16'}
 # and smi_linear_backward_weight
 FC_DTYPES = {'fp32': ('', '', ''), 'bf16': ('_bf16', '_bf16', ''),
              'bf16_all': ('_bf16', '_bf16', '_bf16')}
+# model.noisy.dtype -> suffixes of smi_noisy_forward / smi_noisy_backward_input and of the mu
+# weight gradients' smi_linear_backward_weight, of the launches that take a noise image
+NOISY_DTYPES = {'fp32': ('', ''), 'bf16': ('_bf16', ''), 'bf16_all': ('_bf16', '_bf16')}
 
 
 def conv_chain(input_shape, convs):
@@ -414,7 +435,8 @@ def dqn_model_kwargs(learner_config, env_config):
     spec with pixels, dqn_specs otherwise; algo.distributional.enabled adds
     atoms, v_min and v_max, with kind 'quantile' quantiles and kappa instead,
     with kind 'implicit' the dict of check_implicit; model.noisy.enabled adds
-    noisy = sigma0; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype;
+    noisy = sigma0 and, with model.noisy.dtype = 'bf16' or 'bf16_all' (an optional
+    key, read only then), noisy_dtype; model.conv_dtype = 'bf16' (pixels only) adds conv_dtype;
     model.fc_dtype = 'bf16' or 'bf16_all' (not with noisy layers) adds fc_dtype.
     Host only."""
     if 'pixel' in env_config['obs_spec']:
@@ -447,6 +469,12 @@ def dqn_model_kwargs(learner_config, env_config):
     noisy = learner_config['model'].get('noisy') or {}
     if noisy.get('enabled', False):
         kw['noisy'] = check_noisy(noisy.get('sigma0', 0.5))
+        noisy_dtype = noisy.get('dtype', 'fp32')
+        if noisy_dtype not in NOISY_DTYPES:
+            raise ConfigError("DQN model.noisy.dtype must be 'fp32', 'bf16' or 'bf16_all', got "
+                              '{!r}'.format(noisy_dtype))
+        if noisy_dtype != 'fp32':
+            kw['noisy_dtype'] = noisy_dtype
     fc_dtype = learner_config['model'].get('fc_dtype', 'fp32')
     if fc_dtype not in FC_DTYPES:
         raise ConfigError("DQN model.fc_dtype must be 'fp32', 'bf16' or 'bf16_all', got "
@@ -501,8 +529,12 @@ class FFQfunc(nn.Module):
     def __init__(self, D_in, action_dim, fc_hidden_sizes, dueling, device=None, generator=None,
                  convs=None, input_shape=None, is_uint8=False, atoms=None, v_min=None, v_max=None,
                  quantiles=None, kappa=1.0, implicit=None, noisy=None, conv_dtype='fp32',
-                 fc_dtype='fp32'):
+                 fc_dtype='fp32', noisy_dtype='fp32'):
         super().__init__()
+        if noisy_dtype not in NOISY_DTYPES or (noisy_dtype != 'fp32' and noisy is None):
+            raise ConfigError("FFQfunc noisy_dtype is 'fp32' or, with noisy layers, 'bf16' or "
+                              "'bf16_all'; got {!r}".format(noisy_dtype))
+        self.noisy_dtype = noisy_dtype
         if fc_dtype not in FC_DTYPES or (fc_dtype != 'fp32' and noisy is not None):
             raise ConfigError("FFQfunc fc_dtype is 'fp32' or, without noisy layers, 'bf16' or "
                               "'bf16_all'; got {!r}".format(fc_dtype))
@@ -652,7 +684,8 @@ class FFQfunc(nn.Module):
                     input_shape=self.input_shape, is_uint8=self.is_uint8, atoms=self.atoms,
                     v_min=self.v_min, v_max=self.v_max, quantiles=self.quantiles,
                     kappa=self.kappa if self.quantiles else 1.0, implicit=self.implicit,
-                    noisy=self.noisy, conv_dtype=self.conv_dtype, fc_dtype=self.fc_dtype)
+                    noisy=self.noisy, conv_dtype=self.conv_dtype, fc_dtype=self.fc_dtype,
+                    noisy_dtype=self.noisy_dtype)
         c.copy_from(self)
         return c
 
@@ -781,12 +814,13 @@ class _QNet(LaunchNet):
 
     def nlin(self, noise, li, x, ldx, rows, k, w, ldw, b, n, act, y, ldy):
         """layer li's forward: LaunchNet.lin on the mu parameters without a
-        noise image, smi_noisy_forward with one"""
+        noise image, smi_noisy_forward (on the model's noisy_dtype) with one"""
         if noise is None:
             return self.lin(x, ldx, rows, k, w, ldw, b, n, act, y, ldy)
         sh = self.m.sig_shift
         fi, fo = self._f(noise, li)
-        L.call('smi_noisy_forward', p(x), ldx, rows, k, p(w), p(self.m.flat[self.m.off(w) + sh:]),
+        L.call('smi_noisy_forward' + NOISY_DTYPES[self.m.noisy_dtype][0], p(x), ldx, rows, k, p(w),
+               p(self.m.flat[self.m.off(w) + sh:]),
                ldw, p(b), p(self.m.flat[self.m.off(b) + sh:]), p(fi), p(fo), n, act, p(y), ldy,
                self.st)
 
@@ -796,7 +830,8 @@ class _QNet(LaunchNet):
             return L.call('smi_linear_backward_input' + FC_DTYPES[self.m.fc_dtype][1], p(dy), ldg,
                           rows, n_out, p(w), ldw, k, p(mask), ldm, p(dx), lddx, self.st)
         fi, fo = self._f(noise, li)
-        L.call('smi_noisy_backward_input', p(dy), ldg, rows, n_out, p(w),
+        L.call('smi_noisy_backward_input' + NOISY_DTYPES[self.m.noisy_dtype][0], p(dy), ldg, rows,
+               n_out, p(w),
                p(self.m.flat[self.m.off(w) + self.m.sig_shift:]), ldw, k, p(fi), p(fo), p(mask), ldm,
                p(dx), lddx, self.st)
 
@@ -868,12 +903,14 @@ class _QNet(LaunchNet):
         """from douts[s] = d loss / d (stream s's output) into the gradient image
         g (the flat layout); the weight-gradient calls queue into the caller's
         open group, so every dY / X buffer is written once and left alone (with
-        fc_dtype 'bf16_all' they launch where they stand, on the _bf16 twin)"""
+        fc_dtype 'bf16_all', or noisy_dtype 'bf16_all' and a noise image, they
+        launch where they stand, on the _bf16 twin)"""
         m = self.m
         D, hs, A = m.dims
         S = 2 if m.dueling else 1
         st = self.st
-        dw_call = 'smi_linear_backward_weight' + FC_DTYPES[m.fc_dtype][2]
+        dw_call = 'smi_linear_backward_weight' + (
+            FC_DTYPES[m.fc_dtype][2] if noise is None else NOISY_DTYPES[m.noisy_dtype][1])
         frames = x
         if m.convs:
             x = self.bufs[f'{pre}_c{len(m.convs) - 1}'].view(rows, -1)

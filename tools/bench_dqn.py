@@ -57,9 +57,15 @@ smi_linear_backward_weight against smi_linear_backward_weight_bf16 at those
 shapes, one call each (the small 512-row layers also as one grouped fp32 launch
 against three bf16 calls), then the same learn() cases with 'bf16' and 'bf16_all'.
 
+--noisy --noisy-bf16 / --noisy-bf16-all time model.noisy.dtype = 'bf16' /
+'bf16_all' against 'fp32', the two arms alternating: smi_noisy_forward and
+smi_noisy_backward_input against their _bf16 twins at the shapes of --fc-bf16,
+then --noisy's learn() (with --pixel, --implicit, .. as there) on the two values.
+
 Usage: python tools/bench_dqn.py [--iters 40] [--warmup 10]
                                  [--pixel [--conv-bf16] | --gpus N | --atoms N | --quantiles N [--kappa K]
-                                  | --implicit [--atoms N] | --fc-bf16 | --fc-bf16-all]
+                                  | --implicit [--atoms N] | --fc-bf16 | --fc-bf16-all
+                                  | --noisy [--noisy-bf16 | --noisy-bf16-all]]
 """
 import argparse
 import copy
@@ -456,8 +462,11 @@ def noisy_main(args):
     smi_linear_forward at the FC shapes of the low-dim default and of the pixel model"""
     B, D, A = 512, 17, 6
     p, st = L.ptr, L.stream()
+    dtype = 'bf16_all' if args.noisy_bf16_all else 'bf16' if args.noisy_bf16 else None
+    if dtype:
+        noisy_bf16_layers(args)
     g = torch.Generator().manual_seed(0)
-    for K, N in ((17, 256), (128, 128), (128, 6), (3136, 1024), (512, 6)):
+    for K, N in () if dtype else ((17, 256), (128, 128), (128, 6), (3136, 1024), (512, 6)):
         x, y = torch.randn(B, K, generator=g).cuda(), torch.zeros(B, N).cuda()
         w, ws, b, bs = (torch.randn(*sh, generator=g).cuda() / K ** 0.5 for sh in ((N, K), (N, K), (N,), (N,)))
         fi, fo = torch.randn(K, generator=g).cuda(), torch.randn(N, generator=g).cuda()
@@ -491,7 +500,18 @@ def noisy_main(args):
         lc.algo.distributional.update(enabled=True, kind='quantile', atoms=args.quantiles, kappa=args.kappa)
     elif args.atoms:
         lc.algo.distributional.update(enabled=True, atoms=args.atoms)
-    for noisy_on in (False, True):
+    for graph in (False, True) if dtype else ():      # the noisy step on 'fp32' and on dtype, alternating
+        learners = []
+        for arm in ('fp32', dtype):
+            lc.model.noisy.update(enabled=True, dtype=arm)
+            learners.append(DQNLearner(lc, ec, seed=0, use_graph=graph))
+        res = timed_alternating([lambda ln=ln: ln.learn(b) for ln in learners], args.iters, args.warmup)
+        for arm, (med, q1, q3) in zip(('fp32', dtype), res):
+            print(json.dumps({'measurement': 'dqn_learn_' + ('graph' if graph else 'eager'), 'noisy': True,
+                              'noisy_dtype': arm, 'pixel': bool(args.pixel), 'median_ms': round(med, 4),
+                              'q1_ms': round(q1, 4), 'q3_ms': round(q3, 4), 'iters': args.iters}), flush=True)
+        del learners
+    for noisy_on in () if dtype else (False, True):
         lc.model.noisy.enabled = noisy_on
         for graph in (False, True):
             learner = DQNLearner(lc, ec, seed=0, use_graph=graph)
@@ -501,6 +521,43 @@ def noisy_main(args):
                               'q1_ms': round(q1, 4), 'q3_ms': round(q3, 4), 'iters': args.iters}),
                   flush=True)
             del learner
+
+
+def noisy_bf16_layers(args):
+    """--noisy --noisy-bf16[-all]: smi_noisy_forward and smi_noisy_backward_input against their
+    _bf16 twins, alternating, at the FC shapes of the DQN models (512 rows, and the 32768 sample
+    rows of implicit heads at B = 512, N = 64)"""
+    p, st = L.ptr, L.stream()
+    L.ensure_workspace('cuda')                # the split reductions need it
+    g = torch.Generator().manual_seed(0)
+    for R, K, N in ((512, 17, 256), (512, 128, 128), (512, 128, 6), (512, 512, 6), (512, 3136, 1024),
+                    (32768, 128, 128), (32768, 128, 6)):
+        x, y = torch.randn(R, K, generator=g).cuda(), torch.zeros(R, N).cuda()
+        w, ws, b, bs = (torch.randn(*sh, generator=g).cuda() / K ** 0.5 for sh in ((N, K), (N, K), (N,), (N,)))
+        fi, fo = torch.randn(K, generator=g).cuda(), torch.randn(N, generator=g).cuda()
+        dy, dx = torch.randn(R, N, generator=g).cuda(), torch.zeros(R, K).cuda()
+
+        def fwd(sfx):
+            def run():
+                for _ in range(args.calls):
+                    L.call('smi_noisy_forward' + sfx, p(x), K, R, K, p(w), p(ws), K, p(b), p(bs), p(fi),
+                           p(fo), N, 1, p(y), N, st)
+            return run
+
+        def bwd(sfx):
+            def run():
+                for _ in range(args.calls):
+                    L.call('smi_noisy_backward_input' + sfx, p(dy), N, R, N, p(w), p(ws), K, K, p(fi),
+                           p(fo), p(x), K, p(dx), K, st)
+            return run
+        for name, mk in (('noisy_forward', fwd), ('noisy_backward_input', bwd)):
+            res = timed_alternating([mk(''), mk('_bf16')], args.iters, args.warmup)
+            for arm, t in zip(('fp32', 'bf16'), res):
+                med, q1, q3 = (1e3 * v / args.calls for v in t)
+                print(json.dumps({'measurement': name, 'noisy_dtype': arm, 'rows': R, 'in': K, 'out': N,
+                                  'median_us_per_call': round(med, 2), 'q1_us': round(q1, 2),
+                                  'q3_us': round(q3, 2), 'calls_per_sample': args.calls,
+                                  'iters': args.iters}), flush=True)
 
 
 def fc_main(args):
@@ -635,6 +692,10 @@ def main():
     ap.add_argument('--noisy', action='store_true',
                     help='noisy linear layers against the plain ones; combines with --atoms, '
                          '--quantiles, --implicit and --pixel')
+    ap.add_argument('--noisy-bf16', action='store_true',
+                    help="--noisy with model.noisy.dtype = 'bf16' against 'fp32': the noisy layers and learn()")
+    ap.add_argument('--noisy-bf16-all', action='store_true',
+                    help="--noisy with model.noisy.dtype = 'bf16_all' against 'fp32'")
     ap.add_argument('--fc-bf16', action='store_true',
                     help="model.fc_dtype = 'bf16' against 'fp32': the FC layers and learn()")
     ap.add_argument('--fc-bf16-all', action='store_true',
@@ -650,7 +711,7 @@ def main():
         return fc_all_main(args)
     if args.fc_bf16:
         return fc_main(args)
-    if args.noisy:
+    if args.noisy or args.noisy_bf16 or args.noisy_bf16_all:
         return noisy_main(args)
     if args.implicit:
         return implicit_main(args)
